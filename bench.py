@@ -11,9 +11,12 @@ wall time of the K timed steps.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W        # one rank per GPU, RCCL weight broadcast, no step collective
 
-Extra legs on rank 0 at N=1: `roofline` (dominant kernel of the decode step, hipEvent-timed on the engine
-stream at mid-generation slot state, cycling over the layers so operands are HBM-cold as inside the step) and
-`cpu_baseline` (the reference's CPU path for this hot path, one utterance, on the box's host cores).
+A plain run sets up, warms up, times the K steps and prints the result line.  `--full` adds the untimed extra legs:
+`phase_ms` (a serial pass of one batch on one engine, phase by phase), on rank 0 `roofline` (dominant kernel of the
+decode step, hipEvent-timed on the engine stream at mid-generation slot state, cycling over the layers so operands are
+HBM-cold as inside the step), at N=1 `cpu_baseline` (the reference's CPU path for this hot path, one utterance, on the
+box's host cores) and the `continuous` sub-record.  `--dump-outputs DIR` writes what the last timed step computed
+(codec-token ids, a seeded sample of the waveforms) as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -171,7 +174,7 @@ def continuous_leg(static_value, a):
     import subprocess
     req = int(os.environ.get("NTTS_BENCH_CONT_REQUESTS", "32768"))    # (16 generations of the gang's 2048 slots, ~ 48 s: the finite job's ramp and drain cost 4 % of half that job, 1 / 4 of an eighth's time)
     cmd = [sys.executable, os.path.abspath(__file__), "--mode", "continuous", "--requests", str(req), "--steps", "1", "--warmup", "1", "--warmup-requests", str(req // 8),
-           "--no-cpu-baseline", "--no-roofline", "--gang", str(max(1, a.gang)), "--prefill", str(a.prefill), "--decode", str(a.decode)]
+           "--full", "--no-cpu-baseline", "--no-roofline", "--gang", str(max(1, a.gang)), "--prefill", str(a.prefill), "--decode", str(a.decode)]
     if os.environ.get("NTTS_BENCH_CONT_SLOTS"):
         cmd += ["--engine-slots", os.environ["NTTS_BENCH_CONT_SLOTS"]]
     t0 = time.time()
@@ -280,7 +283,14 @@ def main():
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-codec", action="store_true", help="backbone only (profiling aid; not the headline metric)")
     ap.add_argument("--tiny", action="store_true", help="tiny model geometry (plumbing tests only; not a benchmark)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the untimed extra legs: phase split, roofline, CPU baseline, continuous sub-record (a plain run only times the steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="static mode: write the last timed step's outputs as DIR/<name>.npy (codes: the batch's codec-token ids; waveforms: a "
+                         "seeded sample of its utterances; waveform_rows: which ones), float32 / float64")
     a = ap.parse_args()
+    if a.dump_outputs and (a.mode != "static" or a.no_codec):
+        ap.error("--dump-outputs: static mode with the codec only")
     # Plumbing-test hook (tests/test_dist_gloo.py): run the launch / shard / broadcast / timing logic on CPU
     # ranks over gloo against the SIMT-emulator build of the library.  Never set for a measurement.
     emu_lib = os.environ.get("NTTS_BENCH_EMU_LIB")
@@ -672,6 +682,7 @@ def main():
         return ph, None, wavs
 
     pending = []                                          # codec passes in flight: (codec engine, the lens buffer its export filled)
+    last_out = []                                         # the latest step's outputs, per engine: (codes buffer, rows, waveforms)
     pstate = {"cur": 0, "ready": [0, 0]}                  # pipelined static mode: whose turn it is, how many prefilled batches each gang holds
     async_codec = os.environ.get("NTTS_BENCH_ASYNC_CODEC", "1") != "0"
     gangs = ([list(range(0, G)), list(range(G, 2 * G))] if NG == 2 else [list(range(G)), list(range(G))]) if pipe else [[0], [0]]     # engine indices
@@ -740,9 +751,11 @@ def main():
             assert (n_new == N).all() and (st == 2).all(), "bench run did not produce the expected tokens"
         if codec is not None:
             finish_pending()                                        # gang k - 1's waveforms have left the codec engines' pinned buffers
+            last_out.clear()
             for j, e in zip(gangs[i], cur):
                 wavs = codecs[j].decode_device(codes_ptrs[j], N, np.full(B, N, dtype=np.int32), producer_stream=e.stream())
                 pending.append((codecs[j], lens_bufs[j]))
+                last_out.append((codes_bufs[j], B, wavs))
                 assert wavs.shape == (B, ccfg.hop_length * N)
         tw.append(time.time())
         for e in cur:
@@ -780,10 +793,12 @@ def main():
         wavs = None
         if codec is not None:
             finish_pending()                                        # the previous step's waveforms have left the pinned buffers (enqueued a whole decode phase ago)
+            last_out.clear()
             for j, (e, r) in enumerate(zip(cur, rows)):
                 e.export_codes(list(range(r)), 0, n_codes, codes_ptrs[j], N, lens_ptrs[j], modulo=True)
                 wavs = codecs[j].decode_device(codes_ptrs[j], N, np.full(r, N, dtype=np.int32), producer_stream=e.stream())
                 pending.append((codecs[j], lens_bufs[j], r))
+                last_out.append((codes_bufs[j], r, wavs))
         for e, r in zip(cur, rows):
             st, n_new = e.poll()                                    # blocking: this batch's decode (+ export) done
             assert (n_new[:r] == N).all() and (st[:r] == 2).all(), "bench run did not produce the expected tokens"
@@ -863,6 +878,7 @@ def main():
             ph["handoff_host"] = (time.time() - th) * 1e3
             tc = time.time()
             wavs = codec.decode_device(codes_ptr, N, np.full(B, N, dtype=np.int32), producer_stream=eng.stream())
+            last_out[:] = [(codes_buf, B, wavs)]
             if async_codec and not collect:
                 # batch k's codec pass and the D2H of its waveforms run on the codec engine's stream while the host releases the slots
                 # and enqueues batch k + 1's prompt pass (independent data; the pass is waited for before its buffers are reused and
@@ -983,16 +999,37 @@ def main():
         host_stats = {"host_ms_in_calls_per_step": {"max_over_ranks": float(hmax[0]), "mean_over_ranks": float(hsum[0]) / world},
                       "step_wall_ms": {"max_over_ranks": float(hmax[1]), "mean_over_ranks": float(hsum[1]) / world}}
 
-    # ---- untimed extra legs (phase split, roofline of the dominant kernel, CPU baseline)
+    if a.dump_outputs and rank == 0:
+        # the last timed step = the last batch of Q utterances of the last gang step (its rows dealt out over the engines in order); a seeded
+        # sample of its utterances, as many as keep the files within 64 MB (64 at the default shape: 31 MB)
+        offs = np.cumsum([0] + [r for _, r, _ in last_out])
+        L = ccfg.hop_length * N
+        n = max(1, min(Q, 64, (64 << 20) // (4 * (N + L) + 8)))
+        sel = np.sort(np.random.default_rng(0).choice(Q, size=n, replace=False))
+        codes, wav = [], []
+        for g in offs[-1] - Q + sel:
+            k = int(np.searchsorted(offs, g, side="right")) - 1
+            cb, row = last_out[k][0], int(g - offs[k])
+            codes.append(np.asarray(cb[row] if emu_lib else cb[row].cpu().numpy()))
+            wav.append(last_out[k][2][row])
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        for name, arr in (("codes", np.stack(codes).astype(np.float32)), ("waveforms", np.stack(wav).astype(np.float32)),
+                          ("waveform_rows", sel.astype(np.float64))):
+            np.save(os.path.join(a.dump_outputs, name + ".npy"), arr)
+        stage(f"outputs of the last timed step written to {a.dump_outputs} ({n} of {Q} utterances)")
+
+    # ---- untimed extra legs, --full only (phase split, roofline of the dominant kernel, CPU baseline, continuous sub-record)
     gang_shape = pipe and G > 1 and os.environ.get("NTTS_BENCH_GANG_SHAPE", "1") != "0"
-    if gang_shape:
-        eng.set_gang(1)      # the serial pass and the per-kernel replays below describe ONE engine alone: its single-chain decode shape
-    ph, ids, wavs = one_step(collect=True)
-    if wavs is not None:
-        assert np.isfinite(wavs[:4]).all(), "non-finite waveform"
+    ph = None
+    if a.full:
+        if gang_shape:
+            eng.set_gang(1)      # the serial pass and the per-kernel replays below describe ONE engine alone: its single-chain decode shape
+        ph, ids, wavs = one_step(collect=True)
+        if wavs is not None:
+            assert np.isfinite(wavs[:4]).all(), "non-finite waveform"
     roof = None
     step_info = None
-    if rank == 0 and not a.no_roofline and not cont and not strm:
+    if rank == 0 and a.full and not a.no_roofline and not cont and not strm:
         # slot state at mid-generation (mean context S + N/2 ~ 625): prefill everything, decode N/2 steps
         for c in range(0, B, a.prefill_chunk):
             n = min(a.prefill_chunk, B - c)
@@ -1159,7 +1196,7 @@ def main():
         for s in range(B):
             eng.release(s)
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if rank == 0 and world == 1 and a.full and not a.no_cpu_baseline:
         cpu = cpu_baseline(cfg, w, prompts[0], N, eos, ccfg, cw)
 
     if rank == 0:
@@ -1175,11 +1212,12 @@ def main():
         elif B == 1 and world == 1:
             workload = f"NeuTTS-Air bf16 1xMI355X, batch=1, {S} prefill / {N} decode tokens (BASELINE.json configs[1])"
         else:
-            one_eng = (B * N / ((ph["prefill"] + ph["decode"] + ph["codec"]) * 1e-3)) if (pipe and all(k in ph for k in ("prefill", "decode", "codec")) and ph["decode"] > 0) else None
+            one_eng = (B * N / ((ph["prefill"] + ph["decode"] + ph["codec"]) * 1e-3)) if (pipe and ph and all(k in ph for k in ("prefill", "decode", "codec")) and ph["decode"] > 0) else None
             head = (f"NeuTTS-Air bf16 {world}xMI355X: {(G * B) // Q} batches of {Q} IN FLIGHT per GPU ({G * B} resident"
-                    + (f" on {G} engines of {B} slots, each stepping its rows in lock-step" if B > Q else "") + f"; ONE {B}-slot engine alone = "
-                    f"{one_eng / 1e3:.1f}k tok/s" + ("; 4 x 256 in flight, round 5's shape: 166.2 k, profiles/r06f_bench.json" if (B > Q and Q == 256 and G == 4) else "") + "), "
-                    if (pipe and G > 1 and one_eng) else f"NeuTTS-Air bf16 {world}xMI355X ")
+                    + (f" on {G} engines of {B} slots, each stepping its rows in lock-step" if B > Q else "")
+                    + (f"; ONE {B}-slot engine alone = {one_eng / 1e3:.1f}k tok/s" if one_eng else "")       # (--full: the serial pass behind phase_ms)
+                    + ("; 4 x 256 in flight, round 5's shape: 166.2 k, profiles/r06f_bench.json" if (B > Q and Q == 256 and G == 4) else "") + "), "
+                    if (pipe and G > 1) else f"NeuTTS-Air bf16 {world}xMI355X ")
             workload = (head + f"batch={Q} synthetic prompts per GPU, {S} prefill / {N} decode tokens, "
                         f"STATIC batch (all {B} slots of the continuous-batching engine filled at once, every utterance {N} tokens; the ragged "
                         f"scheduler line is --mode continuous)" + ((f", {(G * B) // Q} batches at a time on {G} {B}-slot engines reading ONE copy of the weights: their prompt passes, decode chains (step graphs replayed alternately, one stream = one hardware queue each) and codec passes side by side" + (f", two such gangs taking turns ({2 * G} engines)" if NG == 2 else "") if G > 1 else ", consecutive batches pipelined over two engines") if pipe else "") + f" + hipGraph decode (BASELINE.json configs[{2 if world == 1 else 3}])")
@@ -1225,7 +1263,7 @@ def main():
             # delivers on this box, next to the gang's line above
             "one_engine_serial": ({"ms_per_batch": ph["prefill"] + ph["decode"] + ph["codec"],
                                    "codec_tokens_per_s": B * N / ((ph["prefill"] + ph["decode"] + ph["codec"]) * 1e-3)}
-                                  if pipe and all(k in ph for k in ("prefill", "decode", "codec")) and ph["decode"] > 0 else None),
+                                  if pipe and ph and all(k in ph for k in ("prefill", "decode", "codec")) and ph["decode"] > 0 else None),
             "pipeline": {"engines": len(engs), "gang": G, "gangs": NG, "overlap": ("prefill x gang | decode x gang (chains side by side) | codec x gang" if NG == 1 else "prefill(gang k+1) | decode(gang k: its batches side by side) | codec(gang k-1)"),
                          "decode_head_start_steps": a.pipe_head if NG == 2 else None, "utterances_resident": len(engs) * B} if pipe else None,
         }
@@ -1234,7 +1272,7 @@ def main():
         # BASELINE.json configs[2] literally says "continuous batching": the ragged-request scheduler measured in the SAME driver
         # invocation (its own process and engines -- the ragged requests need a longer context than the static engines were created
         # with), as a sub-record with its ratio to the static line above.  Rank 0 of a 1-GPU run only; NTTS_BENCH_CONT_LEG=0 skips it.
-        if (world == 1 and not cont and not strm and not nano and not a.tiny and Q == 256 and not emu_lib and not a.no_roofline
+        if (a.full and world == 1 and not cont and not strm and not nano and not a.tiny and Q == 256 and not emu_lib and not a.no_roofline
                 and not a.speech_range_head and os.environ.get("NTTS_BENCH_CONT_LEG", "1") != "0"):
             rec["continuous"] = continuous_leg(value, a)
         print(json.dumps(rec), flush=True)

@@ -129,8 +129,34 @@ def test_bench_continuous_mode_emulator(emu_lib):
     import sys
     env = dict(os.environ, NTTS_BENCH_EMU_LIB=emu_lib)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--tiny", "--mode", "continuous", "--batch", "2", "--requests", "7",
-                        "--prefill", "12", "--decode", "6", "--prefill-chunk", "2", "--steps", "1", "--warmup", "0", "--no-roofline",
+                        "--prefill", "12", "--decode", "6", "--prefill-chunk", "2", "--steps", "1", "--warmup", "0", "--full", "--no-roofline",
                         "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     rec = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
     assert rec["value"] > 0 and rec["phase_ms"]["codec_passes"] == 4      # 7 utterances = 3 full codec batches of 2 + the tail
+
+
+def test_bench_dump_outputs_emulator(emu_lib, tmp_path):
+    """`bench.py --dump-outputs DIR`: the last timed step's codec-token ids and waveforms (a seeded sample of its utterances), float32, identical
+    from run to run with the same arguments; a plain run (no --full) leaves the extra legs out of the result line."""
+    import subprocess
+    import sys
+    import numpy as np
+    env = dict(os.environ, NTTS_BENCH_EMU_LIB=emu_lib)
+    outs = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--tiny", "--gang", "2", "--batch", "2", "--engine-slots", "3", "--prefill", "12",
+                            "--decode", "4", "--prefill-chunk", "2", "--steps", "5", "--warmup", "0", "--dump-outputs", str(d)],
+                           env=env, capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+        rec = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
+        assert rec["steps"] == 5 and rec["phase_ms"] is None and rec["roofline"] is None and rec["cpu_baseline"] is None
+        assert "continuous" not in rec
+        outs.append({k: np.load(d / f"{k}.npy") for k in ("codes", "waveforms", "waveform_rows")})
+    o = outs[0]
+    assert o["codes"].dtype == np.float32 and o["waveforms"].dtype == np.float32 and o["waveform_rows"].dtype == np.float64
+    assert o["codes"].shape == (2, 4) and o["waveforms"].shape[0] == 2 and o["waveforms"].shape[1] % 4 == 0
+    assert np.isfinite(o["waveforms"]).all() and np.abs(o["waveforms"]).max() > 0
+    for k in o:
+        assert np.array_equal(o[k], outs[1][k]), k
