@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define NTTS_ABI_VERSION 9
+#define NTTS_ABI_VERSION 10
 
 enum {
     NTTS_OK = 0,
@@ -173,7 +173,10 @@ int ntts_backbone_read_amax(ntts_backbone* e, float* out, int32_t n);
 int ntts_backbone_activate(ntts_backbone* e, int32_t n, const int32_t* park_slots, const int32_t* slots);
 
 /* Sampling contract of one request = the keyword arguments of the reference's generate() call
- * (ref:neutts/neutts.py:338-347). */
+ * (ref:neutts/neutts.py:338-347).
+ * ABI 10: top_p / min_p, appended (generate()'s own keyword arguments of those names, which the reference's call leaves at their
+ * defaults).  The warpers run in the order of hf:generation/utils.py _get_logits_processor: temperature -> top_k -> top_p -> min_p ->
+ * multinomial.  With top_p = 1 and min_p = 0 a request draws exactly the ids it drew under ABI 9. */
 typedef struct ntts_sampling {
     int32_t max_length;      /* total length cap (prompt + new), <= max_context        [2048] */
     int32_t min_new_tokens;  /* EOS logit = -inf while fewer new tokens than this      [50]   */
@@ -182,6 +185,12 @@ typedef struct ntts_sampling {
     int32_t top_k;           /* [50]  >= 1; logits below the k-th largest are dropped, ties at the k-th kept (<= 512 kept) */
     float temperature;       /* [1.0] > 0 */
     uint64_t seed;           /* Philox4x32-10 key for do_sample=1; the draw of step t depends on (seed, t) only: give each request its own seed */
+    float top_p;             /* [1.0] (0, 1].  < 1: nucleus cut over the top-k survivors, ranked by probability descending (ties: lowest token id first) --
+                              * a token survives while the probability mass strictly before it is < top_p; the most probable one always survives
+                              * (TopPLogitsWarper with min_tokens_to_keep = 1, hf:generation/logits_process.py).  Ignored when do_sample = 0 */
+    float min_p;             /* [0.0] [0, 1].  > 0: a token survives iff its probability is >= min_p x the largest probability
+                              * (MinPLogitsWarper, hf:generation/logits_process.py).  Ignored when do_sample = 0.
+                              * Either field NaN or out of range: NTTS_EINVAL from the prefill call, naming the prompt; no slot is touched */
 } ntts_sampling;
 
 /* Prefill `n` prompts (packed back to back in `ids`, prompt i has lens[i] tokens) into the decode
@@ -518,6 +527,18 @@ int ntts_k_launch_chain_probe(int32_t n_kernels, int32_t grid, int32_t block, in
  * bf16(silu(in[i])).  variant 0 = x / (1 + expf(-x)), 1 = the epilogues' fast form (gemm.h silu_fast); the parity tests run
  * every bf16 bit pattern through both and compare with torch. */
 int ntts_k_silu_probe(const void* in_bf16_dev, void* out_bf16_dev, int64_t n, int32_t variant);
+
+/* ABI 10.  The engine's own token choice (the device function the decode step's sampling kernel calls: top-k radix select, nucleus / min-p cut,
+ * Philox draw) on caller-supplied rows: logits_dev = DEVICE bf16 [rows][ld_logits] processed logits (ld_logits % 8 == 0, 16-byte aligned; -inf where
+ * a token is masked), `vocab` columns of each row count.  group_width > 0 (a multiple of 8): the grouped path -- the probe first computes the
+ * maximum of every group of that many consecutive columns, as the lm_head epilogue leaves them, and the sampler scans only the groups that can
+ * hold one of the k largest (it falls back to the full row by itself when there are fewer groups than k or more than 1024 candidates groups);
+ * group_width = 0: the full-row path.  Per row r (HOST arrays of `rows` entries): top_k[r] >= 1, temperature[r] > 0, top_p[r], min_p[r], seed[r] as
+ * in ntts_sampling (same validation: NTTS_EINVAL); `step` is the Philox counter (the index of the new token).  Out (HOST): token_out[r] the drawn
+ * token, n_out[r] the number of final survivors (<= 512), ids_out[r * 512 ...] their ids in token-id order. */
+int ntts_k_sample_probe(const void* logits_dev, int64_t ld_logits, int32_t rows, int32_t vocab, int32_t group_width, const int32_t* top_k,
+                        const float* temperature, const float* top_p, const float* min_p, const uint64_t* seed, int32_t step,
+                        int32_t* token_out, int32_t* n_out, int32_t* ids_out);
 
 #ifdef __cplusplus
 }

@@ -442,7 +442,7 @@ extern "C" int ntts_backbone_create(const ntts_backbone_config* c, int device, n
     e->slots.resize(B);
 
     // ---- slot state
-    const size_t n_int = (size_t)B * 13 + (size_t)B * c->max_context + (size_t)B * e->max_pages;
+    const size_t n_int = (size_t)B * 15 + (size_t)B * c->max_context + (size_t)B * e->max_pages;
     CR_HIP(hipMalloc((void**)&e->ibuf, n_int * sizeof(int)));
     CR_HIP(hipMemset(e->ibuf, 0, n_int * sizeof(int)));
     int* ip = e->ibuf;
@@ -451,6 +451,8 @@ extern "C" int ntts_backbone_create(const ntts_backbone_config* c, int device, n
     e->sl.mask_eos = ip; ip += B;
     e->sl.top_k = ip; ip += B;
     e->sl.temperature = (float*)ip; ip += B;
+    e->sl.top_p = (float*)ip; ip += B;
+    e->sl.min_p = (float*)ip; ip += B;
     e->sl.seed = (unsigned int*)ip; ip += 2 * B;
     e->sl.out_tokens = ip; ip += (size_t)B * c->max_context;
     e->sl.out_stride = c->max_context;
@@ -1571,6 +1573,11 @@ static int prefill_impl(ntts_backbone* e, int32_t n, const int32_t* ids, const i
             return fail(e, NTTS_EINVAL, "prompt %d: need len < max_length <= max_context (%d, %d)", i, lens[i], samp[i].max_length);
         if (samp[i].do_sample && (samp[i].top_k < 1 || !(samp[i].temperature > 0.f)))
             return fail(e, NTTS_EINVAL, "prompt %d: do_sample needs top_k >= 1 and temperature > 0 (got %d, %g)", i, samp[i].top_k, samp[i].temperature);
+        // TopPLogitsWarper / MinPLogitsWarper's own ranges (hf:generation/logits_process.py); a NaN fails both comparisons
+        if (samp[i].do_sample && !(samp[i].top_p > 0.f && samp[i].top_p <= 1.0f))
+            return fail(e, NTTS_EINVAL, "prompt %d: top_p must lie in (0, 1] (got %g)", i, samp[i].top_p);
+        if (samp[i].do_sample && !(samp[i].min_p >= 0.f && samp[i].min_p <= 1.0f))
+            return fail(e, NTTS_EINVAL, "prompt %d: min_p must lie in [0, 1] (got %g)", i, samp[i].min_p);
         if (samp[i].eos_token_id < 0 || samp[i].eos_token_id >= c.vocab_size) return fail(e, NTTS_EINVAL, "eos id out of range");
         if (e->lr_rows && samp[i].eos_token_id != e->lr_eos)
             return fail(e, NTTS_EINVAL, "prompt %d: eos id %d, but the restricted lm_head was set up for eos id %d (ntts_backbone_set_logits_range)", i, samp[i].eos_token_id, e->lr_eos);
@@ -1665,6 +1672,10 @@ static int prefill_impl(ntts_backbone* e, int32_t n, const int32_t* ids, const i
     const size_t o_topk = m.size();  for (int i = 0; i < n; ++i) m.push_back(samp[i].do_sample ? samp[i].top_k : 0);
     const size_t o_temp = m.size();
     for (int i = 0; i < n; ++i) { int b; const float t = samp[i].do_sample ? samp[i].temperature : 1.0f; memcpy(&b, &t, 4); m.push_back(b); }
+    const size_t o_topp = m.size();
+    for (int i = 0; i < n; ++i) { int b; const float t = samp[i].do_sample ? samp[i].top_p : 1.0f; memcpy(&b, &t, 4); m.push_back(b); }
+    const size_t o_minp = m.size();
+    for (int i = 0; i < n; ++i) { int b; const float t = samp[i].do_sample ? samp[i].min_p : 0.0f; memcpy(&b, &t, 4); m.push_back(b); }
     const size_t o_seed = m.size();
     for (int i = 0; i < n; ++i) { m.push_back((int)(uint32_t)samp[i].seed); m.push_back((int)(uint32_t)(samp[i].seed >> 32)); }
     const size_t o_last = m.size();
@@ -1748,7 +1759,7 @@ static int prefill_impl(ntts_backbone* e, int32_t n, const int32_t* ids, const i
     HIPCHK(e, hipEventRecord(e->ev[0], st));
     PrefillInit pi{};
     pi.slot = md + o_slot; pi.seq_len = md + o_len; pi.min_new = md + o_min; pi.max_len = md + o_max; pi.eos = md + o_eos;
-    pi.top_k = md + o_topk; pi.temp_bits = md + o_temp; pi.seed = md + o_seed;
+    pi.top_k = md + o_topk; pi.temp_bits = md + o_temp; pi.top_p_bits = md + o_topp; pi.min_p_bits = md + o_minp; pi.seed = md + o_seed;
     pi.bt_rows = md + o_bt; pi.block_table = e->block_table; pi.max_pages = e->max_pages; pi.n = n; pi.sl = e->sl;
     NTTS_LAUNCH((prefill_init_kernel), dim3(n), dim3(64), st, pi);
 

@@ -5,6 +5,9 @@
 #include "../../include/neutts_hip.h"
 #include "kernels/gemm.h"
 #include "kernels/norm.h"
+#include "kernels/sample.h"
+
+#include <vector>
 
 using namespace ntts;
 
@@ -328,6 +331,87 @@ extern "C" int ntts_k_silu_probe(const void* in_bf16_dev, void* out_bf16_dev, in
     NTTS_LAUNCH((silu_probe_kernel), dim3((unsigned)((n + 255) / 256)), dim3(256), (hipStream_t)0, (const bf16_t*)in_bf16_dev,
                 (bf16_t*)out_bf16_dev, (long)n, (int)variant);
     return hipDeviceSynchronize() == hipSuccess && hipGetLastError() == hipSuccess ? NTTS_OK : NTTS_EHIP;
+}
+
+// ---- sampler probe: sample_topk_row (the decode step's token choice) on caller-supplied rows, one workgroup per row like sample_greedy_kernel
+struct SampleProbeArgs {
+    const bf16_t* logits;    // [rows][ld]
+    long ld;
+    int vocab;
+    const float* part_val;   // [rows][n_part] group maxima (group_max_kernel), or null: full-row path
+    int n_part, part_width;
+    const int* top_k;        // [rows]
+    const float* fparams;    // [3][rows]: temperature, top_p, min_p
+    const unsigned int* seed;   // [rows][2]
+    unsigned int step;
+    int* token;              // [rows]
+    int* n_surv;             // [rows]
+    int* surv;               // [rows][kSampleCap]
+    int rows;
+};
+// part_val[row][g] = max of columns [g * gw, (g + 1) * gw) of the row (what the lm_head epilogue leaves behind, SampleArgs::part_val)
+NTTS_KERNEL(256) void group_max_kernel(SampleProbeArgs p, float* part_val) {
+    const bf16_t* row = p.logits + (long)blockIdx.x * p.ld;
+    for (int g = threadIdx.x; g < p.n_part; g += 256) {
+        float m = -INFINITY;
+        for (int c = g * p.part_width; c < (g + 1) * p.part_width && c < p.vocab; ++c) m = fmaxf(m, bf2f(row[c]));
+        part_val[(long)blockIdx.x * p.n_part + g] = m;
+    }
+}
+NTTS_KERNEL(256) void sample_probe_kernel(SampleProbeArgs p) {
+    const int b = blockIdx.x;
+    const int tok = sample_topk_row(p.logits + (long)b * p.ld, p.vocab, p.top_k[b], p.fparams[b], p.fparams[p.rows + b], p.fparams[2 * p.rows + b],
+                                    p.seed[2 * b], p.seed[2 * b + 1], p.step, p.part_val ? p.part_val + (long)b * p.n_part : nullptr, p.n_part,
+                                    p.part_width, p.surv + (long)b * kSampleCap, p.n_surv + b);
+    if (threadIdx.x == 0) p.token[b] = tok;
+}
+extern "C" int ntts_k_sample_probe(const void* logits_dev, int64_t ld_logits, int32_t rows, int32_t vocab, int32_t group_width, const int32_t* top_k,
+                                   const float* temperature, const float* top_p, const float* min_p, const uint64_t* seed, int32_t step,
+                                   int32_t* token_out, int32_t* n_out, int32_t* ids_out) {
+    if (!logits_dev || !top_k || !temperature || !top_p || !min_p || !seed || !token_out || !n_out || !ids_out) return NTTS_EINVAL;
+    if (rows < 1 || vocab < 1 || ld_logits < vocab || (ld_logits % 8) || ((uintptr_t)logits_dev & 15) || step < 0) return NTTS_EINVAL;
+    if (group_width < 0 || (group_width % 8)) return NTTS_EINVAL;
+    for (int r = 0; r < rows; ++r)
+        if (top_k[r] < 1 || !(temperature[r] > 0.f) || !(top_p[r] > 0.f && top_p[r] <= 1.0f) || !(min_p[r] >= 0.f && min_p[r] <= 1.0f)) return NTTS_EINVAL;
+    const int n_part = group_width ? (vocab + group_width - 1) / group_width : 0;
+    // one device block: [top_k rows][seed 2 rows][token rows][n_surv rows][surv rows * cap] ints | [temperature, top_p, min_p: 3 rows][part_val rows * n_part] floats
+    const size_t n_int = (size_t)rows * (5 + kSampleCap), n_flt = (size_t)rows * (3 + n_part);
+    std::vector<int> hi(n_int, 0);
+    std::vector<float> hf((size_t)rows * 3);
+    for (int r = 0; r < rows; ++r) {
+        hi[r] = top_k[r];
+        hi[rows + 2 * r] = (int)(uint32_t)seed[r];
+        hi[rows + 2 * r + 1] = (int)(uint32_t)(seed[r] >> 32);
+        hf[r] = temperature[r]; hf[rows + r] = top_p[r]; hf[2 * rows + r] = min_p[r];
+    }
+    int* di = nullptr;
+    float* df = nullptr;
+    if (hipMalloc((void**)&di, n_int * sizeof(int)) != hipSuccess) return NTTS_ENOMEM;
+    if (hipMalloc((void**)&df, n_flt * sizeof(float)) != hipSuccess) { hipFree(di); return NTTS_ENOMEM; }
+    int rc = NTTS_EHIP;
+    if (hipMemcpy(di, hi.data(), n_int * sizeof(int), hipMemcpyHostToDevice) == hipSuccess &&
+        hipMemcpy(df, hf.data(), hf.size() * sizeof(float), hipMemcpyHostToDevice) == hipSuccess) {
+        SampleProbeArgs a{};
+        a.logits = (const bf16_t*)logits_dev; a.ld = ld_logits; a.vocab = vocab; a.n_part = n_part; a.part_width = group_width;
+        a.top_k = di; a.seed = (const unsigned int*)(di + rows); a.token = di + 3 * rows; a.n_surv = di + 4 * rows; a.surv = di + 5 * rows;
+        a.fparams = df; a.step = (unsigned int)step; a.rows = rows;
+        if (group_width) {
+            NTTS_LAUNCH((group_max_kernel), dim3(rows), dim3(256), (hipStream_t)0, a, df + 3 * (size_t)rows);
+            a.part_val = df + 3 * (size_t)rows;
+        }
+        NTTS_LAUNCH((sample_probe_kernel), dim3(rows), dim3(256), (hipStream_t)0, a);
+        if (hipDeviceSynchronize() == hipSuccess && hipGetLastError() == hipSuccess &&
+            hipMemcpy(hi.data(), di, n_int * sizeof(int), hipMemcpyDeviceToHost) == hipSuccess) {
+            for (int r = 0; r < rows; ++r) {
+                token_out[r] = hi[3 * rows + r];
+                n_out[r] = hi[4 * rows + r];
+                for (int a2 = 0; a2 < kSampleCap; ++a2) ids_out[(size_t)r * kSampleCap + a2] = hi[5 * (size_t)rows + (size_t)r * kSampleCap + a2];
+            }
+            rc = NTTS_OK;
+        }
+    }
+    hipFree(di); hipFree(df);
+    return rc;
 }
 
 extern "C" int ntts_k_mfma_probe(float* out_dev_768) {

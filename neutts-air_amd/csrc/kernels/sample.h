@@ -5,8 +5,10 @@
 //   fp32 logits -> MinNewTokensLength (applied in the lm_head epilogue via mask_eos) ->
 //     do_sample=0: argmax (first max wins, torch.argmax)
 //     do_sample=1: [TemperatureLogitsWarper: scores / T] -> TopKLogitsWarper (scores < k-th largest -> -inf, ties at the
-//                  k-th value kept; hf:generation/logits_process.py:542-595) -> softmax -> multinomial(1)
-//                  (the reference's own call: do_sample=True, temperature=1.0, top_k=50, ref:neutts/neutts.py:338-347)
+//                  k-th value kept; hf:generation/logits_process.py:542-595) -> [TopPLogitsWarper, top_p < 1] ->
+//                  [MinPLogitsWarper, min_p > 0] -> softmax -> multinomial(1)
+//                  (the reference's own call: do_sample=True, temperature=1.0, top_k=50, ref:neutts/neutts.py:338-347; top_p /
+//                  min_p are generate()'s own keyword arguments, off -- 1.0 / 0.0 -- in that call)
 //   -> append -> EosTokenCriteria / MaxLengthCriteria.
 // Sampling reads the row of bf16 logits the lm_head epilogue leaves behind (HF's logits ARE bf16 values cast to fp32, so a
 // 16-bit radix select finds the exact k-th largest), draws its uniform from Philox4x32-10 keyed by the request's seed with
@@ -31,6 +33,8 @@ struct SlotArrays {      // device arrays, one entry per decode slot
     int* mask_eos;       // eos+1 while EOS is masked for the NEXT sampled token (n_new < min_new), else 0
     int* top_k;          // 0 = greedy (do_sample=0); k >= 1 = sample among the k largest logits
     float* temperature;  // > 0
+    float* top_p;        // (0, 1]; 1 = no nucleus cut
+    float* min_p;        // [0, 1]; 0 = no min-p cut
     unsigned int* seed;  // [slots][2] Philox key
     int* out_tokens;     // [slots][out_stride]
     int out_stride;
@@ -73,9 +77,18 @@ NTTS_D unsigned int bf16_key(bf16_t v) { return (v & 0x8000u) ? (~(unsigned int)
 // below T holds no element >= T: only the groups with maximum >= T -- k of them plus ties, ~50 x 96 columns of the 217 488 -- are
 // scanned for the exact threshold and the survivors.  Same result as three sweeps over the whole row (the fallback when a row has more
 // than kGroupCap such groups, e.g. constant logits, or when there are fewer groups than k), 1/45 of the bytes and LDS atomics.
+//
+// top_p < 1 / min_p > 0 (TopPLogitsWarper, MinPLogitsWarper behind TopK: hf:generation/logits_process.py) filter the candidate list
+// between the softmax numerators and the draw, in LDS and registers only:
+//   top_p: candidates ranked by value descending, ties by token id ascending; c_0 = 0, c_{j+1} = c_j + e_(j) summed in that order by one
+//          thread (like `total`: the cut depends on the order of those additions), every c_j kept; rank j survives iff j == 0 or c_j < top_p * c_n
+//          ("keep while the mass strictly before the token is < top_p", min_tokens_to_keep = 1);
+//   min_p: survives iff e_a >= min_p (prob >= min_p * max prob: the normaliser cancels and the maximum has e = 1).
+// The survivors stay in token-id order with their e_a; the draw is the same code either way.  With top_p >= 1 and min_p <= 0 the stage is
+// one block-uniform branch not taken.  surv_out / n_out (ntts_k_sample_probe; null in the decode step): the final survivors.
 constexpr int kGroupCap = 1024;
-NTTS_D int sample_topk_row(const bf16_t* row, int V, int k, float temperature, unsigned int s0, unsigned int s1,
-                           unsigned int step, const float* pv, int n_part, int gw) {
+NTTS_D int sample_topk_row(const bf16_t* row, int V, int k, float temperature, float top_p, float min_p, unsigned int s0, unsigned int s1,
+                           unsigned int step, const float* pv, int n_part, int gw, int* surv_out = nullptr, int* n_out = nullptr) {
     NTTS_SHARED unsigned int hist[256];
     NTTS_SHARED unsigned int sel[6];          // [0] high byte, [1] elements above that bin, [2] threshold key, [3] list length, [4] group threshold key, [5] groups kept
     NTTS_SHARED int cidx[kSampleCap];
@@ -86,6 +99,7 @@ NTTS_D int sample_topk_row(const bf16_t* row, int V, int k, float temperature, u
     NTTS_SHARED unsigned int wsum[4];
     NTTS_SHARED float ev[kSampleCap];
     NTTS_SHARED float wmax[4];
+    NTTS_SHARED unsigned int fcnt[8];         // nucleus / min-p stage: survivors per wave, candidates [0, 256) and [256, 512)
     NTTS_SHARED int result;
     const int tid = threadIdx.x;
     if (k > V) k = V;
@@ -179,7 +193,40 @@ NTTS_D int sample_topk_row(const bf16_t* row, int V, int k, float temperature, u
     });
     sync();
     int n = (int)sel[3];
-    if (n > kSampleCap) n = kSampleCap;
+    if (n > kSampleCap) {                                            // (block-uniform; constant rows, a threshold of -inf, k near the cap with ties)
+        // More candidates than the list holds: which of them the appends above kept depends on the order the atomics arrived in.  Keep
+        // the kSampleCap LOWEST token ids instead (oracle/sampling_ref.py: token-id order, capped): the id of the last one is found by a
+        // radix select over the bytes of ~id (larger = lower id) with the histogram walk used above, then the list is gathered again
+        k = kSampleCap;                                              // (find_bin's target)
+        int top = 3;
+        while (top > 0 && ((unsigned int)(V - 1) >> (8 * top)) == 0u) --top;     // bytes of ~id above this one are 0xff for every id < V
+        unsigned int pre = ~0u, base = 0u;
+        for (int b = top; b >= 0; --b) {
+            const unsigned int hm = b == 3 ? 0u : (~0u << (8 * (b + 1)));        // the bytes already decided
+            hist[tid] = 0;
+            sync();
+            for_each_elem([&](int idx, bf16_t v) {
+                const unsigned int u = ~(unsigned int)idx;
+                if (bf16_key(v) >= thr && (u & hm) == (pre & hm)) atomic_add_lds(&hist[(u >> (8 * b)) & 255u], 1u);
+            });
+            sync();
+            find_bin(base);
+            pre = (pre & hm) | (sel[0] << (8 * b)) | (b ? (~0u >> (32 - 8 * b)) : 0u);
+            base = sel[1];
+        }
+        const int id_last = (int)~pre;                               // the largest id that is kept
+        if (tid == 0) sel[3] = 0;                                    // (every thread read the count long ago: barriers in between)
+        sync();
+        for_each_elem([&](int idx, bf16_t v) {
+            if (bf16_key(v) >= thr && idx <= id_last) {
+                const unsigned int at = atomic_add_lds(&sel[3], 1u);
+                if (at < (unsigned int)kSampleCap) { cidx[at] = idx; cval[at] = v; }
+            }
+        });
+        sync();
+        n = (int)sel[3];
+        if (n > kSampleCap) n = kSampleCap;
+    }
     // ---- order the candidates by token id (the append order above is not deterministic): rank sort
     for (int a = tid; a < n; a += 256) {
         const int ia = cidx[a];
@@ -201,6 +248,65 @@ NTTS_D int sample_topk_row(const bf16_t* row, int V, int k, float temperature, u
     const float it = 1.0f / temperature;
     for (int a = tid; a < n; a += 256) ev[a] = fexp((bf2f(sval[a]) - m) * it);
     sync();
+    const bool nucleus = top_p < 1.0f;
+    if (nucleus || min_p > 0.0f) {                                   // (block-uniform)
+        // ---- TopP / MinP: every thread owns candidates tid and tid + 256 (n <= 512)
+        int rk[2] = {0, 0};
+        bool pass[2] = {true, true};                                 // the nucleus test of this thread's candidates
+        if (nucleus) {
+            float* re = reinterpret_cast<float*>(glist);             // e in rank order (the group list is dead by now: 1024 ints)
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                const int a = tid + q * 256;
+                if (a < n) {
+                    const float va = bf2f(sval[a]);
+                    int r = 0;
+                    for (int b = 0; b < n; ++b) { const float vb = bf2f(sval[b]); r += (vb > va) || (vb == va && b < a); }
+                    rk[q] = r;
+                    re[r] = ev[a];
+                }
+            }
+            sync();
+            if (tid == 0) {                                          // one walk, no data-dependent exit: re[j] <- c_j, the mass before rank j
+                float c = 0.f;
+                for (int j = 0; j < n; ++j) { const float e = re[j]; re[j] = c; c += e; }
+                wmax[0] = top_p * c;
+            }
+            sync();
+            const float lim = wmax[0];                               // (c_j never decreases: the ranks that pass are a prefix)
+#pragma unroll
+            for (int q = 0; q < 2; ++q) pass[q] = rk[q] == 0 || re[rk[q]] < lim;
+        }
+        bool kp[2];
+        int id[2];
+        float ee[2];
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            const int a = tid + q * 256;
+            id[q] = a < n ? sidx[a] : 0;
+            ee[q] = a < n ? ev[a] : 0.f;
+            kp[q] = a < n && pass[q] && ee[q] >= min_p;
+        }
+        // order-preserving compaction (export_codes_kernel's scheme), in place: everything is in registers before the barrier
+        const unsigned long long m0 = ballot(kp[0]), m1 = ballot(kp[1]);
+        const int lane = lane_id(), w = wave_id();
+        if (lane == 0) { fcnt[w] = (unsigned int)popc64(m0); fcnt[4 + w] = (unsigned int)popc64(m1); }
+        sync();
+        const int n0 = (int)(fcnt[0] + fcnt[1] + fcnt[2] + fcnt[3]), n1 = (int)(fcnt[4] + fcnt[5] + fcnt[6] + fcnt[7]);
+        if (n0 + n1 > 0) {                                           // (a row of NaNs keeps its list; block-uniform)
+            int off0 = 0, off1 = n0;
+            for (int ww = 0; ww < w; ++ww) { off0 += (int)fcnt[ww]; off1 += (int)fcnt[4 + ww]; }
+            const unsigned long long below = (1ull << lane) - 1ull;
+            if (kp[0]) { const int at = off0 + popc64(m0 & below); sidx[at] = id[0]; ev[at] = ee[0]; }
+            if (kp[1]) { const int at = off1 + popc64(m1 & below); sidx[at] = id[1]; ev[at] = ee[1]; }
+            n = n0 + n1;
+        }
+        sync();
+    }
+    if (surv_out) {                                                  // (probe only; folded away in the decode step)
+        for (int a = tid; a < n; a += 256) surv_out[a] = sidx[a];
+        if (tid == 0) *n_out = n;
+    }
     if (tid == 0) {
         float total = 0.f;
         for (int a = 0; a < n; ++a) total += ev[a];
@@ -259,8 +365,8 @@ NTTS_KERNEL(256) void sample_greedy_kernel(SampleArgs p) {
     int sampled = -1;
     if (k > 0) {
         const int step = (p.phase == SLOT_PREFILLED) ? 0 : p.sl.n_new[b];
-        sampled = sample_topk_row(p.logits + (long)b * p.ld_logits, p.vocab, k, p.sl.temperature[b], p.sl.seed[2 * b],
-                                  p.sl.seed[2 * b + 1], (unsigned int)step, pv, p.n_part, p.part_width);
+        sampled = sample_topk_row(p.logits + (long)b * p.ld_logits, p.vocab, k, p.sl.temperature[b], p.sl.top_p[b], p.sl.min_p[b],
+                                  p.sl.seed[2 * b], p.sl.seed[2 * b + 1], (unsigned int)step, pv, p.n_part, p.part_width);
     }
     if (tid == 0) {
         for (int w = 1; w < 4; ++w)
@@ -290,6 +396,8 @@ struct PrefillInit {
     const int* eos;
     const int* top_k;      // 0 = greedy
     const int* temp_bits;  // float bits
+    const int* top_p_bits; // float bits
+    const int* min_p_bits; // float bits
     const int* seed;       // [n][2]
     const int* bt_rows;    // [n][max_pages]
     int* block_table;      // [slots][max_pages]
@@ -311,6 +419,8 @@ NTTS_KERNEL(64) void prefill_init_kernel(PrefillInit p) {
         p.sl.eos[s] = p.eos[i];
         p.sl.top_k[s] = p.top_k[i];
         p.sl.temperature[s] = __builtin_bit_cast(float, p.temp_bits[i]);
+        p.sl.top_p[s] = __builtin_bit_cast(float, p.top_p_bits[i]);
+        p.sl.min_p[s] = __builtin_bit_cast(float, p.min_p_bits[i]);
         p.sl.seed[2 * s] = (unsigned int)p.seed[2 * i];
         p.sl.seed[2 * s + 1] = (unsigned int)p.seed[2 * i + 1];
         p.sl.mask_eos[s] = p.min_new[i] > 0 ? p.eos[i] + 1 : 0;
@@ -395,6 +505,7 @@ NTTS_KERNEL(64) void activate_slots_kernel(ActivateArgs p) {
         p.sl.pos[dst] = p.sl.pos[src]; p.sl.n_new[dst] = nn; p.sl.cur_tok[dst] = p.sl.cur_tok[src]; p.sl.prompt_len[dst] = p.sl.prompt_len[src];
         p.sl.min_new[dst] = p.sl.min_new[src]; p.sl.max_len[dst] = p.sl.max_len[src]; p.sl.eos[dst] = p.sl.eos[src]; p.sl.mask_eos[dst] = p.sl.mask_eos[src];
         p.sl.top_k[dst] = p.sl.top_k[src]; p.sl.temperature[dst] = p.sl.temperature[src];
+        p.sl.top_p[dst] = p.sl.top_p[src]; p.sl.min_p[dst] = p.sl.min_p[src];
         p.sl.seed[2 * dst] = p.sl.seed[2 * src]; p.sl.seed[2 * dst + 1] = p.sl.seed[2 * src + 1];
         p.sl.state[dst] = p.sl.state[src];
         p.sl.state[src] = SLOT_FREE;

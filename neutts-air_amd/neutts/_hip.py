@@ -18,7 +18,7 @@ DEFAULT_LIB = os.path.join(os.path.dirname(_HERE), "libneutts_hip.so")
 
 NTTS_DT_F32, NTTS_DT_BF16, NTTS_DT_I32, NTTS_DT_FP8_E4M3 = 0, 1, 2, 3
 NTTS_W_BF16, NTTS_W_FP8_E4M3 = 0, 1
-ABI_VERSION = 9
+ABI_VERSION = 10
 NTTS_PAGE_TOKENS = 32            # include/neutts_hip.h
 PAGE_TOKENS = 32
 ERRORS = {-1: "EINVAL", -2: "ENODEV", -3: "ENOMEM", -4: "ESTATE", -5: "EHIP"}
@@ -60,7 +60,8 @@ class StreamParamsC(C.Structure):
 
 class SamplingC(C.Structure):
     _fields_ = [("max_length", C.c_int32), ("min_new_tokens", C.c_int32), ("eos_token_id", C.c_int32),
-                ("do_sample", C.c_int32), ("top_k", C.c_int32), ("temperature", C.c_float), ("seed", C.c_uint64)]
+                ("do_sample", C.c_int32), ("top_k", C.c_int32), ("temperature", C.c_float), ("seed", C.c_uint64),
+                ("top_p", C.c_float), ("min_p", C.c_float)]
 
 
 _LIBS: Dict[str, C.CDLL] = {}
@@ -172,6 +173,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "ntts_k_mfma_probe": (C.c_int, [p]),
         "ntts_k_silu_probe": (C.c_int, [p, p, i64, i32]),
         "ntts_k_launch_chain_probe": (C.c_int, [i32, i32, i32, i32, C.POINTER(C.c_double)]),
+        "ntts_k_sample_probe": (C.c_int, [p, i64, i32, i32, i32, C.POINTER(i32), C.POINTER(f32), C.POINTER(f32), C.POINTER(f32),
+                                          C.POINTER(C.c_uint64), i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError here == header/library drift: fail loudly
@@ -202,7 +205,8 @@ def _tensor_ptr(t):
 
 @dataclass
 class Sampling:
-    """Keyword arguments of the reference's generate() call (ref:neutts/neutts.py:338-347)."""
+    """Keyword arguments of the reference's generate() call (ref:neutts/neutts.py:338-347), plus generate()'s own top_p / min_p (off -- 1.0 / 0.0 --
+    in that call): TopPLogitsWarper / MinPLogitsWarper behind top-k, in transformers' order (include/neutts_hip.h: ntts_sampling)."""
     max_length: int = 2048
     min_new_tokens: int = 50
     eos_token_id: int = 0
@@ -210,10 +214,35 @@ class Sampling:
     top_k: int = 50
     temperature: float = 1.0
     seed: int = 0
+    top_p: float = 1.0
+    min_p: float = 0.0
 
     def to_c(self) -> SamplingC:
         return SamplingC(self.max_length, self.min_new_tokens, self.eos_token_id, int(self.do_sample), self.top_k,
-                         self.temperature, self.seed)
+                         self.temperature, self.seed, self.top_p, self.min_p)
+
+
+SAMPLE_CAP = 512                 # candidates the device sampler keeps (csrc/kernels/sample.h kSampleCap)
+
+
+def sample_probe(lib, logits_ptr: int, ld_logits: int, rows: int, vocab: int, group_width: int, top_k, temperature, top_p, min_p, seed,
+                 step: int):
+    """ntts_k_sample_probe: the engine's token choice on `rows` DEVICE bf16 logits rows at `logits_ptr` (row stride ld_logits elements); the
+    sampling parameters are per row (scalars are broadcast).  group_width 0 = the full-row path, else the grouped path over groups of that
+    many columns.  Returns (tokens [rows], [survivor ids of each row, in token-id order])."""
+    def arr(v, dt):
+        return np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=dt), (rows,)))
+    k, t, tp, mp, sd = arr(top_k, np.int32), arr(temperature, np.float32), arr(top_p, np.float32), arr(min_p, np.float32), arr(seed, np.uint64)
+    tok = np.zeros(rows, dtype=np.int32)
+    n = np.zeros(rows, dtype=np.int32)
+    ids = np.zeros((rows, SAMPLE_CAP), dtype=np.int32)
+    i32p, f32p = C.POINTER(C.c_int32), C.POINTER(C.c_float)
+    rc = lib.ntts_k_sample_probe(C.c_void_p(logits_ptr), ld_logits, rows, vocab, group_width, k.ctypes.data_as(i32p), t.ctypes.data_as(f32p),
+                                 tp.ctypes.data_as(f32p), mp.ctypes.data_as(f32p), sd.ctypes.data_as(C.POINTER(C.c_uint64)), step,
+                                 tok.ctypes.data_as(i32p), n.ctypes.data_as(i32p), ids.ctypes.data_as(i32p))
+    if rc != 0:
+        raise NeuTTSHipError(rc, "ntts_k_sample_probe")
+    return tok, [ids[r, : n[r]].copy() for r in range(rows)]
 
 
 class BackboneEngine:

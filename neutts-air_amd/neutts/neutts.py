@@ -151,6 +151,21 @@ def load_audio_16k(path) -> np.ndarray:
     return x
 
 
+def _check_sampling(top_k, temperature, top_p, min_p, who: str = "") -> None:
+    """The ranges transformers' warpers accept (TopK / Temperature / TopP / MinPLogitsWarper); ValueError before anything reaches the engine."""
+    if isinstance(top_k, bool) or not isinstance(top_k, (int, np.integer)) or top_k < 1:
+        raise ValueError(f"{who}top_k must be an integer >= 1 (got {top_k!r})")
+    for name, v in (("temperature", temperature), ("top_p", top_p), ("min_p", min_p)):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise ValueError(f"{who}{name} must be a number (got {v!r})")
+    if not temperature > 0 or temperature == float("inf"):
+        raise ValueError(f"{who}temperature must be a finite number > 0 (got {temperature!r})")
+    if not 0 < top_p <= 1:
+        raise ValueError(f"{who}top_p must lie in (0, 1] (got {top_p!r})")
+    if not 0 <= min_p <= 1:
+        raise ValueError(f"{who}min_p must lie in [0, 1] (got {min_p!r})")
+
+
 class NeuTTS:
 
     def __init__(
@@ -165,6 +180,10 @@ class NeuTTS:
         lib_path: Optional[str] = None,
         do_sample: bool = True,
         seed: int = 0,
+        top_k: int = 50,
+        temperature: float = 1.0,
+        top_p: float = 1.0,
+        min_p: float = 0.0,
         speech_range_head: bool = False,
         codec_precision: str = "fp16",
     ):
@@ -183,10 +202,15 @@ class NeuTTS:
         self._is_onnx_codec = False
         self._lib_path = lib_path
         self._max_batch = max_batch
-        # sampling contract of the reference call (ref:neutts/neutts.py:338-347); do_sample=False = greedy
+        # sampling contract of the reference call (ref:neutts/neutts.py:338-347: top_k 50, temperature 1.0 -- the defaults); do_sample=False = greedy.
+        # top_p / min_p are generate()'s own keyword arguments of those names (TopPLogitsWarper / MinPLogitsWarper behind top-k), off in that
+        # call.  Every entry point takes per-call overrides of the four.
+        _check_sampling(top_k, temperature, top_p, min_p)
         self.do_sample = do_sample
-        self.top_k = 50
-        self.temperature = 1.0
+        self.top_k = top_k
+        self.temperature = temperature
+        self.top_p = top_p
+        self.min_p = min_p
         self.min_new_tokens = 50
         self._seed = seed
 
@@ -348,21 +372,24 @@ class NeuTTS:
         self.codec = _CodecFacade(engine, enc_engine)
 
     # ------------------------------------------------------------------------------------------ public API
-    def infer(self, text: str, ref_codes, ref_text: str) -> np.ndarray:
-        """Generate speech for `text` in the voice of the encoded reference (ref:neutts/neutts.py:216-243)."""
+    def infer(self, text: str, ref_codes, ref_text: str, *, temperature=None, top_k=None, top_p=None, min_p=None) -> np.ndarray:
+        """Generate speech for `text` in the voice of the encoded reference (ref:neutts/neutts.py:216-243).  temperature / top_k / top_p /
+        min_p override the instance's sampling attributes for this call (None = the attribute)."""
+        samp = self._resolve_sampling(1, temperature, top_k, top_p, min_p)
         prompt_ids = self._apply_chat_template(ref_codes, ref_text, text)
-        new_ids = self.generate_codes([prompt_ids])[0]
+        new_ids = self._generate([prompt_ids], samp)[0]
         wav = self._decode_ids(new_ids)
         return wav if self.watermarker is None else self.watermarker.apply_watermark(wav, sample_rate=24_000)
 
-    def infer_batch(self, texts: Sequence[str], ref_codes, ref_texts) -> List[np.ndarray]:
+    def infer_batch(self, texts: Sequence[str], ref_codes, ref_texts, *, temperature=None, top_k=None, top_p=None, min_p=None) -> List[np.ndarray]:
         """Many utterances at once: continuous batching over the engine's decode slots (over every engine's, with engines > 1),
-        one codec pass."""
+        one codec pass.  The sampling overrides take one value for the call or one per utterance."""
+        samp = self._resolve_sampling(len(texts), temperature, top_k, top_p, min_p)
         if not isinstance(ref_texts, (list, tuple)):
             ref_texts = [ref_texts] * len(texts)
             ref_codes = [ref_codes] * len(texts)
         prompts = [self._apply_chat_template(rc, rt, t) for rc, rt, t in zip(ref_codes, ref_texts, texts)]
-        codes = [self._ids_to_codes(ids) for ids in self.generate_codes(prompts)]
+        codes = [self._ids_to_codes(ids) for ids in self._generate(prompts, samp)]
         if any(len(c) == 0 for c in codes):
             raise ValueError("No valid speech tokens found in the output.")
         wavs = self.codec.engine.decode(codes)
@@ -370,20 +397,23 @@ class NeuTTS:
             wavs = [self.watermarker.apply_watermark(w, sample_rate=24_000) for w in wavs]
         return wavs
 
-    def infer_stream(self, text: str, ref_codes, ref_text: str) -> Generator[np.ndarray, None, None]:
-        """Streaming synthesis with the reference's window / cross-fade semantics (ref:neutts/neutts.py:373-465)."""
+    def infer_stream(self, text: str, ref_codes, ref_text: str, *, temperature=None, top_k=None, top_p=None, min_p=None) -> Generator[np.ndarray, None, None]:
+        """Streaming synthesis with the reference's window / cross-fade semantics (ref:neutts/neutts.py:373-465).  Sampling overrides as `infer`
+        (checked here, before the generator is handed out)."""
+        samp = self._resolve_sampling(1, temperature, top_k, top_p, min_p)
         prompt_ids = self._apply_chat_template(ref_codes, ref_text, text)
         ref = [int(c) for c in _to_list(ref_codes)]
         if self._stream_on_device([ref]):       # token cache, windows, codec pass and cross-fade on the device (csrc/stream.cpp): a set of one stream
-            return (chunk for _, chunk in self._infer_stream_batch_hip([prompt_ids], [ref]))
-        return self._infer_stream_hip(prompt_ids, ref)        # host loop: a watermarker (a host library) sits between the codec and the slice
+            return (chunk for _, chunk in self._infer_stream_batch_hip([prompt_ids], [ref], samp))
+        return self._infer_stream_hip(prompt_ids, ref, samp)        # host loop: a watermarker (a host library) sits between the codec and the slice
 
-    def infer_stream_batch(self, texts: Sequence[str], ref_codes, ref_texts) -> Generator[tuple, None, None]:
+    def infer_stream_batch(self, texts: Sequence[str], ref_codes, ref_texts, *, temperature=None, top_k=None, top_p=None, min_p=None) -> Generator[tuple, None, None]:
         """Many utterances streamed at once (BASELINE config 5's shape: a decode batch with the codec on its own stream):
         yields `(utterance index, chunk)` pairs; the chunks of one utterance, in order, are exactly what `infer_stream`
         yields for it.  One decode burst serves every running utterance, and all windows that became decodable in a burst
         go through the codec in ONE batched call, enqueued behind the next burst (the two engines' streams overlap).
-        At most `max_batch` utterances (the engine's decode slots) per call."""
+        At most `max_batch` utterances (the engine's decode slots) per call.  Sampling overrides as `infer_batch`."""
+        samp = self._resolve_sampling(len(texts), temperature, top_k, top_p, min_p)
         if not isinstance(ref_texts, (list, tuple)):
             ref_texts = [ref_texts] * len(texts)
             ref_codes = [ref_codes] * len(texts)
@@ -391,7 +421,7 @@ class NeuTTS:
         if len(texts) > cap:
             raise ValueError(f"{len(texts)} utterances exceed the engine's {cap} decode slots")
         prompts = [self._apply_chat_template(rc, rt, t) for rc, rt, t in zip(ref_codes, ref_texts, texts)]
-        return self._infer_stream_batch_hip(prompts, [[int(c) for c in _to_list(rc)] for rc in ref_codes])
+        return self._infer_stream_batch_hip(prompts, [[int(c) for c in _to_list(rc)] for rc in ref_codes], samp)
 
     def encode_reference(self, ref_audio_path: str | Path):
         """ref:neutts/neutts.py:266-271: 16 kHz mono -> `codec.encode_code` -> 1-D int codes at 50 Hz.  On the encoder engine
@@ -404,20 +434,45 @@ class NeuTTS:
         return ref_codes
 
     # ------------------------------------------------------------------------------------------ id-level hot path
-    def _sampling(self, prompt_len: int, index: int = 0) -> _hip.Sampling:
+    def _resolve_sampling(self, n: int, temperature=None, top_k=None, top_p=None, min_p=None) -> List[tuple]:
+        """Per-call sampling overrides -> one checked (top_k, temperature, top_p, min_p) per utterance.  None = the instance attribute; a list /
+        tuple / array gives one value per utterance (the batch entry points).  ValueError on a bad value, before the engine is touched."""
+        cols = []
+        for name, v in (("top_k", top_k), ("temperature", temperature), ("top_p", top_p), ("min_p", min_p)):
+            if v is None:
+                v = getattr(self, name)
+            if isinstance(v, (list, tuple, np.ndarray)):
+                v = list(v)
+                if len(v) != n:
+                    raise ValueError(f"{name}: {len(v)} values for {n} utterances")
+                v = [getattr(self, name) if x is None else x for x in v]
+            else:
+                v = [v] * n
+            cols.append(v)
+        out = list(zip(*cols)) if n else []
+        for i, (k, t, tp, mp) in enumerate(out):
+            _check_sampling(k, t, tp, mp, f"utterance {i}: " if n > 1 else "")
+        return [(int(k), float(t), float(tp), float(mp)) for k, t, tp, mp in out]
+
+    def _sampling(self, prompt_len: int, index: int = 0, samp: Optional[Sequence[tuple]] = None) -> _hip.Sampling:
         if self._eos_id is None:
             raise RuntimeError("eos token id unknown: supply 'eos_token_id' with in-memory weights")
         # one Philox key per request: (call counter, index within the call)
         seed = (self._seed * 0x9E3779B97F4A7C15 + index * 0xD1B54A32D192ED03 + 1) & 0xFFFFFFFFFFFFFFFF
+        top_k, temperature, top_p, min_p = samp[index] if samp is not None else (self.top_k, self.temperature, self.top_p, self.min_p)
         return _hip.Sampling(max_length=self.max_context, min_new_tokens=self.min_new_tokens, eos_token_id=self._eos_id,
-                             do_sample=self.do_sample, top_k=self.top_k, temperature=self.temperature, seed=seed)
+                             do_sample=self.do_sample, top_k=top_k, temperature=temperature, seed=seed, top_p=top_p, min_p=min_p)
 
-    def generate_codes(self, prompts: Sequence[Sequence[int]]) -> List[List[int]]:
-        """Batched equivalent of `_infer_torch` (ref:neutts/neutts.py:334-352): new token ids per prompt."""
+    def generate_codes(self, prompts: Sequence[Sequence[int]], *, temperature=None, top_k=None, top_p=None, min_p=None) -> List[List[int]]:
+        """Batched equivalent of `_infer_torch` (ref:neutts/neutts.py:334-352): new token ids per prompt.  The sampling overrides take one
+        value for the call or one per prompt."""
+        return self._generate(prompts, self._resolve_sampling(len(prompts), temperature, top_k, top_p, min_p))
+
+    def _generate(self, prompts: Sequence[Sequence[int]], samp: Sequence[tuple]) -> List[List[int]]:
         self._seed += 1
         # utterances of one speaker start with the same tokens (chat header + reference-text phones, ref :307,:315-325):
         # the engine keeps one copy of those KV pages and computes only what differs
-        sampling = [self._sampling(len(p), i) for i, p in enumerate(prompts)]
+        sampling = [self._sampling(len(p), i, samp) for i, p in enumerate(prompts)]
         # more utterances than decode slots: freed slots are refilled about a tenth of an engine's slots at a time (24 of 256) -- a prompt
         # pass over a handful of prompts costs 1.5-2 us per token against 0.84 for 32 and more, an idle slot a step each
         # (profiles/r05m_probe_prefill_size.txt); scheduling only, the ids do not depend on it
@@ -493,7 +548,7 @@ class NeuTTS:
         return ids[:j] + [speech_gen_start] + list(codes)
 
     # ------------------------------------------------------------------------------------------ streaming
-    def _infer_stream_hip(self, prompt_ids: List[int], ref_codes: List[int]) -> Generator[np.ndarray, None, None]:
+    def _infer_stream_hip(self, prompt_ids: List[int], ref_codes: List[int], samp: Optional[Sequence[tuple]] = None) -> Generator[np.ndarray, None, None]:
         """Window / cross-fade semantics of ref:neutts/neutts.py:401-465 (Appendix C of SURVEY.md), token by token.
         The backbone and the codec are separate engines on separate HIP streams: the next `chunk` decode steps are
         enqueued (asynchronously) BEFORE the codec pass of the chunk that just became decodable, so the codec runs
@@ -502,7 +557,7 @@ class NeuTTS:
         self._seed += 1
         slot = eng.acquire_slot()         # from the engine's pool: a stream that is still open never shares its slot
         try:
-            eng.prefill([prompt_ids], [slot], [self._sampling(len(prompt_ids))])
+            eng.prefill([prompt_ids], [slot], [self._sampling(len(prompt_ids), 0, samp)])
         except Exception:
             eng.release(slot)
             raise
@@ -614,7 +669,7 @@ class NeuTTS:
             self._gang_codec0_lent = True
         return self._gang_codecs
 
-    def _infer_stream_batch_gang(self, prompts: List[List[int]], ref_codes: List[List[int]]):
+    def _infer_stream_batch_gang(self, prompts: List[List[int]], ref_codes: List[List[int]], samp: Optional[Sequence[tuple]] = None):
         """infer_stream_batch over an ENGINE GANG (BASELINE configs[4]'s literal shape: ref:neutts/neutts.py:373-465
         for many utterances at once).  The utterances are dealt out in admission groups over the gang's engines; every group is a
         device-side stream set (ntts_streams_*) on its engine, the engine's codec engine on the same lane.  Per turn of an engine:
@@ -688,7 +743,7 @@ class NeuTTS:
                             while i1 < len(idx) and (i1 == i0 or used + len(prompts[idx[i1]]) <= budget):
                                 used += len(prompts[idx[i1]])
                                 i1 += 1
-                            eng.prefill([prompts[i] for i in idx[i0:i1]], slots[i0:i1], [self._sampling(len(prompts[i]), i) for i in idx[i0:i1]])
+                            eng.prefill([prompts[i] for i in idx[i0:i1]], slots[i0:i1], [self._sampling(len(prompts[i]), i, samp) for i in idx[i0:i1]])
                             i0 = i1
                         item[0] = _hip.StreamSet(eng, codecs[k], slots, [ref_codes[i] for i in idx], int(eng.cfg["max_context"]), chunk, look_f,
                                                  self.streaming_lookback, self.streaming_overlap_frames, self.hop_length,
@@ -724,13 +779,13 @@ class NeuTTS:
                             except _hip.NeuTTSHipError:
                                 pass
 
-    def _infer_stream_batch_hip(self, prompts: List[List[int]], ref_codes: List[List[int]]):
+    def _infer_stream_batch_hip(self, prompts: List[List[int]], ref_codes: List[List[int]], samp: Optional[Sequence[tuple]] = None):
         # (stream_on_gang: off unless the caller sets it -- it pays for one of the two models measured.  512 streams of the fp8 Nano-sized model
         #  over four 128-slot engines, one admission group per engine: 150.2 k codec-tokens/s and first audio 152 / 168 / 186 ms against 144.2 k /
         #  182 ms on ONE 512-slot engine; NeuTTS-Air bf16: 256 streams over 4 x 64 slots 80.3 k against 100.5 k on one engine, 512 streams over
         #  4 x 128 111.9 k against 114.9 k -- four chains stream Air's larger weights four times; profiles/r05o_sweep_stream_gang*.txt)
         if (self.gang is not None and len(prompts) > 1 and getattr(self, "stream_on_gang", False) and self._stream_on_device(ref_codes)):
-            yield from self._infer_stream_batch_gang(prompts, ref_codes)
+            yield from self._infer_stream_batch_gang(prompts, ref_codes, samp)
             return
         eng = self.backbone
         n = len(prompts)
@@ -746,7 +801,7 @@ class NeuTTS:
                 while i1 < n and (i1 == i0 or used + len(prompts[i1]) <= budget):
                     used += len(prompts[i1])
                     i1 += 1
-                eng.prefill(prompts[i0:i1], slots[i0:i1], [self._sampling(len(prompts[i]), i) for i in range(i0, i1)])
+                eng.prefill(prompts[i0:i1], slots[i0:i1], [self._sampling(len(prompts[i]), i, samp) for i in range(i0, i1)])
                 i0 = i1
         except Exception:                  # a later group failed: the earlier groups' slots must not stay RUNNING
             eng.sync()
