@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define NTTS_ABI_VERSION 10
+#define NTTS_ABI_VERSION 11
 
 enum {
     NTTS_OK = 0,
@@ -176,7 +176,19 @@ int ntts_backbone_activate(ntts_backbone* e, int32_t n, const int32_t* park_slot
  * (ref:neutts/neutts.py:338-347).
  * ABI 10: top_p / min_p, appended (generate()'s own keyword arguments of those names, which the reference's call leaves at their
  * defaults).  The warpers run in the order of hf:generation/utils.py _get_logits_processor: temperature -> top_k -> top_p -> min_p ->
- * multinomial.  With top_p = 1 and min_p = 0 a request draws exactly the ids it drew under ABI 9. */
+ * multinomial.  With top_p = 1 and min_p = 0 a request draws exactly the ids it drew under ABI 9.
+ * ABI 11: repetition_penalty / prompt_ignore_length, appended (generate()'s keyword argument `repetition_penalty`, which the reference's call leaves at
+ * 1.0, and RepetitionPenaltyLogitsProcessor's `prompt_ignore_length`: hf:generation/logits_process.py).  The processor runs FIRST in
+ * hf:generation/utils.py _get_logits_processor -- before MinNewTokensLength and the warpers -- and so applies to greedy and sampled requests alike: for
+ * every token id that occurs in the request's prompt (from position prompt_ignore_length on) or in what it has generated so far,
+ * score = score * p if score < 0 else score / p.  It lives in the lm_head epilogue, on a per-slot bitmap of seen tokens that follows the request
+ * through parking rows and slot recycling.
+ * NUMERICS: the penalised value is bf16_rne(fp32(v) * p) or bf16_rne(fp32(v) / p), v = the bf16 logit the lm_head produces.  HF keeps the fp32 product;
+ * the engine rounds it ONCE, because its exact 16-bit top-k select and its argmax partials both work on bf16 rows and must agree with each other.  The
+ * deviation from HF is at most half a bf16 ulp of the penalised logit (relative 2^-8) and touches penalised tokens only: the one place where the
+ * processed logits (ntts_backbone_read_logits) are not HF's value for value.  -inf (a masked EOS) stays -inf for any valid p; no NaN arises.
+ * With repetition_penalty = 1 (or 0, a zeroed field) a request computes exactly what it computed under ABI 10, and an engine that has no penalised
+ * request in flight runs exactly the kernels it ran under ABI 10. */
 typedef struct ntts_sampling {
     int32_t max_length;      /* total length cap (prompt + new), <= max_context        [2048] */
     int32_t min_new_tokens;  /* EOS logit = -inf while fewer new tokens than this      [50]   */
@@ -191,6 +203,10 @@ typedef struct ntts_sampling {
     float min_p;             /* [0.0] [0, 1].  > 0: a token survives iff its probability is >= min_p x the largest probability
                               * (MinPLogitsWarper, hf:generation/logits_process.py).  Ignored when do_sample = 0.
                               * Either field NaN or out of range: NTTS_EINVAL from the prefill call, naming the prompt; no slot is touched */
+    float repetition_penalty;      /* [1.0] finite and > 0; 1 = off, and so is 0 (a zeroed field, as with ntts_backbone_config.park_slots).  NaN, negative or
+                                    * inf: NTTS_EINVAL from the prefill call, naming the prompt; no slot is touched */
+    int32_t prompt_ignore_length;  /* [0] >= 0: the first so many prompt ids do not count as seen (0 = HF's default, the whole prompt counts; a value above
+                                    * the prompt length means the whole prompt is ignored: generated tokens only).  Ignored when the penalty is off */
 } ntts_sampling;
 
 /* Prefill `n` prompts (packed back to back in `ids`, prompt i has lens[i] tokens) into the decode
@@ -292,6 +308,11 @@ int ntts_backbone_sync(ntts_backbone* e);
  * `keep_logits` was enabled; row = slot. */
 int ntts_backbone_set_debug(ntts_backbone* e, int32_t keep_logits);
 int ntts_backbone_read_logits(ntts_backbone* e, int32_t slot, float* out, int32_t n);
+/* ABI 11.  Blocking debug read of slot `slot`'s row of the seen bitmap the repetition penalty works on: bit c (word c >> 5, bit c & 31) = lm_head
+ * COLUMN c has occurred -- the token id itself, or with ntts_backbone_set_logits_range the position in [lo, hi) followed by the EOS column (ids outside
+ * are not recorded).  n_words 32-bit words are written (zeros past the row's end).  Rows of requests whose penalty is 1 are cleared by the prompt pass
+ * and then left alone.  NTTS_ESTATE while no bitmap exists: it is allocated with the first request whose penalty is not 1. */
+int ntts_backbone_read_seen(ntts_backbone* e, int32_t slot, uint32_t* words_out, int32_t n_words);
 /* Teacher forcing for the margin-aware parity tests: replace the token slot `slot` emitted last
  * (and will feed to the next step) by `token`. */
 int ntts_backbone_debug_force(ntts_backbone* e, int32_t slot, int32_t token);
@@ -539,6 +560,18 @@ int ntts_k_silu_probe(const void* in_bf16_dev, void* out_bf16_dev, int64_t n, in
 int ntts_k_sample_probe(const void* logits_dev, int64_t ld_logits, int32_t rows, int32_t vocab, int32_t group_width, const int32_t* top_k,
                         const float* temperature, const float* top_p, const float* min_p, const uint64_t* seed, int32_t step,
                         int32_t* token_out, int32_t* n_out, int32_t* ids_out);
+
+/* ABI 11.  The engine's lm_head launch (the GEMM tile + argmax / penalty epilogue the decode step runs) on caller-supplied data.  X_dev: DEVICE bf16
+ * [M][K]; W_dev: DEVICE bf16 [N][K] row-major -- the probe packs it the way the engine packs the head (tile-major; fp8 != 0: quantised per output
+ * channel to e4m3, X to e4m3 at the static scale xscale, K % 128 == 0).  variant: 0 = 64 x 64 tile, 1 = 128 x 128, 2 = 256 x 256, 4 = 256 x 288 natural-order
+ * tile (bf16 only), 8 = the small-batch GEMV form (M <= 16, N % 16 == 0).  HOST inputs: seen = [M][(N + 31) / 32] words of seen-column bits, or NULL
+ * for the plain lm_head (rep_pen is then not read); rep_pen = [M] penalties (finite, > 0; 1 = row untouched); mask_eos = [M] column + 1 whose logit is
+ * -inf for that row, 0 = none (may be NULL).  HOST outputs: logits_out fp32 [M][N] (the debug dump), logits_bf16_out [M][N] bit patterns (the row the
+ * sampler reads), part_val / part_idx [M][*n_part] the (max, first index) partials, partial i covering columns [i * *part_width, (i + 1) * *part_width);
+ * part_cap = entries per row available in the two arrays (NTTS_EINVAL if too few). */
+int ntts_k_head_penalty_probe(const void* X_dev, const void* W_dev, int32_t M, int32_t N, int32_t K, int32_t variant, int32_t fp8, float xscale,
+                              const uint32_t* seen, const float* rep_pen, const int32_t* mask_eos, float* logits_out, uint16_t* logits_bf16_out,
+                              float* part_val, int32_t* part_idx, int32_t part_cap, int32_t* n_part, int32_t* part_width);
 
 #ifdef __cplusplus
 }

@@ -15,6 +15,7 @@
 #include <chrono>
 #include <set>
 #include <string>
+#include <cfloat>
 #include <vector>
 
 #include "../../include/neutts_hip.h"
@@ -41,6 +42,7 @@ struct LayerW {
 
 struct HostSlot {
     bool sampling = false;      // do_sample=1 request (needs the bf16 logits row)
+    bool penalised = false;     // repetition_penalty != 1 request (needs the seen bitmap)
     int state = SLOT_FREE;      // host view: FREE / RUNNING (may already be finished on device)
     int prompt_len = 0, max_len = 0;
     int pos_upper = 0;          // upper bound of the device-side pos
@@ -128,6 +130,17 @@ struct ntts_backbone {
     long ldl = 0;
     int n_sampling = 0;              // running slots with do_sample=1
     bool graph_has_logits = false;
+    // Repetition penalty (ABI 11): one bit per lm_head column and slot (parking rows included), allocated with the first penalised request the way
+    // logits_bf16 is with the first sampling one.  While no penalised request is live the lm_head and the sampling kernel get a null pointer and
+    // run exactly the kernels they ran before; the captured steps bake that choice (graph_has_seen), like graph_has_logits.
+    unsigned int* seen = nullptr;    // [B][seen_pitch]
+    long seen_pitch = 0;             // words per row (gemm.h seen_pitch_for: the tiles' padding columns included)
+    int* seen_cols = nullptr;        // [B * max_context] a prompt pass's columns to mark (sample.h seen_mark_prompt_kernel) ...
+    int* seen_cols_host = nullptr;   // ... and their page-locked staging copy, guarded by seen_ev like the meta block's stages (no pageable upload:
+    hipEvent_t seen_ev = nullptr;    //     that would stall the host until the prompt stream reaches the copy)
+    bool seen_ev_used = false;
+    int n_penalised = 0;             // live requests with repetition_penalty != 1
+    bool graph_has_seen = false;
     // ---- decode-step shape, fixed at create() from the batch size (every constant below was swept on MI355X; the losing variants and
     //      their knobs are gone -- DESIGN.md section 4 keeps the numbers, the git history the code)
     int ks_o = 1, ks_d = 1;          // split-K of o_proj / down_proj (fp32 slabs reduced by the norm kernel behind them)
@@ -442,7 +455,7 @@ extern "C" int ntts_backbone_create(const ntts_backbone_config* c, int device, n
     e->slots.resize(B);
 
     // ---- slot state
-    const size_t n_int = (size_t)B * 15 + (size_t)B * c->max_context + (size_t)B * e->max_pages;
+    const size_t n_int = (size_t)B * 16 + (size_t)B * c->max_context + (size_t)B * e->max_pages;
     CR_HIP(hipMalloc((void**)&e->ibuf, n_int * sizeof(int)));
     CR_HIP(hipMemset(e->ibuf, 0, n_int * sizeof(int)));
     int* ip = e->ibuf;
@@ -453,6 +466,11 @@ extern "C" int ntts_backbone_create(const ntts_backbone_config* c, int device, n
     e->sl.temperature = (float*)ip; ip += B;
     e->sl.top_p = (float*)ip; ip += B;
     e->sl.min_p = (float*)ip; ip += B;
+    e->sl.rep_pen = (float*)ip; ip += B;
+    {
+        std::vector<float> ones(B, 1.0f);       // 1 = off: the rows of slots no penalised request has filled are never looked up in the bitmap
+        CR_HIP(hipMemcpy(e->sl.rep_pen, ones.data(), (size_t)B * sizeof(float), hipMemcpyHostToDevice));
+    }
     e->sl.seed = (unsigned int*)ip; ip += 2 * B;
     e->sl.out_tokens = ip; ip += (size_t)B * c->max_context;
     e->sl.out_stride = c->max_context;
@@ -555,7 +573,7 @@ extern "C" int ntts_backbone_create(const ntts_backbone_config* c, int device, n
     CR_HIP(hipMalloc((void**)&e->attn_pf, T * c->num_heads * e->HD * 2));
     CR_HIP(hipMalloc((void**)&e->o_pf, T * H * 2));
     CR_HIP(hipMalloc((void**)&e->act_pf, T * F * 2));
-    e->meta_cap = 2 * T + (size_t)B * (16 + e->max_pages) + (T / 64 + 3 * B) * 2 + 6 * (size_t)B + 3 * (size_t)B * e->max_pages + 64;
+    e->meta_cap = 2 * T + (size_t)B * (19 + e->max_pages) + (T / 64 + 3 * B) * 2 + 6 * (size_t)B + 3 * (size_t)B * e->max_pages + 64;
     CR_HIP(hipMalloc((void**)&e->meta_dev, e->meta_cap * sizeof(int)));
     for (int i = 0; i < ntts_backbone::kMetaStages; ++i) {
         CR_HIP(hipHostMalloc((void**)&e->meta_host[i], e->meta_cap * sizeof(int), hipHostMallocDefault));
@@ -586,7 +604,7 @@ extern "C" void ntts_backbone_destroy(ntts_backbone* e) {
     bool last_reader = true;
     if (e->share) { last_reader = e->share->refs.fetch_sub(1) == 1; if (last_reader) delete e->share; else e->share->last_decode_ns[e->share_idx].store(0); }
     void* bufs[] = {last_reader ? e->arena : nullptr, e->gu_map_gate, e->gu_map_up, e->kv, e->ibuf, e->h_dec, e->xn_dec, e->qkv_dec, e->attn_dec,
-                    e->act_dec, e->slabs, e->slabs2, e->h_alt, e->part_val, e->part_idx, e->logits, e->logits_bf16, e->h_pf, e->xn_pf, e->qkv_pf, e->attn_pf,
+                    e->act_dec, e->slabs, e->slabs2, e->h_alt, e->part_val, e->part_idx, e->logits, e->logits_bf16, e->seen, e->seen_cols, e->h_pf, e->xn_pf, e->qkv_pf, e->attn_pf,
                     e->o_pf, e->act_pf, e->meta_dev, e->as_scores, e->as_stats, e->as_oslabs, e->step_meta, e->rope_rows};
     for (void* b : bufs)
         if (b) hipFree(b);
@@ -597,6 +615,8 @@ extern "C" void ntts_backbone_destroy(ntts_backbone* e) {
         if (e->meta_ev[i]) hipEventDestroy(e->meta_ev[i]);
     }
     if (e->small_host) hipHostFree(e->small_host);
+    if (e->seen_cols_host) hipHostFree(e->seen_cols_host);
+    if (e->seen_ev) hipEventDestroy(e->seen_ev);
     for (int i = 0; i < ntts_backbone::kSmallStages; ++i)
         if (e->small_ev[i]) hipEventDestroy(e->small_ev[i]);
     if (e->snap_host) hipHostFree(e->snap_host);
@@ -1208,17 +1228,8 @@ static void k_lm_head(ntts_backbone* e, bool keep_logits, int rows) {
     a.part_val = e->part_val; a.part_idx = e->part_idx; a.mask_eos = e->sl.mask_eos;
     a.logits = keep_logits ? e->logits : nullptr; a.ld_logits = V;
     a.logits_bf16 = (keep_logits && e->n_sampling > 0) ? e->logits_bf16 : nullptr; a.ld_logits_bf16 = e->ldl;
-    switch (e->head_tile) {     // (the 256-row tiles stream W with the non-temporal policy: read once per step)
-        case 0: gemm_skinny<EPI_ARGMAX>(a, 1, e->stream); break;
-        case 4: gemm_launch<4, 3, 4, EPI_ARGMAX, 2, 0, 64, true, false, 6>(a, 1, e->stream); break;   // natural-order 256 x 288 (bf16)
-        case 2:
-            if (e->fp8) gemm_launch<4, 4, 4, EPI_ARGMAX, 2, 0, 64, true, true>(a, 1, e->stream);
-            else gemm_launch<4, 4, 4, EPI_ARGMAX, 2, 0, 64, true>(a, 1, e->stream);
-            break;
-        default:
-            if (e->fp8) gemm_launch<2, 2, 4, EPI_ARGMAX, 2, 0, 64, false, true>(a, 1, e->stream);
-            else gemm_launch<2, 2, 4, EPI_ARGMAX, 2>(a, 1, e->stream);
-    }
+    if (e->n_penalised > 0) { a.seen = e->seen; a.seen_pitch = e->seen_pitch; a.rep_pen = e->sl.rep_pen; }
+    lm_head_launch(a, e->head_tile, e->fp8, e->stream);     // (gemm.h: the tile per head_tile, with or without the penalty epilogue)
 }
 
 static void lm_head_and_sample(ntts_backbone* e, int phase) {
@@ -1229,6 +1240,7 @@ static void lm_head_and_sample(ntts_backbone* e, int phase) {
     s.part_width = e->small ? 16 : e->head_tile == 4 ? 96 : 64;
     s.logits = e->n_sampling > 0 ? e->logits_bf16 : nullptr; s.ld_logits = e->ldl; s.vocab = e->lr_rows ? e->lr_rows : e->cfg.vocab_size;
     if (e->lr_rows) { s.n_range = e->lr_rows - 1; s.id_base = e->lr_lo; s.id_tail = e->lr_eos; }
+    if (e->n_penalised > 0) { s.seen = e->seen; s.seen_pitch = e->seen_pitch; }
     NTTS_LAUNCH((sample_greedy_kernel), dim3(rows), dim3(256), e->stream, s);
 }
 
@@ -1460,8 +1472,8 @@ static void ks_lm_head(ntts_backbone* e, bool keep_logits) {
     a.part_val = e->part_val; a.part_idx = e->part_idx; a.mask_eos = e->sl.mask_eos;
     a.logits = keep_logits ? e->logits : nullptr; a.ld_logits = V;
     a.logits_bf16 = (keep_logits && e->n_sampling > 0) ? e->logits_bf16 : nullptr; a.ld_logits_bf16 = e->ldl;
-    if (e->fp8) { gemv_launch<EPI_ARGMAX, false, 4, true>(a, 1, e->stream); return; }
-    gemv_launch<EPI_ARGMAX, false>(a, 1, e->stream);
+    if (e->n_penalised > 0) { a.seen = e->seen; a.seen_pitch = e->seen_pitch; a.rep_pen = e->sl.rep_pen; }
+    lm_head_gemv_launch(a, e->fp8, e->stream);
 }
 
 static void decode_step_small(ntts_backbone* e) {
@@ -1549,6 +1561,9 @@ static hipError_t upload_meta(ntts_backbone* e, const int* src, size_t n, hipStr
     return hipEventRecord(e->meta_ev[k], st);
 }
 
+// the penalty a request runs with: a zeroed field means off, like 1
+static float rep_penalty_of(const ntts_sampling& s) { return s.repetition_penalty == 0.f ? 1.0f : s.repetition_penalty; }
+
 // Prompt pass.  With donor_slot / shared_len (ntts_backbone_prefill_shared): prompt i re-uses the KV pages that hold the
 // first pos0[i] = floor(shared_len[i] / 32) * 32 tokens of its donor's prompt -- only the remaining tokens are packed,
 // embedded and pushed through the layers; their queries attend to the shared pages exactly as they would to their own.
@@ -1578,6 +1593,12 @@ static int prefill_impl(ntts_backbone* e, int32_t n, const int32_t* ids, const i
             return fail(e, NTTS_EINVAL, "prompt %d: top_p must lie in (0, 1] (got %g)", i, samp[i].top_p);
         if (samp[i].do_sample && !(samp[i].min_p >= 0.f && samp[i].min_p <= 1.0f))
             return fail(e, NTTS_EINVAL, "prompt %d: min_p must lie in [0, 1] (got %g)", i, samp[i].min_p);
+        // RepetitionPenaltyLogitsProcessor's own range (hf:generation/logits_process.py: a strictly positive float); 0 = a zeroed field = off.  A NaN fails
+        // every comparison but the first
+        if (samp[i].repetition_penalty != 0.f && !(samp[i].repetition_penalty > 0.f && samp[i].repetition_penalty <= FLT_MAX))
+            return fail(e, NTTS_EINVAL, "prompt %d: repetition_penalty must be finite and > 0 (got %g)", i, samp[i].repetition_penalty);
+        if (rep_penalty_of(samp[i]) != 1.0f && samp[i].prompt_ignore_length < 0)
+            return fail(e, NTTS_EINVAL, "prompt %d: prompt_ignore_length must be >= 0 (got %d)", i, samp[i].prompt_ignore_length);
         if (samp[i].eos_token_id < 0 || samp[i].eos_token_id >= c.vocab_size) return fail(e, NTTS_EINVAL, "eos id out of range");
         if (e->lr_rows && samp[i].eos_token_id != e->lr_eos)
             return fail(e, NTTS_EINVAL, "prompt %d: eos id %d, but the restricted lm_head was set up for eos id %d (ntts_backbone_set_logits_range)", i, samp[i].eos_token_id, e->lr_eos);
@@ -1676,6 +1697,25 @@ static int prefill_impl(ntts_backbone* e, int32_t n, const int32_t* ids, const i
     for (int i = 0; i < n; ++i) { int b; const float t = samp[i].do_sample ? samp[i].top_p : 1.0f; memcpy(&b, &t, 4); m.push_back(b); }
     const size_t o_minp = m.size();
     for (int i = 0; i < n; ++i) { int b; const float t = samp[i].do_sample ? samp[i].min_p : 0.0f; memcpy(&b, &t, 4); m.push_back(b); }
+    const size_t o_pen = m.size();
+    for (int i = 0; i < n; ++i) { int b; const float t = rep_penalty_of(samp[i]); memcpy(&b, &t, 4); m.push_back(b); }
+    // the lm_head columns every penalised request's prompt marks in its bitmap row: ids[prompt_ignore_length ..] of the FULL prompt (a shared prefix
+    // counts like any other token), mapped to columns -- with a restricted head [range | EOS], ids it does not have are dropped
+    std::vector<int> mark_cols;
+    const size_t o_moff = m.size();
+    int add_pen = 0;
+    for (int i = 0; i < n; ++i) {
+        m.push_back((int)mark_cols.size());
+        if (rep_penalty_of(samp[i]) == 1.0f) continue;
+        ++add_pen;
+        for (int t = std::min(samp[i].prompt_ignore_length, lens[i]); t < lens[i]; ++t) {
+            const int id = ids[id_off[i] + t];
+            if (!e->lr_rows) mark_cols.push_back(id);
+            else if (id >= e->lr_lo && id < e->lr_hi) mark_cols.push_back(id - e->lr_lo);
+            else if (id == e->lr_eos) mark_cols.push_back(e->lr_rows - 1);
+        }
+    }
+    m.push_back((int)mark_cols.size());
     const size_t o_seed = m.size();
     for (int i = 0; i < n; ++i) { m.push_back((int)(uint32_t)samp[i].seed); m.push_back((int)(uint32_t)(samp[i].seed >> 32)); }
     const size_t o_last = m.size();
@@ -1727,6 +1767,26 @@ static int prefill_impl(ntts_backbone* e, int32_t n, const int32_t* ids, const i
         for (int i = 0; i < n; ++i) e->slots[slots[i]].sampling = samp[i].do_sample != 0;
         e->n_sampling += add;
     }
+    if (add_pen && !e->seen) {   // the first penalised request: the bitmap of every slot, zeroed (rows are cleared again by each prompt pass that fills them)
+        const long pitch = seen_pitch_for(c.vocab_size);
+        unsigned int* bm = nullptr;
+        int* cols = nullptr;
+        hipError_t rc = hipStreamSynchronize(e->stream);
+        if (rc == hipSuccess) rc = hipMalloc((void**)&bm, (size_t)B * pitch * sizeof(unsigned int));
+        if (rc == hipSuccess) rc = hipMemset(bm, 0, (size_t)B * pitch * sizeof(unsigned int));
+        if (rc == hipSuccess) rc = hipMalloc((void**)&cols, (size_t)B * c.max_context * sizeof(int));
+        if (rc == hipSuccess && !e->seen_cols_host) rc = hipHostMalloc((void**)&e->seen_cols_host, (size_t)B * c.max_context * sizeof(int), hipHostMallocDefault);
+        if (rc == hipSuccess && !e->seen_ev) rc = hipEventCreateWithFlags(&e->seen_ev, hipEventDisableTiming);
+        if (rc != hipSuccess) {
+            if (bm) (void)hipFree(bm);
+            if (cols) (void)hipFree(cols);
+            for (int i = 0; i < n; ++i) { HostSlot& s = e->slots[slots[i]]; drop_pages(e, s); if (s.sampling) { s.sampling = false; e->n_sampling--; } }
+            return fail(e, NTTS_EHIP, "seen bitmap allocation failed: %s", hipGetErrorString(rc));
+        }
+        e->seen = bm; e->seen_pitch = pitch; e->seen_cols = cols;
+    }
+    for (int i = 0; i < n; ++i) e->slots[slots[i]].penalised = rep_penalty_of(samp[i]) != 1.0f;
+    e->n_penalised += add_pen;
     // With a side stream the whole pass (meta upload included) runs there, ordered behind the work already on the engine's
     // stream and followed by that stream; every launch helper reads e->stream, so it is swapped for the duration of the call.
     // If the ordering events cannot be recorded the pass stays on the engine's own stream (correct, merely not CU-masked);
@@ -1759,9 +1819,21 @@ static int prefill_impl(ntts_backbone* e, int32_t n, const int32_t* ids, const i
     HIPCHK(e, hipEventRecord(e->ev[0], st));
     PrefillInit pi{};
     pi.slot = md + o_slot; pi.seq_len = md + o_len; pi.min_new = md + o_min; pi.max_len = md + o_max; pi.eos = md + o_eos;
-    pi.top_k = md + o_topk; pi.temp_bits = md + o_temp; pi.top_p_bits = md + o_topp; pi.min_p_bits = md + o_minp; pi.seed = md + o_seed;
+    pi.top_k = md + o_topk; pi.temp_bits = md + o_temp; pi.top_p_bits = md + o_topp; pi.min_p_bits = md + o_minp; pi.pen_bits = md + o_pen; pi.seed = md + o_seed;
+    pi.seen = e->seen; pi.seen_pitch = e->seen_pitch;
     pi.bt_rows = md + o_bt; pi.block_table = e->block_table; pi.max_pages = e->max_pages; pi.n = n; pi.sl = e->sl;
     NTTS_LAUNCH((prefill_init_kernel), dim3(n), dim3(64), st, pi);
+    if (add_pen) {   // (the device buffer is re-used stream-ordered behind the previous pass's marking kernel; the pinned stage waits for its last copy)
+        if (!mark_cols.empty()) {
+            if (e->seen_ev_used) HIPCHK(e, hipEventSynchronize(e->seen_ev));
+            memcpy(e->seen_cols_host, mark_cols.data(), mark_cols.size() * sizeof(int));
+            HIPCHK(e, hipMemcpyAsync(e->seen_cols, e->seen_cols_host, mark_cols.size() * sizeof(int), hipMemcpyHostToDevice, st));
+            HIPCHK(e, hipEventRecord(e->seen_ev, st));
+            e->seen_ev_used = true;
+        }
+        SeenMarkArgs sm{md + o_slot, md + o_moff, e->seen_cols, e->seen, e->seen_pitch};
+        NTTS_LAUNCH((seen_mark_prompt_kernel), dim3(n), dim3(256), st, sm);
+    }
 
     const int Ti = (int)T;
     NormArgs n0{};
@@ -1949,8 +2021,9 @@ extern "C" int ntts_backbone_decode(ntts_backbone* e, int32_t n_steps) {
         const int nt = (int)trip.size() / 3;
         NTTS_LAUNCH((bt_update_kernel), dim3((nt + 63) / 64), dim3(64), st, (const int*)e->meta_dev, nt, e->block_table, e->max_pages);
     }
-    if ((e->graph || e->graph_split || e->graph_shape[0] || e->graph_shape[1]) && e->graph_has_logits != (e->n_sampling > 0))   // the step's launch arguments changed:
-        drop_graphs(e);                                                                                                            // every capture is stale
+    if ((e->graph || e->graph_split || e->graph_shape[0] || e->graph_shape[1]) &&
+        (e->graph_has_logits != (e->n_sampling > 0) || e->graph_has_seen != (e->n_penalised > 0)))   // the step's launch arguments (and the lm_head's kernel) changed:
+        drop_graphs(e);                                                                             // every capture is stale
     // small-batch path: steps whose longest context has reached attn_split_ctx run the context-split attention (its own graph)
     const bool can_split = e->attn_split > 0 && !e->attn_tl;
     auto wants_split = [&](int step) { return can_split && ctx_now + step >= e->attn_split_ctx; };
@@ -1968,6 +2041,7 @@ extern "C" int ntts_backbone_decode(ntts_backbone* e, int32_t n_steps) {
     if (e->use_graph && can_split && wants_split(n_steps - 1) && !e->graph_split_tried) {
         e->graph_split_tried = true;
         e->graph_has_logits = e->n_sampling > 0;
+        e->graph_has_seen = e->n_penalised > 0;
         e->split_active = true;
         capture(1, &e->graph_split);
         e->split_active = false;
@@ -1975,6 +2049,7 @@ extern "C" int ntts_backbone_decode(ntts_backbone* e, int32_t n_steps) {
     if (e->use_graph && !e->graph_tried) {
         e->graph_tried = true;
         e->graph_has_logits = e->n_sampling > 0;
+        e->graph_has_seen = e->n_penalised > 0;
         capture(1, &e->graph);   // several steps per graph were measured: -0.3 % per step (profiles/r02a_sweep_nt_graphsteps.jsonl), not kept
     }
     HIPCHK(e, hipEventRecord(e->ev[2], st));
@@ -2212,6 +2287,7 @@ static int release_host(ntts_backbone* e, int32_t slot) {   // host half of a re
     drop_pages(e, s);
     s.prompt.clear();
     if (s.sampling) { s.sampling = false; e->n_sampling--; }
+    if (s.penalised) { s.penalised = false; e->n_penalised--; }
     s.state = SLOT_FREE;
     s.gen++;
     return NTTS_OK;
@@ -2271,6 +2347,7 @@ extern "C" int ntts_backbone_activate(ntts_backbone* e, int32_t n, const int32_t
     HIPCHK(e, upload_meta(e, pairs.data(), pairs.size(), e->stream));
     ActivateArgs a{};
     a.pairs = e->meta_dev; a.sl = e->sl; a.block_table = e->block_table; a.max_pages = e->max_pages;
+    a.seen = e->seen; a.seen_pitch = e->seen_pitch;
     NTTS_LAUNCH((activate_slots_kernel), dim3(n), dim3(64), e->stream, a);
     for (int i = 0; i < n; ++i) {
         HostSlot& src = e->slots[park_slots[i]];
@@ -2329,6 +2406,17 @@ extern "C" int ntts_backbone_read_logits(ntts_backbone* e, int32_t slot, float* 
         return NTTS_OK;
     }
     HIPCHK(e, hipMemcpy(out, e->logits + (size_t)slot * e->cfg.vocab_size, n * sizeof(float), hipMemcpyDeviceToHost));
+    return NTTS_OK;
+}
+
+extern "C" int ntts_backbone_read_seen(ntts_backbone* e, int32_t slot, uint32_t* words_out, int32_t n_words) {
+    if (!e || !words_out || n_words < 1 || slot < 0 || slot >= e->cfg.max_batch) return fail(e, NTTS_EINVAL, "bad argument");
+    if (!e->seen) return fail(e, NTTS_ESTATE, "no seen bitmap yet: it is allocated with the first request whose repetition_penalty is not 1");
+    HIPCHK(e, hipSetDevice(e->device));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    const long have = std::min<long>(n_words, e->seen_pitch);
+    HIPCHK(e, hipMemcpy(words_out, e->seen + (size_t)slot * e->seen_pitch, (size_t)have * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    for (long k = have; k < n_words; ++k) words_out[k] = 0;
     return NTTS_OK;
 }
 

@@ -4,8 +4,11 @@
 
 #include "../../include/neutts_hip.h"
 #include "kernels/gemm.h"
+#include "kernels/gemv.h"
 #include "kernels/norm.h"
 #include "kernels/sample.h"
+
+#include <string.h>
 
 #include <vector>
 
@@ -418,4 +421,95 @@ extern "C" int ntts_k_mfma_probe(float* out_dev_768) {
     if (!out_dev_768) return NTTS_EINVAL;
     NTTS_LAUNCH((mfma_probe_kernel), dim3(1), dim3(64), (hipStream_t)0, out_dev_768);
     return hipDeviceSynchronize() == hipSuccess ? NTTS_OK : NTTS_EHIP;
+}
+
+// ---- the lm_head launch of the decode step (gemm.h lm_head_launch / gemv.h lm_head_gemv_launch) on caller-supplied operands: the penalty epilogue of
+//      every tile variant against tests/repetition_spec.py.  The head is packed here by the kernels the engine packs it with.
+extern "C" int ntts_k_head_penalty_probe(const void* X_dev, const void* W_dev, int32_t M, int32_t N, int32_t K, int32_t variant, int32_t fp8, float xscale,
+                                         const uint32_t* seen, const float* rep_pen, const int32_t* mask_eos, float* logits_out,
+                                         uint16_t* logits_bf16_out, float* part_val, int32_t* part_idx, int32_t part_cap, int32_t* n_part,
+                                         int32_t* part_width) {
+    if (!X_dev || !W_dev || !logits_out || !logits_bf16_out || !part_val || !part_idx || !n_part || !part_width) return NTTS_EINVAL;
+    if (M < 1 || N < 16 || K < 64 || (K % 64) || (fp8 && (K % 128))) return NTTS_EINVAL;
+    if (variant != 0 && variant != 1 && variant != 2 && variant != 4 && variant != 8) return NTTS_EINVAL;
+    if ((variant == 4 && fp8) || (variant == 8 && (M > kGemvRows || (N % 16) || K > 1024))) return NTTS_EINVAL;
+    if (fp8 && !(xscale > 0.f)) return NTTS_EINVAL;
+    if (seen) {
+        if (!rep_pen) return NTTS_EINVAL;
+        for (int m = 0; m < M; ++m)
+            if (!(rep_pen[m] > 0.f && rep_pen[m] <= 3.0e38f)) return NTTS_EINVAL;
+    }
+    const int width = variant == 8 ? 16 : variant == 4 ? 96 : 64;
+    const int np = variant == 8 ? N / 16 : variant == 0 ? (N + 63) / 64 : variant == 4 ? ((N + 287) / 288) * 3 : variant == 2 ? ((N + 255) / 256) * 4 : ((N + 127) / 128) * 2;
+    if (part_cap < np) return NTTS_EINVAL;
+    const long Np = ((long)N + 63) / 64 * 64, ldl = ((long)N + 7) / 8 * 8, pitch = seen_pitch_for(N), wsrc = ((long)N + 31) / 32;
+    const size_t esz = fp8 ? 1 : 2;
+    struct Buf { void* p = nullptr; ~Buf() { if (p) (void)hipFree(p); } };
+    Buf wt, ws, xq, xf, lg, lb, pv, pi, bm, pen, me;
+    auto dalloc = [](Buf& b, size_t bytes) { return hipMalloc(&b.p, bytes) == hipSuccess && hipMemset(b.p, 0, bytes) == hipSuccess; };
+    if (!dalloc(wt, (size_t)Np * K * esz) || !dalloc(lg, (size_t)M * N * 4) || !dalloc(lb, (size_t)M * ldl * 2) || !dalloc(pv, (size_t)M * np * 4) ||
+        !dalloc(pi, (size_t)M * np * 4) || !dalloc(me, (size_t)M * 4)) return NTTS_ENOMEM;
+    const hipStream_t st = (hipStream_t)0;
+    {   // (plain pointers for the launches: the emulator's launch captures its arguments by value)
+        const void* src = W_dev;
+        const int* nomap = nullptr;
+        if (fp8) {
+            if (!dalloc(ws, (size_t)Np * 4) || !dalloc(xq, (size_t)M * K) || !dalloc(xf, (size_t)M * K * 4)) return NTTS_ENOMEM;
+            unsigned char* dst = (unsigned char*)wt.p;
+            float* sc = (float*)ws.p;
+            NTTS_LAUNCH((pack_weight_fp8_kernel), dim3((unsigned)N), dim3(256), st, src, 0, dst, sc, nomap, 0L, (long)K);
+            std::vector<bf16_t> xb((size_t)M * K);
+            std::vector<float> xw((size_t)M * K);
+            if (hipMemcpy(xb.data(), X_dev, xb.size() * 2, hipMemcpyDeviceToHost) != hipSuccess) return NTTS_EHIP;
+            for (size_t i = 0; i < xb.size(); ++i) { const unsigned int u = (unsigned int)xb[i] << 16; memcpy(&xw[i], &u, 4); }
+            if (hipMemcpy(xf.p, xw.data(), xw.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return NTTS_EHIP;
+            const float* xin = (const float*)xf.p;
+            unsigned char* xout = (unsigned char*)xq.p;
+            const long nx = (long)M * K;
+            NTTS_LAUNCH((fp8_quantize_kernel), dim3((unsigned)((nx + 511) / 512)), dim3(256), st, xin, xout, nx, 1.0f / xscale);
+        } else {
+            bf16_t* dst = (bf16_t*)wt.p;
+            NTTS_LAUNCH((pack_weight_kernel), dim3((unsigned)N), dim3(256), st, src, 0, dst, nomap, 0L, (long)K, 1);
+        }
+    }
+    if (mask_eos && hipMemcpy(me.p, mask_eos, (size_t)M * 4, hipMemcpyHostToDevice) != hipSuccess) return NTTS_EHIP;
+    if (seen) {
+        if (!dalloc(bm, (size_t)M * pitch * 4) || !dalloc(pen, (size_t)M * 4)) return NTTS_ENOMEM;
+        for (int m = 0; m < M; ++m)
+            if (hipMemcpy((unsigned int*)bm.p + (size_t)m * pitch, seen + (size_t)m * wsrc, (size_t)wsrc * 4, hipMemcpyHostToDevice) != hipSuccess) return NTTS_EHIP;
+        if (N % 32) {    // bits past column N - 1 in the caller's last word are not columns: dropped
+            std::vector<unsigned int> last(M);
+            for (int m = 0; m < M; ++m) last[m] = seen[(size_t)m * wsrc + wsrc - 1] & ((1u << (N % 32)) - 1u);
+            for (int m = 0; m < M; ++m)
+                if (hipMemcpy((unsigned int*)bm.p + (size_t)m * pitch + wsrc - 1, &last[m], 4, hipMemcpyHostToDevice) != hipSuccess) return NTTS_EHIP;
+        }
+        if (hipMemcpy(pen.p, rep_pen, (size_t)M * 4, hipMemcpyHostToDevice) != hipSuccess) return NTTS_EHIP;
+    }
+    const bf16_t* X = fp8 ? (const bf16_t*)xq.p : (const bf16_t*)X_dev;
+    if (variant == 8) {
+        GemvArgs a{};
+        a.X = X; a.ldx = K; a.W = (const bf16_t*)wt.p; a.ldw = K; a.w_tile_major = 1; a.slab_rows = M; a.M = M; a.N = N; a.K = K; a.n_valid = N;
+        a.wscale = fp8 ? (const float*)ws.p : nullptr; a.xscale = xscale;
+        a.part_val = (float*)pv.p; a.part_idx = (int*)pi.p; a.mask_eos = (const int*)me.p;
+        a.logits = (float*)lg.p; a.ld_logits = N; a.logits_bf16 = (bf16_t*)lb.p; a.ld_logits_bf16 = ldl;
+        if (seen) { a.seen = (const unsigned int*)bm.p; a.seen_pitch = pitch; a.rep_pen = (const float*)pen.p; }
+        lm_head_gemv_launch(a, fp8 != 0, st);
+    } else {
+        GemmArgs a{};
+        a.w_tile_major = 1;
+        a.X = X; a.ldx = K; a.W = (const bf16_t*)wt.p; a.ldw = K; a.M = M; a.N = N; a.K = K;
+        a.wscale = fp8 ? (const float*)ws.p : nullptr; a.xscale = xscale;
+        a.part_val = (float*)pv.p; a.part_idx = (int*)pi.p; a.mask_eos = (const int*)me.p;
+        a.logits = (float*)lg.p; a.ld_logits = N; a.logits_bf16 = (bf16_t*)lb.p; a.ld_logits_bf16 = ldl;
+        if (seen) { a.seen = (const unsigned int*)bm.p; a.seen_pitch = pitch; a.rep_pen = (const float*)pen.p; }
+        lm_head_launch(a, variant, fp8 != 0, st);
+    }
+    if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess) return NTTS_EHIP;
+    if (hipMemcpy(logits_out, lg.p, (size_t)M * N * 4, hipMemcpyDeviceToHost) != hipSuccess) return NTTS_EHIP;
+    if (hipMemcpy2D(logits_bf16_out, (size_t)N * 2, lb.p, (size_t)ldl * 2, (size_t)N * 2, (size_t)M, hipMemcpyDeviceToHost) != hipSuccess) return NTTS_EHIP;
+    if (hipMemcpy(part_val, pv.p, (size_t)M * np * 4, hipMemcpyDeviceToHost) != hipSuccess) return NTTS_EHIP;
+    if (hipMemcpy(part_idx, pi.p, (size_t)M * np * 4, hipMemcpyDeviceToHost) != hipSuccess) return NTTS_EHIP;
+    *n_part = np;
+    *part_width = width;
+    return NTTS_OK;
 }

@@ -34,9 +34,13 @@ enum GemmEpi {
     EPI_BF16_SILU = 4, // out bf16 = bf16(silu(acc + bias))   (codec MLP fc1; the codec reference is fp32)
     EPI_F32 = 5,       // out fp32 [M][N] = acc + bias (+ fp32 residual): codec residual stream / ISTFT head / DFT
     EPI_RESID = 6,     // out bf16 [M][N] = bf16(resid_bf16 + bf16(acc + bias)): o_proj + residual add (may be in place)
-    EPI_SILU_SPLIT3 = 7  // codec, precision = high: v = silu(acc + bias) leaves as a SPLIT bf16 operand row [hi | lo | hi] of 3 N columns
+    EPI_SILU_SPLIT3 = 7, // codec, precision = high: v = silu(acc + bias) leaves as a SPLIT bf16 operand row [hi | lo | hi] of 3 N columns
                          // (hi = bf16(v), lo = bf16(v - hi); ldo = 3 N): the next GEMM's K-loop over [wh | wh | wl] sees v to ~16 mantissa bits
+    EPI_ARGMAX_PEN = 8   // EPI_ARGMAX with the repetition penalty (GemmArgs::seen / rep_pen) applied to bf16(acc) ahead of everything that reads the logit; the
+                         // EOS mask then overwrites its column as before (-inf either way: the two commute for any valid penalty).  A kernel
+                         // of its own, launched only while a penalised request is live: the plain lm_head keeps its instructions and its registers
 };
+constexpr bool epi_is_argmax(int epi) { return epi == EPI_ARGMAX || epi == EPI_ARGMAX_PEN; }
 
 struct GemmArgs {
     const bf16_t* X;
@@ -65,6 +69,10 @@ struct GemmArgs {
     long ld_logits;
     bf16_t* logits_bf16;   // optional bf16 [M][ld_logits_bf16] processed logits for the top-k sampler
     long ld_logits_bf16;
+    // EPI_ARGMAX_PEN: RepetitionPenaltyLogitsProcessor (hf:generation/logits_process.py) on the columns a row has seen
+    const unsigned int* seen;   // [M][seen_pitch] bitmap, bit c of a row (word c >> 5, bit c & 31) = lm_head COLUMN c occurred in that row's prompt or output;
+    long seen_pitch;            // words per row, padded so that every column of every tile (N rounded up to the widest tile, 288) has its word
+    const float* rep_pen;       // [M] penalty per row, finite and > 0; exactly 1 = the row is left alone (its bitmap is not read)
     // EPI_F32
     const float* resid;    // optional fp32 [M][ldr] added in the epilogue (may alias out)
     long ldr;
@@ -165,6 +173,9 @@ NTTS_D f32x2 silu_fast2(f32x2 x) {
     sg[1] = x[1] >= 0.f ? r[1] : tr[1];
     return x * sg;
 }
+// The penalised logit: v * p below zero, v / p from zero up (HF's own fp32 arithmetic: an IEEE division, not a reciprocal), then ONE rounding to
+// bf16 -- the sampler's 16-bit radix select and the argmax partials both work on bf16 rows.  -inf (a masked EOS) stays -inf, NaN stays NaN.
+NTTS_D float rep_penalised(float v, float pen) { return rbf(v < 0.f ? v * pen : v / pen); }
 NTTS_D float gemm_bias(const GemmArgs& p, int n) { return p.bias_f32 ? p.bias_f32[n] : (p.bias ? bf2f(p.bias[n]) : 0.f); }
 
 // ---- epilogue shared by the GEMM kernels: lane owns token m (per a) x features nb16 .. nb16+15
@@ -355,10 +366,24 @@ NTTS_D void gemm_epilogue(const GemmArgs& p, f32x4 (&acc)[TM][4], int mrow0, int
 #pragma unroll
                 for (int j = 0; j < 4; ++j) *(f32x4*)(dst + j * 4) = acc[a][j];
             }
-        } else if constexpr (EPI == EPI_ARGMAX) {
+        } else if constexpr (epi_is_argmax(EPI)) {
             float best = -INFINITY;
             int bidx = 0x7fffffff;
             const int meos = (mok && p.mask_eos) ? p.mask_eos[m] : 0;   // eos id + 1, or 0
+            if constexpr (EPI == EPI_ARGMAX_PEN) {
+                // this lane's 16 columns start at a multiple of 16: their seen bits are ONE halfword of the row.  The penalised value replaces the
+                // accumulator in place (rounding it again below changes nothing), so the dump, the bf16 row and the partials all see it
+                const float pen = mok ? p.rep_pen[m] : 1.0f;
+                unsigned int sbits = 0;
+                if (pen != 1.0f) sbits = ((const unsigned short*)(p.seen + (long)m * p.seen_pitch))[nb16 >> 4];
+                if (sbits) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r)
+                            if ((sbits >> (j * 4 + r)) & 1u) acc[a][j][r] = rep_penalised(rbf(acc[a][j][r]), pen);
+                }
+            }
             alignas(16) bf16_t lo[16];
 #pragma unroll
             for (int j = 0; j < 4; ++j)
@@ -421,10 +446,31 @@ NTTS_D void gemm_epilogue_nat(const GemmArgs& p, f32x4 (&acc)[TM][TN], int mrow0
                     else for (int e = 0; e < 4; ++e) if (n4 + e < p.N) dst[e] = o[e];
                 }
             }
-        } else if constexpr (EPI == EPI_ARGMAX) {
+        } else if constexpr (epi_is_argmax(EPI)) {
             float best = -INFINITY;
             int bidx = 0x7fffffff;
             const int meos = (mok && p.mask_eos) ? p.mask_eos[m] : 0;   // eos id + 1, or 0
+            if constexpr (EPI == EPI_ARGMAX_PEN) {
+                // the wave's TN * 16 columns start at a multiple of 32 (nw0 = 32 * (9 nb + 3 wn) on the 256 x 288 tile): TN / 2 words of the row;
+                // column nw0 + j*16 + g*4 + r is bit (j & 1) * 16 + g*4 + r of word j >> 1
+                static_assert(TN % 2 == 0, "whole bitmap words per wave tile");
+                const float pen = mok ? p.rep_pen[m] : 1.0f;
+                unsigned int sw[TN / 2], any = 0;
+#pragma unroll
+                for (int q = 0; q < TN / 2; ++q) sw[q] = 0;
+                if (pen != 1.0f) {
+                    const unsigned int* sp = p.seen + (long)m * p.seen_pitch + (nw0 >> 5);
+#pragma unroll
+                    for (int q = 0; q < TN / 2; ++q) { sw[q] = sp[q]; any |= sw[q]; }
+                }
+                if (any) {
+#pragma unroll
+                    for (int j = 0; j < TN; ++j)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r)
+                            if ((sw[j >> 1] >> ((j & 1) * 16 + g * 4 + r)) & 1u) acc[a][j][r] = rep_penalised(rbf(acc[a][j][r]), pen);
+                }
+            }
 #pragma unroll
             for (int j = 0; j < TN; ++j) {
                 alignas(8) bf16_t lo[4];
@@ -458,7 +504,7 @@ NTTS_D void gemm_epilogue_nat(const GemmArgs& p, f32x4 (&acc)[TM][TN], int mrow0
                 p.part_idx[pi] = bidx;
             }
         } else {
-            static_assert(EPI == EPI_ARGMAX || EPI == EPI_BF16, "epilogues of the natural-order tile");
+            static_assert(epi_is_argmax(EPI) || EPI == EPI_BF16, "epilogues of the natural-order tile");
         }
     }
 }
@@ -495,7 +541,7 @@ NTTS_KERNEL(WM * WN * 64) void gemm_kernel(GemmArgs p) {
     static_assert(!F16 || (!F8 && TN == 4 && (EPI == EPI_BF16 || EPI == EPI_BF16_SILU || EPI == EPI_F32)), "fp16 operands: codec GEMMs");
     static_assert(BK == 64 || BK == 32, "ring slot K extent");
     static_assert(!F8 || BK == 64, "fp8: one ring slot = 128-byte rows");
-    static_assert(TN == 4 || ((EPI == EPI_ARGMAX || EPI == EPI_BF16) && !F8 && BK == 64), "natural-order tile: lm_head / prefill QKV, bf16");
+    static_assert(TN == 4 || ((epi_is_argmax(EPI) || EPI == EPI_BF16) && !F8 && BK == 64), "natural-order tile: lm_head / prefill QKV, bf16");
     constexpr int ESZ = F8 ? 1 : 2;            // bytes per operand element
     constexpr int CW = TN * 16;                // output columns per wave
     constexpr int BM = WM * TM * 16, BN = WN * CW, NW = WM * WN;
@@ -694,7 +740,7 @@ inline void gemm_launch(GemmArgs p, int ksplit, hipStream_t s) {
     if (ksplit > ktiles) ksplit = ktiles;
     p.k_tiles_per_split = (ktiles + ksplit - 1) / ksplit;
     const int nsplit = (ktiles + p.k_tiles_per_split - 1) / p.k_tiles_per_split;
-    if constexpr (EPI == EPI_ARGMAX) p.part_stride = p.nblocks * WN;
+    if constexpr (epi_is_argmax(EPI)) p.part_stride = p.nblocks * WN;
     if (EPI == EPI_SPLITK && p.xcd_maffine == -1 && (p.mblocks == 1 || p.mblocks == 2 || p.mblocks == 4 || p.mblocks == 8)) {   // row-block placement requested
         p.xcd_maffine = nsplit;
         p.xcd_xps = 8 / p.mblocks;
@@ -735,6 +781,33 @@ inline void gemm_launch(GemmArgs p, int ksplit, hipStream_t s) {
     else if (tl_ >= 240) ::ntts::gemm_launch<2, 2, 4, EPI, 2, 0, 64, false, false, 4, true>(p, 1, s); \
     else ::ntts::gemm_launch<4, 1, 1, EPI, 4, 0, 64, false, false, 4, true>(p, 1, s); } while (0)
 #define NTTS_GEMM_S(EPI, p, ks, s) ::ntts::gemm_launch<4, 1, 1, EPI, 4>(p, ks, s)
+
+// The decode lm_head (backbone.cpp k_lm_head; kapi.cpp ntts_k_head_penalty_probe runs the same launch on caller-supplied data).  head_tile: 0 = 64 x 64
+// skinny / 4-slot ring, 1 = 128 x 128, 2 = 256 x 256 (16 waves), 4 = natural-order 256 x 288 (12 waves, bf16 only); the 256-row tiles stream W with the
+// non-temporal policy (read once per step).  a.seen != null selects the kernels with the repetition penalty in their epilogue.
+template <int EPI>
+inline void lm_head_launch_epi(const GemmArgs& a, int head_tile, bool fp8, hipStream_t s) {
+    switch (head_tile) {
+        case 0:
+            if (fp8) gemm_launch<4, 1, 1, EPI, 4, 0, 64, false, true>(a, 1, s);
+            else gemm_launch<4, 1, 1, EPI, 4>(a, 1, s);
+            break;
+        case 4: gemm_launch<4, 3, 4, EPI, 2, 0, 64, true, false, 6>(a, 1, s); break;
+        case 2:
+            if (fp8) gemm_launch<4, 4, 4, EPI, 2, 0, 64, true, true>(a, 1, s);
+            else gemm_launch<4, 4, 4, EPI, 2, 0, 64, true>(a, 1, s);
+            break;
+        default:
+            if (fp8) gemm_launch<2, 2, 4, EPI, 2, 0, 64, false, true>(a, 1, s);
+            else gemm_launch<2, 2, 4, EPI, 2>(a, 1, s);
+    }
+}
+inline void lm_head_launch(const GemmArgs& a, int head_tile, bool fp8, hipStream_t s) {
+    if (a.seen) lm_head_launch_epi<EPI_ARGMAX_PEN>(a, head_tile, fp8, s);
+    else lm_head_launch_epi<EPI_ARGMAX>(a, head_tile, fp8, s);
+}
+// words per row of a seen bitmap for a head of N columns: every tile's padding columns (up to 287 past N) have their word, rows stay 16-byte aligned
+inline long seen_pitch_for(int N) { return ((long)N + 288 + 31) / 32 / 4 * 4 + 4; }
 
 // number of split-K slabs gemm_launch will produce for (K, ksplit); ktile = K extent of one 128-byte tile (64 bf16, 128 fp8)
 inline int gemm_nsplit(int K, int ksplit, int ktile = 64) {

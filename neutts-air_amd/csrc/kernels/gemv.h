@@ -62,6 +62,9 @@ struct GemvArgs {
     long ld_logits;
     bf16_t* logits_bf16;
     long ld_logits_bf16;
+    const unsigned int* seen;   // EPI_ARGMAX_PEN (gemm.h GemmArgs): [M][seen_pitch] seen-column bitmap and the per-row repetition penalty
+    long seen_pitch;
+    const float* rep_pen;
     // F8 kernels (fp8 model, gemm.h GemmArgs): X and W hold e4m3 BYTES (ldx / K count elements = bytes; a 128-byte k-tile is 128 k-values, K % 128 == 0),
     // the panel in LDS holds bytes (PRO: pro.out_fp8_inv quantises the normalised rows), out = acc * (xscale * wscale[n]); EPI_SILU_MUL emits e4m3
     // bytes when out_fp8_inv > 0 (down_proj's input).  Byte for byte the staging is the bf16 kernel's: a lane's 32 bytes per k-tile are 32 k-values
@@ -171,7 +174,7 @@ NTTS_KERNEL((FW + 4) * 64) void gemv_kernel(GemvArgs p) {
     const bf16_t* xrow = xs + l15 * kGemvXld + g * 16 - col0;
     // (not for the lm_head: 13.6 k workgroups stream 390 MB and what matters there is how fast a CU turns workgroups over -- with the
     //  ring, 182 instead of 142 VGPRs and the pinned order, it went 70 -> 90 us; profiles/r03g_sweep_b1_gemv_prologue.log)
-    constexpr int kXPf = EPI == EPI_ARGMAX ? 1 : KT < 4 ? KT : 4;
+    constexpr int kXPf = epi_is_argmax(EPI) ? 1 : KT < 4 ? KT : 4;
     bf16x8 xq[kXPf][2];
     auto xload = [&](int j, bf16x8 (&d)[2]) {
         const bf16_t* xp = xrow + (kt0 + (j < nk ? j : nk - 1)) * 64;
@@ -232,10 +235,20 @@ NTTS_KERNEL((FW + 4) * 64) void gemv_kernel(GemvArgs p) {
                 *(unsigned int*)((unsigned char*)p.out + (long)m * p.ldo + fb) = *(unsigned int*)&q2[0];
             } else *(u32x2*)((bf16_t*)p.out + (long)m * p.ldo + fb) = *(u32x2*)&o[0];
         }
-    } else if constexpr (EPI == EPI_ARGMAX) {
+    } else if constexpr (epi_is_argmax(EPI)) {
         float best = -INFINITY;
         int bidx = 0x7fffffff;
         const int meos = (mok && p.mask_eos) ? p.mask_eos[m] : 0;     // eos id + 1, or 0
+        if constexpr (EPI == EPI_ARGMAX_PEN) {                        // the wave's 16 features are one halfword of the row; this lane's 4 are bits g*4 .. g*4+3
+            const float pen = mok ? p.rep_pen[m] : 1.0f;
+            unsigned int sbits = 0;
+            if (pen != 1.0f) sbits = (((const unsigned short*)(p.seen + (long)m * p.seen_pitch))[f0 >> 4] >> (g * 4)) & 15u;
+            if (sbits) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    if ((sbits >> r) & 1u) acc[r] = rep_penalised(rbf(acc[r]), pen);
+            }
+        }
         alignas(8) bf16_t lo[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -259,7 +272,7 @@ NTTS_KERNEL((FW + 4) * 64) void gemv_kernel(GemvArgs p) {
             p.part_idx[pi] = bidx;
         }
     } else {
-        static_assert(EPI == EPI_SPLITK || EPI == EPI_SILU_MUL || EPI == EPI_ARGMAX, "epilogues of the small-batch kernel");
+        static_assert(EPI == EPI_SPLITK || EPI == EPI_SILU_MUL || epi_is_argmax(EPI), "epilogues of the small-batch kernel");
     }
     if (p.tl) { wait_vmem(); if (w == 0) mark(5); }
 }
@@ -280,7 +293,7 @@ inline void gemv_launch(GemvArgs p, int ksplit, hipStream_t s) {
     ksplit = gemv_ksplit(p.K / (F8 ? 2 : 1), ksplit);             // (PRO: the panel is the whole normalised row, K = H <= 1024; fp8: 128 k-values per k-tile)
     p.k_tiles_per_split = (ktiles + ksplit - 1) / ksplit;
     const int nsplit = (ktiles + p.k_tiles_per_split - 1) / p.k_tiles_per_split;
-    if constexpr (EPI == EPI_ARGMAX) p.part_stride = p.N / 16;
+    if constexpr (epi_is_argmax(EPI)) p.part_stride = p.N / 16;
     const int kps = p.k_tiles_per_split;
     const dim3 grid((p.N + 16 * FW - 1) / (16 * FW), nsplit), block((FW + 4) * 64);
     if constexpr (EPI == EPI_SPLITK) {                            // the split-K GEMVs come in every slice length
@@ -294,6 +307,12 @@ inline void gemv_launch(GemvArgs p, int ksplit, hipStream_t s) {
         if (kps <= 8) { NTTS_LAUNCH((gemv_kernel<EPI, PRO, 8, FW, F8>), grid, block, s, p); return; }
     }
     NTTS_LAUNCH((gemv_kernel<EPI, PRO, 16, FW, F8>), grid, block, s, p);
+}
+
+// the small-batch lm_head (backbone.cpp ks_lm_head, kapi.cpp ntts_k_head_penalty_probe); a.seen != null: the kernels with the repetition penalty
+inline void lm_head_gemv_launch(const GemvArgs& a, bool fp8, hipStream_t s) {
+    if (a.seen) { if (fp8) gemv_launch<EPI_ARGMAX_PEN, false, 4, true>(a, 1, s); else gemv_launch<EPI_ARGMAX_PEN, false>(a, 1, s); }
+    else { if (fp8) gemv_launch<EPI_ARGMAX, false, 4, true>(a, 1, s); else gemv_launch<EPI_ARGMAX, false>(a, 1, s); }
 }
 
 // number of split-K slabs gemv_launch produces for (K, ksplit)

@@ -10,6 +10,10 @@
 //                  (the reference's own call: do_sample=True, temperature=1.0, top_k=50, ref:neutts/neutts.py:338-347; top_p /
 //                  min_p are generate()'s own keyword arguments, off -- 1.0 / 0.0 -- in that call)
 //   -> append -> EosTokenCriteria / MaxLengthCriteria.
+// RepetitionPenaltyLogitsProcessor (repetition_penalty != 1; first in hf:generation/utils.py _get_logits_processor, ahead of MinNewTokensLength and the
+// warpers) also lives in the lm_head epilogue (gemm.h EPI_ARGMAX_PEN): it reads a per-slot bitmap of the lm_head columns the request has seen.  This file
+// keeps that bitmap: the prompt pass clears a slot's row and marks its prompt's ids, the sampling kernel marks every token it appends (so step t + 1's
+// lm_head sees the token of step t), ntts_backbone_activate moves the row with the rest of the slot.
 // Sampling reads the row of bf16 logits the lm_head epilogue leaves behind (HF's logits ARE bf16 values cast to fp32, so a
 // 16-bit radix select finds the exact k-th largest), draws its uniform from Philox4x32-10 keyed by the request's seed with
 // the step index as counter: reproducible for a given seed whatever slot / batch the request runs in (callers give each
@@ -35,6 +39,7 @@ struct SlotArrays {      // device arrays, one entry per decode slot
     float* temperature;  // > 0
     float* top_p;        // (0, 1]; 1 = no nucleus cut
     float* min_p;        // [0, 1]; 0 = no min-p cut
+    float* rep_pen;      // repetition penalty, finite and > 0; exactly 1 = off (every row holds 1 until a penalised request fills it)
     unsigned int* seed;  // [slots][2] Philox key
     int* out_tokens;     // [slots][out_stride]
     int out_stride;
@@ -53,7 +58,13 @@ struct SampleArgs {
     // compacted head (ntts_backbone_set_logits_range): column c of the lm_head is token id_base + c for c < n_range and the EOS id for
     // c == n_range; n_range = 0: column = token id
     int n_range, id_base, id_tail;
+    unsigned int* seen;      // [slots][seen_pitch] seen-column bitmap (gemm.h GemmArgs::seen); null while no penalised request is live
+    long seen_pitch;
 };
+
+// one bit of a seen bitmap, from any number of workgroups at once (duplicates are the norm).  Spelled with the compiler's builtin so that the same
+// line is a global_atomic_or on the device and a host atomic on the CPU emulator
+NTTS_D void seen_mark(unsigned int* row, int col) { __atomic_fetch_or(row + (col >> 5), 1u << (col & 31), __ATOMIC_RELAXED); }
 
 constexpr int kSampleCap = 512;   // candidates kept (k plus ties at the k-th value, capped)
 
@@ -374,6 +385,8 @@ NTTS_KERNEL(256) void sample_greedy_kernel(SampleArgs p) {
         SlotArrays& s = p.sl;
         if (live) {
             int tok = k > 0 ? sampled : bidx;
+            // (a COLUMN: before the compacted head's id mapping; a row without one finite logit yields no index -- nothing to mark)
+            if (p.seen && s.rep_pen[b] != 1.0f && (unsigned int)tok < (unsigned int)p.vocab) seen_mark(p.seen + (long)b * p.seen_pitch, tok);
             if (p.n_range > 0) tok = tok < p.n_range ? tok + p.id_base : p.id_tail;
             const int n = (p.phase == SLOT_PREFILLED) ? 0 : s.n_new[b];
             s.out_tokens[(long)b * s.out_stride + n] = tok;
@@ -398,17 +411,24 @@ struct PrefillInit {
     const int* temp_bits;  // float bits
     const int* top_p_bits; // float bits
     const int* min_p_bits; // float bits
+    const int* pen_bits;   // float bits: the repetition penalty, 1 = off
     const int* seed;       // [n][2]
     const int* bt_rows;    // [n][max_pages]
     int* block_table;      // [slots][max_pages]
     int max_pages;
     int n;
     SlotArrays sl;
+    unsigned int* seen;    // seen bitmap (null: none allocated yet): the rows of the slots being filled are cleared here
+    long seen_pitch;
 };
 NTTS_KERNEL(64) void prefill_init_kernel(PrefillInit p) {
     const int i = blockIdx.x;
     const int s = p.slot[i];
     for (int k = threadIdx.x; k < p.max_pages; k += 64) p.block_table[(long)s * p.max_pages + k] = p.bt_rows[(long)i * p.max_pages + k];
+    if (p.seen) {
+        u32x4* row = (u32x4*)(p.seen + (long)s * p.seen_pitch);      // (the pitch is a multiple of 4 words)
+        for (long k = threadIdx.x; k < p.seen_pitch / 4; k += 64) row[k] = u32x4{0u, 0u, 0u, 0u};
+    }
     if (threadIdx.x == 0) {
         p.sl.state[s] = SLOT_PREFILLED;
         p.sl.pos[s] = p.seq_len[i];
@@ -421,11 +441,27 @@ NTTS_KERNEL(64) void prefill_init_kernel(PrefillInit p) {
         p.sl.temperature[s] = __builtin_bit_cast(float, p.temp_bits[i]);
         p.sl.top_p[s] = __builtin_bit_cast(float, p.top_p_bits[i]);
         p.sl.min_p[s] = __builtin_bit_cast(float, p.min_p_bits[i]);
+        p.sl.rep_pen[s] = __builtin_bit_cast(float, p.pen_bits[i]);
         p.sl.seed[2 * s] = (unsigned int)p.seed[2 * i];
         p.sl.seed[2 * s + 1] = (unsigned int)p.seed[2 * i + 1];
         p.sl.mask_eos[s] = p.min_new[i] > 0 ? p.eos[i] + 1 : 0;
         p.sl.cur_tok[s] = 0;
     }
+}
+// The prompt's share of a penalised request's bitmap (launched behind prefill_init_kernel, which cleared the rows): cols = the lm_head columns of the
+// ids at positions >= prompt_ignore_length of the FULL prompts of the call's penalised requests, back to back; request i owns cols[off[i] .. off[i + 1])
+// (empty for an unpenalised one).  The host has already mapped ids to columns and dropped those a restricted head does not have.
+struct SeenMarkArgs {
+    const int* slot;       // [n]
+    const int* off;        // [n + 1]
+    const int* cols;
+    unsigned int* seen;
+    long seen_pitch;
+};
+NTTS_KERNEL(256) void seen_mark_prompt_kernel(SeenMarkArgs p) {
+    const int i = blockIdx.x;
+    unsigned int* row = p.seen + (long)p.slot[i] * p.seen_pitch;
+    for (int t = p.off[i] + (int)threadIdx.x; t < p.off[i + 1]; t += 256) seen_mark(row, p.cols[t]);
 }
 NTTS_KERNEL(64) void zero_slots_kernel(const int* slots, int n, int* state) {   // ntts_backbone_release_many: state[slots[i]] = FREE
     const int i = blockIdx.x * 64 + threadIdx.x;
@@ -494,6 +530,8 @@ struct ActivateArgs {
     SlotArrays sl;
     int* block_table;        // [slots][max_pages]
     int max_pages;
+    unsigned int* seen;      // seen bitmap (null: none allocated): the row moves with the request
+    long seen_pitch;
 };
 NTTS_KERNEL(64) void activate_slots_kernel(ActivateArgs p) {
     const int src = p.pairs[2 * blockIdx.x], dst = p.pairs[2 * blockIdx.x + 1];
@@ -501,11 +539,13 @@ NTTS_KERNEL(64) void activate_slots_kernel(ActivateArgs p) {
     const int nn = p.sl.n_new[src];
     for (int k = lane; k < nn; k += 64) p.sl.out_tokens[(long)dst * p.sl.out_stride + k] = p.sl.out_tokens[(long)src * p.sl.out_stride + k];
     for (int k = lane; k < p.max_pages; k += 64) p.block_table[(long)dst * p.max_pages + k] = p.block_table[(long)src * p.max_pages + k];
+    if (p.seen)              // (an unpenalised request's row is all zeros: it replaces whatever the decode slot's last occupant left)
+        for (long k = lane; k < p.seen_pitch; k += 64) p.seen[(long)dst * p.seen_pitch + k] = p.seen[(long)src * p.seen_pitch + k];
     if (lane == 0) {
         p.sl.pos[dst] = p.sl.pos[src]; p.sl.n_new[dst] = nn; p.sl.cur_tok[dst] = p.sl.cur_tok[src]; p.sl.prompt_len[dst] = p.sl.prompt_len[src];
         p.sl.min_new[dst] = p.sl.min_new[src]; p.sl.max_len[dst] = p.sl.max_len[src]; p.sl.eos[dst] = p.sl.eos[src]; p.sl.mask_eos[dst] = p.sl.mask_eos[src];
         p.sl.top_k[dst] = p.sl.top_k[src]; p.sl.temperature[dst] = p.sl.temperature[src];
-        p.sl.top_p[dst] = p.sl.top_p[src]; p.sl.min_p[dst] = p.sl.min_p[src];
+        p.sl.top_p[dst] = p.sl.top_p[src]; p.sl.min_p[dst] = p.sl.min_p[src]; p.sl.rep_pen[dst] = p.sl.rep_pen[src];
         p.sl.seed[2 * dst] = p.sl.seed[2 * src]; p.sl.seed[2 * dst + 1] = p.sl.seed[2 * src + 1];
         p.sl.state[dst] = p.sl.state[src];
         p.sl.state[src] = SLOT_FREE;

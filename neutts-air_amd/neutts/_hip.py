@@ -18,7 +18,7 @@ DEFAULT_LIB = os.path.join(os.path.dirname(_HERE), "libneutts_hip.so")
 
 NTTS_DT_F32, NTTS_DT_BF16, NTTS_DT_I32, NTTS_DT_FP8_E4M3 = 0, 1, 2, 3
 NTTS_W_BF16, NTTS_W_FP8_E4M3 = 0, 1
-ABI_VERSION = 10
+ABI_VERSION = 11
 NTTS_PAGE_TOKENS = 32            # include/neutts_hip.h
 PAGE_TOKENS = 32
 ERRORS = {-1: "EINVAL", -2: "ENODEV", -3: "ENOMEM", -4: "ESTATE", -5: "EHIP"}
@@ -61,7 +61,7 @@ class StreamParamsC(C.Structure):
 class SamplingC(C.Structure):
     _fields_ = [("max_length", C.c_int32), ("min_new_tokens", C.c_int32), ("eos_token_id", C.c_int32),
                 ("do_sample", C.c_int32), ("top_k", C.c_int32), ("temperature", C.c_float), ("seed", C.c_uint64),
-                ("top_p", C.c_float), ("min_p", C.c_float)]
+                ("top_p", C.c_float), ("min_p", C.c_float), ("repetition_penalty", C.c_float), ("prompt_ignore_length", C.c_int32)]
 
 
 _LIBS: Dict[str, C.CDLL] = {}
@@ -140,6 +140,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "ntts_backbone_sync": (C.c_int, [p]),
         "ntts_backbone_set_debug": (C.c_int, [p, i32]),
         "ntts_backbone_read_logits": (C.c_int, [p, i32, C.POINTER(f32), i32]),
+        "ntts_backbone_read_seen": (C.c_int, [p, i32, C.POINTER(C.c_uint32), i32]),
         "ntts_backbone_debug_force": (C.c_int, [p, i32, i32]),
         "ntts_backbone_last_timing": (C.c_int, [p, C.POINTER(f32), C.POINTER(f32)]),
         "ntts_backbone_step_bytes": (C.c_int, [p, C.POINTER(C.c_double)]),
@@ -175,6 +176,9 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "ntts_k_launch_chain_probe": (C.c_int, [i32, i32, i32, i32, C.POINTER(C.c_double)]),
         "ntts_k_sample_probe": (C.c_int, [p, i64, i32, i32, i32, C.POINTER(i32), C.POINTER(f32), C.POINTER(f32), C.POINTER(f32),
                                           C.POINTER(C.c_uint64), i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
+        "ntts_k_head_penalty_probe": (C.c_int, [p, p, i32, i32, i32, i32, i32, f32, C.POINTER(C.c_uint32), C.POINTER(f32), C.POINTER(i32),
+                                                C.POINTER(f32), C.POINTER(C.c_uint16), C.POINTER(f32), C.POINTER(i32), i32, C.POINTER(i32),
+                                                C.POINTER(i32)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError here == header/library drift: fail loudly
@@ -206,7 +210,9 @@ def _tensor_ptr(t):
 @dataclass
 class Sampling:
     """Keyword arguments of the reference's generate() call (ref:neutts/neutts.py:338-347), plus generate()'s own top_p / min_p (off -- 1.0 / 0.0 --
-    in that call): TopPLogitsWarper / MinPLogitsWarper behind top-k, in transformers' order (include/neutts_hip.h: ntts_sampling)."""
+    in that call): TopPLogitsWarper / MinPLogitsWarper behind top-k, in transformers' order (include/neutts_hip.h: ntts_sampling).
+    repetition_penalty / prompt_ignore_length (ABI 11): generate()'s `repetition_penalty` (1.0 = off, the reference's value) and
+    RepetitionPenaltyLogitsProcessor's `prompt_ignore_length`; the penalty applies to greedy and sampled requests alike."""
     max_length: int = 2048
     min_new_tokens: int = 50
     eos_token_id: int = 0
@@ -216,10 +222,12 @@ class Sampling:
     seed: int = 0
     top_p: float = 1.0
     min_p: float = 0.0
+    repetition_penalty: float = 1.0
+    prompt_ignore_length: int = 0
 
     def to_c(self) -> SamplingC:
         return SamplingC(self.max_length, self.min_new_tokens, self.eos_token_id, int(self.do_sample), self.top_k,
-                         self.temperature, self.seed, self.top_p, self.min_p)
+                         self.temperature, self.seed, self.top_p, self.min_p, self.repetition_penalty, self.prompt_ignore_length)
 
 
 SAMPLE_CAP = 512                 # candidates the device sampler keeps (csrc/kernels/sample.h kSampleCap)
@@ -243,6 +251,42 @@ def sample_probe(lib, logits_ptr: int, ld_logits: int, rows: int, vocab: int, gr
     if rc != 0:
         raise NeuTTSHipError(rc, "ntts_k_sample_probe")
     return tok, [ids[r, : n[r]].copy() for r in range(rows)]
+
+
+HEAD_VARIANTS = {"64x64": 0, "128x128": 1, "256x256": 2, "256x288": 4, "gemv": 8}     # ntts_k_head_penalty_probe `variant`
+
+
+def head_penalty_probe(lib, x_ptr: int, w_ptr: int, M: int, N: int, K: int, variant: int, seen=None, rep_pen=None, mask_eos=None,
+                       fp8: bool = False, xscale: float = 1.0):
+    """ntts_k_head_penalty_probe: the engine's lm_head launch of tile `variant` (HEAD_VARIANTS) on DEVICE bf16 X [M][K] and W [N][K] (row-major; the
+    probe packs W as the engine packs the head).  seen: None (the plain lm_head) or a bool / 0-1 array [M][N] of seen columns; rep_pen: [M]
+    penalties; mask_eos: [M] column + 1 to mask, 0 = none.  Returns (logits fp32 [M][N], bf16 row bit patterns uint16 [M][N],
+    partial maxima [M][n_part], their indices, columns per partial)."""
+    words = None
+    pen = None
+    if seen is not None:
+        bits = np.zeros((M, (N + 31) // 32 * 32), dtype=np.uint8)
+        bits[:, :N] = np.asarray(seen, dtype=bool).reshape(M, N)
+        words = np.ascontiguousarray(np.packbits(bits, axis=1, bitorder="little").view("<u4"))
+        pen = np.ascontiguousarray(np.broadcast_to(np.asarray(rep_pen, dtype=np.float32), (M,)))
+    me = None if mask_eos is None else np.ascontiguousarray(np.broadcast_to(np.asarray(mask_eos, dtype=np.int32), (M,)))
+    cap = N // 16 + 16
+    logits = np.zeros((M, N), dtype=np.float32)
+    row16 = np.zeros((M, N), dtype=np.uint16)
+    pv = np.zeros((M, cap), dtype=np.float32)
+    pi = np.zeros((M, cap), dtype=np.int32)
+    n_part, width = C.c_int32(), C.c_int32()
+    i32p, f32p = C.POINTER(C.c_int32), C.POINTER(C.c_float)
+    rc = lib.ntts_k_head_penalty_probe(C.c_void_p(x_ptr), C.c_void_p(w_ptr), M, N, K, variant, int(fp8), xscale,
+                                       None if words is None else words.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                       None if pen is None else pen.ctypes.data_as(f32p), None if me is None else me.ctypes.data_as(i32p),
+                                       logits.ctypes.data_as(f32p), row16.ctypes.data_as(C.POINTER(C.c_uint16)), pv.ctypes.data_as(f32p),
+                                       pi.ctypes.data_as(i32p), cap, C.byref(n_part), C.byref(width))
+    if rc != 0:
+        raise NeuTTSHipError(rc, "ntts_k_head_penalty_probe")
+    n = n_part.value
+    # (the library wrote rows of n_part entries back to back)
+    return logits, row16, pv.reshape(-1)[: M * n].reshape(M, n).copy(), pi.reshape(-1)[: M * n].reshape(M, n).copy(), width.value
 
 
 class BackboneEngine:
@@ -595,6 +639,13 @@ class BackboneEngine:
         out = np.empty(self.vocab_size, dtype=np.float32)
         self._chk(self.lib.ntts_backbone_read_logits(self.h, slot, out.ctypes.data_as(C.POINTER(C.c_float)), len(out)))
         return out
+
+    def read_seen(self, slot: int) -> np.ndarray:
+        """The lm_head columns slot `slot`'s repetition penalty counts as seen (ntts_backbone_read_seen), as a sorted array of column indices:
+        token ids, or with set_logits_range positions in [lo, hi) followed by the EOS column.  NTTS_ESTATE before the first penalised request."""
+        words = np.zeros((self.vocab_size + 31) // 32, dtype=np.uint32)
+        self._chk(self.lib.ntts_backbone_read_seen(self.h, slot, words.ctypes.data_as(C.POINTER(C.c_uint32)), len(words)))
+        return np.flatnonzero(np.unpackbits(words.view(np.uint8), bitorder="little")[: self.vocab_size])
 
     def debug_force(self, slot: int, token: int):
         self._chk(self.lib.ntts_backbone_debug_force(self.h, slot, token))

@@ -166,6 +166,16 @@ def _check_sampling(top_k, temperature, top_p, min_p, who: str = "") -> None:
         raise ValueError(f"{who}min_p must lie in [0, 1] (got {min_p!r})")
 
 
+def _check_repetition(repetition_penalty, repetition_ignore_prompt, who: str = "") -> None:
+    """RepetitionPenaltyLogitsProcessor's range (a strictly positive, finite float; 1.0 = off) and a plain bool; ValueError before anything
+    reaches the engine."""
+    v = repetition_penalty
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not v > 0 or v == float("inf"):
+        raise ValueError(f"{who}repetition_penalty must be a finite number > 0 (got {v!r})")
+    if not isinstance(repetition_ignore_prompt, (bool, np.bool_)):
+        raise ValueError(f"{who}repetition_ignore_prompt must be True or False (got {repetition_ignore_prompt!r})")
+
+
 class NeuTTS:
 
     def __init__(
@@ -184,6 +194,8 @@ class NeuTTS:
         temperature: float = 1.0,
         top_p: float = 1.0,
         min_p: float = 0.0,
+        repetition_penalty: float = 1.0,
+        repetition_ignore_prompt: bool = False,
         speech_range_head: bool = False,
         codec_precision: str = "fp16",
     ):
@@ -205,7 +217,14 @@ class NeuTTS:
         # sampling contract of the reference call (ref:neutts/neutts.py:338-347: top_k 50, temperature 1.0 -- the defaults); do_sample=False = greedy.
         # top_p / min_p are generate()'s own keyword arguments of those names (TopPLogitsWarper / MinPLogitsWarper behind top-k), off in that
         # call.  Every entry point takes per-call overrides of the four.
+        # repetition_penalty is generate()'s keyword argument of that name (RepetitionPenaltyLogitsProcessor, ahead of every warper; 1.0 = off, the
+        # reference's value): codec-token decoders loop, and a penalty on tokens already seen is the standard remedy.  repetition_ignore_prompt = True
+        # counts generated tokens only (the processor's prompt_ignore_length = the utterance's own prompt length): a cloning prompt is mostly
+        # reference codec tokens.  Both have per-call overrides too.
         _check_sampling(top_k, temperature, top_p, min_p)
+        _check_repetition(repetition_penalty, repetition_ignore_prompt)
+        self.repetition_penalty = repetition_penalty
+        self.repetition_ignore_prompt = repetition_ignore_prompt
         self.do_sample = do_sample
         self.top_k = top_k
         self.temperature = temperature
@@ -372,19 +391,20 @@ class NeuTTS:
         self.codec = _CodecFacade(engine, enc_engine)
 
     # ------------------------------------------------------------------------------------------ public API
-    def infer(self, text: str, ref_codes, ref_text: str, *, temperature=None, top_k=None, top_p=None, min_p=None) -> np.ndarray:
+    def infer(self, text: str, ref_codes, ref_text: str, *, temperature=None, top_k=None, top_p=None, min_p=None, **repetition) -> np.ndarray:
         """Generate speech for `text` in the voice of the encoded reference (ref:neutts/neutts.py:216-243).  temperature / top_k / top_p /
-        min_p override the instance's sampling attributes for this call (None = the attribute)."""
-        samp = self._resolve_sampling(1, temperature, top_k, top_p, min_p)
+        min_p override the instance's sampling attributes for this call (None = the attribute), and so do the two further keywords every entry
+        point takes behind them: repetition_penalty= and repetition_ignore_prompt= (anything else is a TypeError)."""
+        samp = self._resolve_sampling(1, temperature, top_k, top_p, min_p, repetition)
         prompt_ids = self._apply_chat_template(ref_codes, ref_text, text)
         new_ids = self._generate([prompt_ids], samp)[0]
         wav = self._decode_ids(new_ids)
         return wav if self.watermarker is None else self.watermarker.apply_watermark(wav, sample_rate=24_000)
 
-    def infer_batch(self, texts: Sequence[str], ref_codes, ref_texts, *, temperature=None, top_k=None, top_p=None, min_p=None) -> List[np.ndarray]:
+    def infer_batch(self, texts: Sequence[str], ref_codes, ref_texts, *, temperature=None, top_k=None, top_p=None, min_p=None, **repetition) -> List[np.ndarray]:
         """Many utterances at once: continuous batching over the engine's decode slots (over every engine's, with engines > 1),
         one codec pass.  The sampling overrides take one value for the call or one per utterance."""
-        samp = self._resolve_sampling(len(texts), temperature, top_k, top_p, min_p)
+        samp = self._resolve_sampling(len(texts), temperature, top_k, top_p, min_p, repetition)
         if not isinstance(ref_texts, (list, tuple)):
             ref_texts = [ref_texts] * len(texts)
             ref_codes = [ref_codes] * len(texts)
@@ -397,23 +417,23 @@ class NeuTTS:
             wavs = [self.watermarker.apply_watermark(w, sample_rate=24_000) for w in wavs]
         return wavs
 
-    def infer_stream(self, text: str, ref_codes, ref_text: str, *, temperature=None, top_k=None, top_p=None, min_p=None) -> Generator[np.ndarray, None, None]:
+    def infer_stream(self, text: str, ref_codes, ref_text: str, *, temperature=None, top_k=None, top_p=None, min_p=None, **repetition) -> Generator[np.ndarray, None, None]:
         """Streaming synthesis with the reference's window / cross-fade semantics (ref:neutts/neutts.py:373-465).  Sampling overrides as `infer`
         (checked here, before the generator is handed out)."""
-        samp = self._resolve_sampling(1, temperature, top_k, top_p, min_p)
+        samp = self._resolve_sampling(1, temperature, top_k, top_p, min_p, repetition)
         prompt_ids = self._apply_chat_template(ref_codes, ref_text, text)
         ref = [int(c) for c in _to_list(ref_codes)]
         if self._stream_on_device([ref]):       # token cache, windows, codec pass and cross-fade on the device (csrc/stream.cpp): a set of one stream
             return (chunk for _, chunk in self._infer_stream_batch_hip([prompt_ids], [ref], samp))
         return self._infer_stream_hip(prompt_ids, ref, samp)        # host loop: a watermarker (a host library) sits between the codec and the slice
 
-    def infer_stream_batch(self, texts: Sequence[str], ref_codes, ref_texts, *, temperature=None, top_k=None, top_p=None, min_p=None) -> Generator[tuple, None, None]:
+    def infer_stream_batch(self, texts: Sequence[str], ref_codes, ref_texts, *, temperature=None, top_k=None, top_p=None, min_p=None, **repetition) -> Generator[tuple, None, None]:
         """Many utterances streamed at once (BASELINE config 5's shape: a decode batch with the codec on its own stream):
         yields `(utterance index, chunk)` pairs; the chunks of one utterance, in order, are exactly what `infer_stream`
         yields for it.  One decode burst serves every running utterance, and all windows that became decodable in a burst
         go through the codec in ONE batched call, enqueued behind the next burst (the two engines' streams overlap).
         At most `max_batch` utterances (the engine's decode slots) per call.  Sampling overrides as `infer_batch`."""
-        samp = self._resolve_sampling(len(texts), temperature, top_k, top_p, min_p)
+        samp = self._resolve_sampling(len(texts), temperature, top_k, top_p, min_p, repetition)
         if not isinstance(ref_texts, (list, tuple)):
             ref_texts = [ref_texts] * len(texts)
             ref_codes = [ref_codes] * len(texts)
@@ -434,11 +454,17 @@ class NeuTTS:
         return ref_codes
 
     # ------------------------------------------------------------------------------------------ id-level hot path
-    def _resolve_sampling(self, n: int, temperature=None, top_k=None, top_p=None, min_p=None) -> List[tuple]:
-        """Per-call sampling overrides -> one checked (top_k, temperature, top_p, min_p) per utterance.  None = the instance attribute; a list /
-        tuple / array gives one value per utterance (the batch entry points).  ValueError on a bad value, before the engine is touched."""
+    def _resolve_sampling(self, n: int, temperature=None, top_k=None, top_p=None, min_p=None, repetition: Optional[dict] = None) -> List[tuple]:
+        """Per-call sampling overrides -> one checked (top_k, temperature, top_p, min_p, repetition_penalty, repetition_ignore_prompt) per
+        utterance.  None = the instance attribute; a list / tuple / array gives one value per utterance (the batch entry points).  `repetition`:
+        the entry point's remaining keywords, repetition_penalty / repetition_ignore_prompt.  ValueError on a bad value, before the engine is touched."""
+        repetition = dict(repetition or {})
+        rp, rip = repetition.pop("repetition_penalty", None), repetition.pop("repetition_ignore_prompt", None)
+        if repetition:
+            raise TypeError(f"unexpected keyword argument {sorted(repetition)[0]!r}")
         cols = []
-        for name, v in (("top_k", top_k), ("temperature", temperature), ("top_p", top_p), ("min_p", min_p)):
+        for name, v in (("top_k", top_k), ("temperature", temperature), ("top_p", top_p), ("min_p", min_p), ("repetition_penalty", rp),
+                        ("repetition_ignore_prompt", rip)):
             if v is None:
                 v = getattr(self, name)
             if isinstance(v, (list, tuple, np.ndarray)):
@@ -450,23 +476,26 @@ class NeuTTS:
                 v = [v] * n
             cols.append(v)
         out = list(zip(*cols)) if n else []
-        for i, (k, t, tp, mp) in enumerate(out):
+        for i, (k, t, tp, mp, pen, ign) in enumerate(out):
             _check_sampling(k, t, tp, mp, f"utterance {i}: " if n > 1 else "")
-        return [(int(k), float(t), float(tp), float(mp)) for k, t, tp, mp in out]
+            _check_repetition(pen, ign, f"utterance {i}: " if n > 1 else "")
+        return [(int(k), float(t), float(tp), float(mp), float(pen), bool(ign)) for k, t, tp, mp, pen, ign in out]
 
     def _sampling(self, prompt_len: int, index: int = 0, samp: Optional[Sequence[tuple]] = None) -> _hip.Sampling:
         if self._eos_id is None:
             raise RuntimeError("eos token id unknown: supply 'eos_token_id' with in-memory weights")
         # one Philox key per request: (call counter, index within the call)
         seed = (self._seed * 0x9E3779B97F4A7C15 + index * 0xD1B54A32D192ED03 + 1) & 0xFFFFFFFFFFFFFFFF
-        top_k, temperature, top_p, min_p = samp[index] if samp is not None else (self.top_k, self.temperature, self.top_p, self.min_p)
+        top_k, temperature, top_p, min_p, pen, ign = samp[index] if samp is not None else (
+            self.top_k, self.temperature, self.top_p, self.min_p, self.repetition_penalty, self.repetition_ignore_prompt)
         return _hip.Sampling(max_length=self.max_context, min_new_tokens=self.min_new_tokens, eos_token_id=self._eos_id,
-                             do_sample=self.do_sample, top_k=top_k, temperature=temperature, seed=seed, top_p=top_p, min_p=min_p)
+                             do_sample=self.do_sample, top_k=top_k, temperature=temperature, seed=seed, top_p=top_p, min_p=min_p,
+                             repetition_penalty=pen, prompt_ignore_length=prompt_len if ign else 0)
 
-    def generate_codes(self, prompts: Sequence[Sequence[int]], *, temperature=None, top_k=None, top_p=None, min_p=None) -> List[List[int]]:
+    def generate_codes(self, prompts: Sequence[Sequence[int]], *, temperature=None, top_k=None, top_p=None, min_p=None, **repetition) -> List[List[int]]:
         """Batched equivalent of `_infer_torch` (ref:neutts/neutts.py:334-352): new token ids per prompt.  The sampling overrides take one
         value for the call or one per prompt."""
-        return self._generate(prompts, self._resolve_sampling(len(prompts), temperature, top_k, top_p, min_p))
+        return self._generate(prompts, self._resolve_sampling(len(prompts), temperature, top_k, top_p, min_p, repetition))
 
     def _generate(self, prompts: Sequence[Sequence[int]], samp: Sequence[tuple]) -> List[List[int]]:
         self._seed += 1
