@@ -313,6 +313,28 @@ int ntts_backbone_read_logits(ntts_backbone* e, int32_t slot, float* out, int32_
  * are not recorded).  n_words 32-bit words are written (zeros past the row's end).  Rows of requests whose penalty is 1 are cleared by the prompt pass
  * and then left alone.  NTTS_ESTATE while no bitmap exists: it is allocated with the first request whose penalty is not 1. */
 int ntts_backbone_read_seen(ntts_backbone* e, int32_t slot, uint32_t* words_out, int32_t n_words);
+/* Per-token log-probabilities.  NEW SYMBOLS ONLY: NTTS_ABI_VERSION stays 11 and ntts_sampling keeps its layout -- a caller that never names these
+ * functions sees the library it saw before.
+ * DEFINITION.  For a request's i-th new token t_i, chosen from the processed logits row r_i -- the bf16-valued row the lm_head produces, after the
+ * repetition penalty and the MinNewTokens EOS mask: exactly what ntts_backbone_read_logits taps and what HF hands its warpers --
+ *     logprob_i = r_i[t_i] - logsumexp(r_i)      over the whole lm_head row: all V columns, -inf columns contributing 0.
+ * Temperature, top_k, top_p and min_p do NOT enter.  For a greedy request this is transformers' compute_transition_scores(sequences, scores,
+ * normalize_logits=True); for a sampled one it is the model's own probability of the drawn token (the convention of serving stacks' `logprobs`), not
+ * the renormalised mass among the warpers' survivors.  With ntts_backbone_set_logits_range the row is the COMPACTED row (the range's columns + EOS): the
+ * tokens outside the range are not part of the sum.  The first token (chosen behind the prompt pass) and the EOS token both get a value: a request
+ * always has exactly n_new log-probabilities.  A sequence's score is their arithmetic mean.
+ * The log-sum-exp is reduced inside the lm_head epilogue (the [B][V] logits are never materialised) and carried to the sampling kernel beside the
+ * argmax partials; fp32 throughout, within 1e-4 absolute of the float64 value on the tapped row.
+ * ntts_backbone_set_logprobs: the engine-level switch (per engine: every twin of a gang has its own).  NTTS_ESTATE while any slot or parking row is in
+ * use, like ntts_backbone_set_logits_range.  The first enable allocates the record ([slots][max_context] fp32) and the third partial array; switching
+ * drops the captured step graphs.  While on, every request records.  While off (the default) nothing is allocated and the step launches exactly the
+ * kernels it launched before. */
+int ntts_backbone_set_logprobs(ntts_backbone* e, int32_t enable);
+/* Blocking read of slot `slot`'s log-probabilities, ordered like ntts_backbone_read: *n_out = n_new, min(cap, n_new) values are written, entry i
+ * belongs to the i-th id ntts_backbone_read returns.  NTTS_ESTATE while the switch is off. */
+int ntts_backbone_read_logprobs(ntts_backbone* e, int32_t slot, float* out, int32_t cap, int32_t* n_out);
+/* The same for a slot the last completed snapshot showed FINISHED, on the side copy stream, under the rule of ntts_backbone_read_finished. */
+int ntts_backbone_read_finished_logprobs(ntts_backbone* e, int32_t slot, float* out, int32_t cap, int32_t* n_out);
 /* Teacher forcing for the margin-aware parity tests: replace the token slot `slot` emitted last
  * (and will feed to the next step) by `token`. */
 int ntts_backbone_debug_force(ntts_backbone* e, int32_t slot, int32_t token);
@@ -572,6 +594,14 @@ int ntts_k_sample_probe(const void* logits_dev, int64_t ld_logits, int32_t rows,
 int ntts_k_head_penalty_probe(const void* X_dev, const void* W_dev, int32_t M, int32_t N, int32_t K, int32_t variant, int32_t fp8, float xscale,
                               const uint32_t* seen, const float* rep_pen, const int32_t* mask_eos, float* logits_out, uint16_t* logits_bf16_out,
                               float* part_val, int32_t* part_idx, int32_t part_cap, int32_t* n_part, int32_t* part_width);
+/* ntts_k_head_penalty_probe with the log-sum-exp epilogue (the kernels the decode step launches while ntts_backbone_set_logprobs is on): same inputs,
+ * same outputs, plus part_sum [M][*n_part] = the sum over partial i's columns n < N of exp(v - part_val[i]) (0 where part_val is -inf), and
+ * row_lse [M][2] = (M, log S) per row as the sampling kernel's own merge of the partials computes them: M = the row maximum, S = sum of
+ * exp(v - M) over the row, so that logsumexp(row) = M + log S. */
+int ntts_k_head_logprob_probe(const void* X_dev, const void* W_dev, int32_t M, int32_t N, int32_t K, int32_t variant, int32_t fp8, float xscale,
+                              const uint32_t* seen, const float* rep_pen, const int32_t* mask_eos, float* logits_out, uint16_t* logits_bf16_out,
+                              float* part_val, int32_t* part_idx, float* part_sum, int32_t part_cap, int32_t* n_part, int32_t* part_width,
+                              float* row_lse);
 
 #ifdef __cplusplus
 }

@@ -141,6 +141,13 @@ struct ntts_backbone {
     bool seen_ev_used = false;
     int n_penalised = 0;             // live requests with repetition_penalty != 1
     bool graph_has_seen = false;
+    // Per-token log-probabilities (ntts_backbone_set_logprobs): while on, the lm_head runs the kernels whose epilogue also leaves the partial sums
+    // of exp (gemm.h EPI_ARGMAX_LSE) and the sampling kernel records log softmax(row)[token] beside every id.  While off both get null pointers,
+    // nothing is allocated and the step is the step it was; the captured steps bake the choice (graph_has_lse).
+    bool logprobs_on = false;
+    float* part_sum = nullptr;       // [B][n_part_full], beside part_val
+    float* out_logprobs = nullptr;   // [B][max_context], entry for entry beside sl.out_tokens
+    bool graph_has_lse = false;
     // ---- decode-step shape, fixed at create() from the batch size (every constant below was swept on MI355X; the losing variants and
     //      their knobs are gone -- DESIGN.md section 4 keeps the numbers, the git history the code)
     int ks_o = 1, ks_d = 1;          // split-K of o_proj / down_proj (fp32 slabs reduced by the norm kernel behind them)
@@ -604,7 +611,7 @@ extern "C" void ntts_backbone_destroy(ntts_backbone* e) {
     bool last_reader = true;
     if (e->share) { last_reader = e->share->refs.fetch_sub(1) == 1; if (last_reader) delete e->share; else e->share->last_decode_ns[e->share_idx].store(0); }
     void* bufs[] = {last_reader ? e->arena : nullptr, e->gu_map_gate, e->gu_map_up, e->kv, e->ibuf, e->h_dec, e->xn_dec, e->qkv_dec, e->attn_dec,
-                    e->act_dec, e->slabs, e->slabs2, e->h_alt, e->part_val, e->part_idx, e->logits, e->logits_bf16, e->seen, e->seen_cols, e->h_pf, e->xn_pf, e->qkv_pf, e->attn_pf,
+                    e->act_dec, e->slabs, e->slabs2, e->h_alt, e->part_val, e->part_idx, e->logits, e->logits_bf16, e->seen, e->seen_cols, e->part_sum, e->out_logprobs, e->h_pf, e->xn_pf, e->qkv_pf, e->attn_pf,
                     e->o_pf, e->act_pf, e->meta_dev, e->as_scores, e->as_stats, e->as_oslabs, e->step_meta, e->rope_rows};
     for (void* b : bufs)
         if (b) hipFree(b);
@@ -1229,7 +1236,8 @@ static void k_lm_head(ntts_backbone* e, bool keep_logits, int rows) {
     a.logits = keep_logits ? e->logits : nullptr; a.ld_logits = V;
     a.logits_bf16 = (keep_logits && e->n_sampling > 0) ? e->logits_bf16 : nullptr; a.ld_logits_bf16 = e->ldl;
     if (e->n_penalised > 0) { a.seen = e->seen; a.seen_pitch = e->seen_pitch; a.rep_pen = e->sl.rep_pen; }
-    lm_head_launch(a, e->head_tile, e->fp8, e->stream);     // (gemm.h: the tile per head_tile, with or without the penalty epilogue)
+    if (e->logprobs_on) a.part_sum = e->part_sum;
+    lm_head_launch(a, e->head_tile, e->fp8, e->stream);     // (gemm.h: the tile per head_tile, with or without the penalty / log-sum-exp epilogue)
 }
 
 static void lm_head_and_sample(ntts_backbone* e, int phase) {
@@ -1241,6 +1249,7 @@ static void lm_head_and_sample(ntts_backbone* e, int phase) {
     s.logits = e->n_sampling > 0 ? e->logits_bf16 : nullptr; s.ld_logits = e->ldl; s.vocab = e->lr_rows ? e->lr_rows : e->cfg.vocab_size;
     if (e->lr_rows) { s.n_range = e->lr_rows - 1; s.id_base = e->lr_lo; s.id_tail = e->lr_eos; }
     if (e->n_penalised > 0) { s.seen = e->seen; s.seen_pitch = e->seen_pitch; }
+    if (e->logprobs_on) { s.part_sum = e->part_sum; s.out_logprobs = e->out_logprobs; }
     NTTS_LAUNCH((sample_greedy_kernel), dim3(rows), dim3(256), e->stream, s);
 }
 
@@ -1473,6 +1482,7 @@ static void ks_lm_head(ntts_backbone* e, bool keep_logits) {
     a.logits = keep_logits ? e->logits : nullptr; a.ld_logits = V;
     a.logits_bf16 = (keep_logits && e->n_sampling > 0) ? e->logits_bf16 : nullptr; a.ld_logits_bf16 = e->ldl;
     if (e->n_penalised > 0) { a.seen = e->seen; a.seen_pitch = e->seen_pitch; a.rep_pen = e->sl.rep_pen; }
+    if (e->logprobs_on) a.part_sum = e->part_sum;
     lm_head_gemv_launch(a, e->fp8, e->stream);
 }
 
@@ -2022,7 +2032,7 @@ extern "C" int ntts_backbone_decode(ntts_backbone* e, int32_t n_steps) {
         NTTS_LAUNCH((bt_update_kernel), dim3((nt + 63) / 64), dim3(64), st, (const int*)e->meta_dev, nt, e->block_table, e->max_pages);
     }
     if ((e->graph || e->graph_split || e->graph_shape[0] || e->graph_shape[1]) &&
-        (e->graph_has_logits != (e->n_sampling > 0) || e->graph_has_seen != (e->n_penalised > 0)))   // the step's launch arguments (and the lm_head's kernel) changed:
+        (e->graph_has_logits != (e->n_sampling > 0) || e->graph_has_seen != (e->n_penalised > 0) || e->graph_has_lse != e->logprobs_on))   // the step's launch arguments (and the lm_head's kernel) changed:
         drop_graphs(e);                                                                             // every capture is stale
     // small-batch path: steps whose longest context has reached attn_split_ctx run the context-split attention (its own graph)
     const bool can_split = e->attn_split > 0 && !e->attn_tl;
@@ -2042,6 +2052,7 @@ extern "C" int ntts_backbone_decode(ntts_backbone* e, int32_t n_steps) {
         e->graph_split_tried = true;
         e->graph_has_logits = e->n_sampling > 0;
         e->graph_has_seen = e->n_penalised > 0;
+        e->graph_has_lse = e->logprobs_on;
         e->split_active = true;
         capture(1, &e->graph_split);
         e->split_active = false;
@@ -2050,6 +2061,7 @@ extern "C" int ntts_backbone_decode(ntts_backbone* e, int32_t n_steps) {
         e->graph_tried = true;
         e->graph_has_logits = e->n_sampling > 0;
         e->graph_has_seen = e->n_penalised > 0;
+        e->graph_has_lse = e->logprobs_on;
         capture(1, &e->graph);   // several steps per graph were measured: -0.3 % per step (profiles/r02a_sweep_nt_graphsteps.jsonl), not kept
     }
     HIPCHK(e, hipEventRecord(e->ev[2], st));
@@ -2147,6 +2159,67 @@ extern "C" int ntts_backbone_read(ntts_backbone* e, int32_t slot, int32_t* out_i
         HIPCHK(e, hipMemcpy(out_ids, e->sl.out_tokens + (size_t)slot * e->sl.out_stride, k * sizeof(int), hipMemcpyDeviceToHost));
     *n_out = nn;
     if (finished) *finished = (st == SLOT_FINISHED) ? 1 : 0;
+    return NTTS_OK;
+}
+
+// Per-token log-probabilities: the engine-level switch and the two reads (the twins of ntts_backbone_read / ntts_backbone_read_finished)
+extern "C" int ntts_backbone_set_logprobs(ntts_backbone* e, int32_t enable) {
+    if (!e) return NTTS_EINVAL;
+    for (const HostSlot& sl : e->slots)
+        if (sl.state != SLOT_FREE) return fail(e, NTTS_ESTATE, "set_logprobs: a slot is in use");
+    const bool on = enable != 0;
+    if (on == e->logprobs_on) return NTTS_OK;
+    HIPCHK(e, hipSetDevice(e->device));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    if (on && !e->part_sum) {        // the first enable: the third partial array and the record, zeroed
+        const size_t np = (size_t)e->cfg.max_batch * e->n_part_full * sizeof(float), nr = (size_t)e->cfg.max_batch * e->cfg.max_context * sizeof(float);
+        float *ps = nullptr, *lp = nullptr;
+        hipError_t rc = hipMalloc((void**)&ps, np);
+        if (rc == hipSuccess) rc = hipMemset(ps, 0, np);
+        if (rc == hipSuccess) rc = hipMalloc((void**)&lp, nr);
+        if (rc == hipSuccess) rc = hipMemset(lp, 0, nr);
+        if (rc != hipSuccess) {
+            if (ps) (void)hipFree(ps);
+            if (lp) (void)hipFree(lp);
+            return fail(e, NTTS_EHIP, "set_logprobs: allocation failed: %s", hipGetErrorString(rc));
+        }
+        e->part_sum = ps; e->out_logprobs = lp;
+    }
+    drop_graphs(e);                  // the lm_head's kernel and the sampling kernel's arguments are baked into the captured step
+    e->logprobs_on = on;
+    return NTTS_OK;
+}
+
+extern "C" int ntts_backbone_read_logprobs(ntts_backbone* e, int32_t slot, float* out, int32_t cap, int32_t* n_out) {
+    if (!e || slot < 0 || slot >= e->cfg.max_batch || !n_out) return fail(e, NTTS_EINVAL, "bad argument");
+    if (!e->logprobs_on) return fail(e, NTTS_ESTATE, "log-probabilities are not recorded: call ntts_backbone_set_logprobs(e, 1) first");
+    HIPCHK(e, hipSetDevice(e->device));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    int nn = 0;
+    HIPCHK(e, hipMemcpy(&nn, e->sl.n_new + slot, sizeof(int), hipMemcpyDeviceToHost));
+    if (e->slots[slot].state == SLOT_FREE) nn = 0;
+    const int k = nn < cap ? nn : cap;
+    if (out && k > 0)
+        HIPCHK(e, hipMemcpy(out, e->out_logprobs + (size_t)slot * e->sl.out_stride, k * sizeof(float), hipMemcpyDeviceToHost));
+    *n_out = nn;
+    return NTTS_OK;
+}
+
+extern "C" int ntts_backbone_read_finished_logprobs(ntts_backbone* e, int32_t slot, float* out, int32_t cap, int32_t* n_out) {
+    if (!e || slot < 0 || slot >= e->cfg.max_batch || !n_out) return fail(e, NTTS_EINVAL, "bad argument");
+    if (!e->logprobs_on) return fail(e, NTTS_ESTATE, "log-probabilities are not recorded: call ntts_backbone_set_logprobs(e, 1) first");
+    const int B = e->cfg.max_batch;
+    if (!e->snap_valid || e->snap_host[slot] != SLOT_FINISHED || e->slots[slot].state == SLOT_FREE || e->snap_gen[slot] != e->slots[slot].gen)
+        return fail(e, NTTS_ESTATE, "slot %d was not finished in the last completed snapshot (or was released / refilled since it was taken)", slot);
+    HIPCHK(e, hipSetDevice(e->device));
+    // (ntts_backbone_read_finished's rule: a finished slot's record does not change until the slot is released)
+    const int nn = e->snap_host[B + slot];
+    const int k = nn < cap ? nn : cap;
+    if (out && k > 0) {
+        HIPCHK(e, hipMemcpyAsync(out, e->out_logprobs + (size_t)slot * e->sl.out_stride, k * sizeof(float), hipMemcpyDeviceToHost, e->copy_stream));
+        HIPCHK(e, hipStreamSynchronize(e->copy_stream));
+    }
+    *n_out = nn;
     return NTTS_OK;
 }
 
@@ -2348,6 +2421,7 @@ extern "C" int ntts_backbone_activate(ntts_backbone* e, int32_t n, const int32_t
     ActivateArgs a{};
     a.pairs = e->meta_dev; a.sl = e->sl; a.block_table = e->block_table; a.max_pages = e->max_pages;
     a.seen = e->seen; a.seen_pitch = e->seen_pitch;
+    a.out_logprobs = e->logprobs_on ? e->out_logprobs : nullptr;
     NTTS_LAUNCH((activate_slots_kernel), dim3(n), dim3(64), e->stream, a);
     for (int i = 0; i < n; ++i) {
         HostSlot& src = e->slots[park_slots[i]];

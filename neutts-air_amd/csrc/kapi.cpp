@@ -425,10 +425,11 @@ extern "C" int ntts_k_mfma_probe(float* out_dev_768) {
 
 // ---- the lm_head launch of the decode step (gemm.h lm_head_launch / gemv.h lm_head_gemv_launch) on caller-supplied operands: the penalty epilogue of
 //      every tile variant against tests/repetition_spec.py.  The head is packed here by the kernels the engine packs it with.
-extern "C" int ntts_k_head_penalty_probe(const void* X_dev, const void* W_dev, int32_t M, int32_t N, int32_t K, int32_t variant, int32_t fp8, float xscale,
-                                         const uint32_t* seen, const float* rep_pen, const int32_t* mask_eos, float* logits_out,
-                                         uint16_t* logits_bf16_out, float* part_val, int32_t* part_idx, int32_t part_cap, int32_t* n_part,
-                                         int32_t* part_width) {
+//      part_sum / row_lse non-null (ntts_k_head_logprob_probe): the launch with the log-sum-exp epilogue, then sample.h's own merge of the partials.
+static int head_probe(const void* X_dev, const void* W_dev, int32_t M, int32_t N, int32_t K, int32_t variant, int32_t fp8, float xscale,
+                      const uint32_t* seen, const float* rep_pen, const int32_t* mask_eos, float* logits_out,
+                      uint16_t* logits_bf16_out, float* part_val, int32_t* part_idx, int32_t part_cap, int32_t* n_part,
+                      int32_t* part_width, float* part_sum, float* row_lse) {
     if (!X_dev || !W_dev || !logits_out || !logits_bf16_out || !part_val || !part_idx || !n_part || !part_width) return NTTS_EINVAL;
     if (M < 1 || N < 16 || K < 64 || (K % 64) || (fp8 && (K % 128))) return NTTS_EINVAL;
     if (variant != 0 && variant != 1 && variant != 2 && variant != 4 && variant != 8) return NTTS_EINVAL;
@@ -445,10 +446,11 @@ extern "C" int ntts_k_head_penalty_probe(const void* X_dev, const void* W_dev, i
     const long Np = ((long)N + 63) / 64 * 64, ldl = ((long)N + 7) / 8 * 8, pitch = seen_pitch_for(N), wsrc = ((long)N + 31) / 32;
     const size_t esz = fp8 ? 1 : 2;
     struct Buf { void* p = nullptr; ~Buf() { if (p) (void)hipFree(p); } };
-    Buf wt, ws, xq, xf, lg, lb, pv, pi, bm, pen, me;
+    Buf wt, ws, xq, xf, lg, lb, pv, pi, bm, pen, me, psum, rl;
     auto dalloc = [](Buf& b, size_t bytes) { return hipMalloc(&b.p, bytes) == hipSuccess && hipMemset(b.p, 0, bytes) == hipSuccess; };
     if (!dalloc(wt, (size_t)Np * K * esz) || !dalloc(lg, (size_t)M * N * 4) || !dalloc(lb, (size_t)M * ldl * 2) || !dalloc(pv, (size_t)M * np * 4) ||
         !dalloc(pi, (size_t)M * np * 4) || !dalloc(me, (size_t)M * 4)) return NTTS_ENOMEM;
+    if (part_sum && (!dalloc(psum, (size_t)M * np * 4) || !dalloc(rl, (size_t)M * 2 * 4))) return NTTS_ENOMEM;
     const hipStream_t st = (hipStream_t)0;
     {   // (plain pointers for the launches: the emulator's launch captures its arguments by value)
         const void* src = W_dev;
@@ -493,6 +495,7 @@ extern "C" int ntts_k_head_penalty_probe(const void* X_dev, const void* W_dev, i
         a.part_val = (float*)pv.p; a.part_idx = (int*)pi.p; a.mask_eos = (const int*)me.p;
         a.logits = (float*)lg.p; a.ld_logits = N; a.logits_bf16 = (bf16_t*)lb.p; a.ld_logits_bf16 = ldl;
         if (seen) { a.seen = (const unsigned int*)bm.p; a.seen_pitch = pitch; a.rep_pen = (const float*)pen.p; }
+        a.part_sum = (float*)psum.p;
         lm_head_gemv_launch(a, fp8 != 0, st);
     } else {
         GemmArgs a{};
@@ -502,14 +505,42 @@ extern "C" int ntts_k_head_penalty_probe(const void* X_dev, const void* W_dev, i
         a.part_val = (float*)pv.p; a.part_idx = (int*)pi.p; a.mask_eos = (const int*)me.p;
         a.logits = (float*)lg.p; a.ld_logits = N; a.logits_bf16 = (bf16_t*)lb.p; a.ld_logits_bf16 = ldl;
         if (seen) { a.seen = (const unsigned int*)bm.p; a.seen_pitch = pitch; a.rep_pen = (const float*)pen.p; }
+        a.part_sum = (float*)psum.p;
         lm_head_launch(a, variant, fp8 != 0, st);
+    }
+    if (part_sum) {   // (M, log S) per row, by the code the sampling kernel merges the partials with
+        const float* pvp = (const float*)pv.p;
+        const float* psp = (const float*)psum.p;
+        float* rlp = (float*)rl.p;
+        NTTS_LAUNCH((lse_merge_probe_kernel), dim3((unsigned)M), dim3(256), st, pvp, psp, (int)np, rlp);
     }
     if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess) return NTTS_EHIP;
     if (hipMemcpy(logits_out, lg.p, (size_t)M * N * 4, hipMemcpyDeviceToHost) != hipSuccess) return NTTS_EHIP;
     if (hipMemcpy2D(logits_bf16_out, (size_t)N * 2, lb.p, (size_t)ldl * 2, (size_t)N * 2, (size_t)M, hipMemcpyDeviceToHost) != hipSuccess) return NTTS_EHIP;
     if (hipMemcpy(part_val, pv.p, (size_t)M * np * 4, hipMemcpyDeviceToHost) != hipSuccess) return NTTS_EHIP;
     if (hipMemcpy(part_idx, pi.p, (size_t)M * np * 4, hipMemcpyDeviceToHost) != hipSuccess) return NTTS_EHIP;
+    if (part_sum) {
+        if (hipMemcpy(part_sum, psum.p, (size_t)M * np * 4, hipMemcpyDeviceToHost) != hipSuccess) return NTTS_EHIP;
+        if (hipMemcpy(row_lse, rl.p, (size_t)M * 2 * 4, hipMemcpyDeviceToHost) != hipSuccess) return NTTS_EHIP;
+    }
     *n_part = np;
     *part_width = width;
     return NTTS_OK;
+}
+
+extern "C" int ntts_k_head_penalty_probe(const void* X_dev, const void* W_dev, int32_t M, int32_t N, int32_t K, int32_t variant, int32_t fp8, float xscale,
+                                         const uint32_t* seen, const float* rep_pen, const int32_t* mask_eos, float* logits_out,
+                                         uint16_t* logits_bf16_out, float* part_val, int32_t* part_idx, int32_t part_cap, int32_t* n_part,
+                                         int32_t* part_width) {
+    return head_probe(X_dev, W_dev, M, N, K, variant, fp8, xscale, seen, rep_pen, mask_eos, logits_out, logits_bf16_out, part_val, part_idx, part_cap,
+                      n_part, part_width, nullptr, nullptr);
+}
+
+extern "C" int ntts_k_head_logprob_probe(const void* X_dev, const void* W_dev, int32_t M, int32_t N, int32_t K, int32_t variant, int32_t fp8, float xscale,
+                                         const uint32_t* seen, const float* rep_pen, const int32_t* mask_eos, float* logits_out,
+                                         uint16_t* logits_bf16_out, float* part_val, int32_t* part_idx, float* part_sum, int32_t part_cap,
+                                         int32_t* n_part, int32_t* part_width, float* row_lse) {
+    if (!part_sum || !row_lse) return NTTS_EINVAL;
+    return head_probe(X_dev, W_dev, M, N, K, variant, fp8, xscale, seen, rep_pen, mask_eos, logits_out, logits_bf16_out, part_val, part_idx, part_cap,
+                      n_part, part_width, part_sum, row_lse);
 }

@@ -36,11 +36,16 @@ enum GemmEpi {
     EPI_RESID = 6,     // out bf16 [M][N] = bf16(resid_bf16 + bf16(acc + bias)): o_proj + residual add (may be in place)
     EPI_SILU_SPLIT3 = 7, // codec, precision = high: v = silu(acc + bias) leaves as a SPLIT bf16 operand row [hi | lo | hi] of 3 N columns
                          // (hi = bf16(v), lo = bf16(v - hi); ldo = 3 N): the next GEMM's K-loop over [wh | wh | wl] sees v to ~16 mantissa bits
-    EPI_ARGMAX_PEN = 8   // EPI_ARGMAX with the repetition penalty (GemmArgs::seen / rep_pen) applied to bf16(acc) ahead of everything that reads the logit; the
+    EPI_ARGMAX_PEN = 8,  // EPI_ARGMAX with the repetition penalty (GemmArgs::seen / rep_pen) applied to bf16(acc) ahead of everything that reads the logit; the
                          // EOS mask then overwrites its column as before (-inf either way: the two commute for any valid penalty).  A kernel
                          // of its own, launched only while a penalised request is live: the plain lm_head keeps its instructions and its registers
+    EPI_ARGMAX_LSE = 9,      // EPI_ARGMAX / EPI_ARGMAX_PEN that also leave GemmArgs::part_sum = sum of exp(v - partial max) over the partial's in-range columns,
+    EPI_ARGMAX_PEN_LSE = 10  // v = the processed value the dump, the bf16 row and the max see: the log-sum-exp of the row, carried through the partials to the
+                             // sampling kernel (per-token log-probabilities).  Kernels of their own again, launched only while ntts_backbone_set_logprobs is on
 };
-constexpr bool epi_is_argmax(int epi) { return epi == EPI_ARGMAX || epi == EPI_ARGMAX_PEN; }
+constexpr bool epi_is_argmax(int epi) { return epi == EPI_ARGMAX || epi == EPI_ARGMAX_PEN || epi == EPI_ARGMAX_LSE || epi == EPI_ARGMAX_PEN_LSE; }
+constexpr bool epi_has_pen(int epi) { return epi == EPI_ARGMAX_PEN || epi == EPI_ARGMAX_PEN_LSE; }
+constexpr bool epi_has_lse(int epi) { return epi == EPI_ARGMAX_LSE || epi == EPI_ARGMAX_PEN_LSE; }
 
 struct GemmArgs {
     const bf16_t* X;
@@ -101,6 +106,8 @@ struct GemmArgs {
                               // bytes between consecutive K tiles of a row -- so that a block's X tile is one contiguous run; 0: row-major rows of ldx elements
     unsigned long long* tl;   // diagnostics (ntts_backbone_gemv_timeline on a large-batch engine): [workgroups][16] timestamps of wave 0 -- 0 entry,
                               // 1 first ring slots requested, 2 first tile landed (past the first barrier), 3 k-loop done, 4 epilogue issued, 5 stores drained
+    // EPI_ARGMAX_LSE / EPI_ARGMAX_PEN_LSE (last, so that no other field moves)
+    float* part_sum;          // [M][part_stride], beside part_val: sum over the partial's columns n < N of exp(v - part_val); 0 when part_val is -inf
 };
 
 // position t of the grouped tile order (8 m-blocks x all n-blocks per group, m fastest) -> tile coordinates
@@ -176,6 +183,13 @@ NTTS_D f32x2 silu_fast2(f32x2 x) {
 // The penalised logit: v * p below zero, v / p from zero up (HF's own fp32 arithmetic: an IEEE division, not a reciprocal), then ONE rounding to
 // bf16 -- the sampler's 16-bit radix select and the argmax partials both work on bf16 rows.  -inf (a masked EOS) stays -inf, NaN stays NaN.
 NTTS_D float rep_penalised(float v, float pen) { return rbf(v < 0.f ? v * pen : v / pen); }
+// (max, sum of exp(v - max)) pairs of two column groups -> the pair of their union.  A group without one finite value is (-inf, 0); the exponent is
+// formed only between two DIFFERENT maxima, of which the larger one is finite: exp(-inf - -inf) never arises, and exp(-inf - finite) = 0 scales a 0
+NTTS_D void lse_merge(float& mx, float& sum, float omx, float osum) {
+    if (omx > mx) { sum = osum + sum * fexp(mx - omx); mx = omx; }
+    else if (omx < mx) sum += osum * fexp(omx - mx);
+    else sum += osum;
+}
 NTTS_D float gemm_bias(const GemmArgs& p, int n) { return p.bias_f32 ? p.bias_f32[n] : (p.bias ? bf2f(p.bias[n]) : 0.f); }
 
 // ---- epilogue shared by the GEMM kernels: lane owns token m (per a) x features nb16 .. nb16+15
@@ -370,7 +384,7 @@ NTTS_D void gemm_epilogue(const GemmArgs& p, f32x4 (&acc)[TM][4], int mrow0, int
             float best = -INFINITY;
             int bidx = 0x7fffffff;
             const int meos = (mok && p.mask_eos) ? p.mask_eos[m] : 0;   // eos id + 1, or 0
-            if constexpr (EPI == EPI_ARGMAX_PEN) {
+            if constexpr (epi_has_pen(EPI)) {
                 // this lane's 16 columns start at a multiple of 16: their seen bits are ONE halfword of the row.  The penalised value replaces the
                 // accumulator in place (rounding it again below changes nothing), so the dump, the bf16 row and the partials all see it
                 const float pen = mok ? p.rep_pen[m] : 1.0f;
@@ -397,7 +411,17 @@ NTTS_D void gemm_epilogue(const GemmArgs& p, f32x4 (&acc)[TM][4], int mrow0, int
                         if (mok && p.logits) p.logits[(long)m * p.ld_logits + n] = v;
                         if (v > best) { best = v; bidx = n; }      // ascending n + strict '>' = first max wins
                     }
+                    if constexpr (epi_has_lse(EPI)) acc[a][j][r] = n < p.N ? v : -INFINITY;   // the processed value, kept for the sum below
                 }
+            float lsum = 0.f;
+            if constexpr (epi_has_lse(EPI)) {
+                if (best > -INFINITY) {                            // (-inf: all padding, or only a masked EOS -- the sum stays 0)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) lsum += fexp(acc[a][j][r] - best);
+                }
+            }
             if (p.logits_bf16 && mok) {
                 bf16_t* dst = p.logits_bf16 + (long)m * p.ld_logits_bf16 + nb16;
                 if (nb16 + 16 <= p.N) {
@@ -412,12 +436,18 @@ NTTS_D void gemm_epilogue(const GemmArgs& p, f32x4 (&acc)[TM][4], int mrow0, int
             for (int sh = 16; sh <= 32; sh <<= 1) {
                 const float ov = shfl_xor(best, sh);
                 const int oi = shfl_xor(bidx, sh);
+                if constexpr (epi_has_lse(EPI)) {                  // (max, sum) pairs merge by rescaling to the larger maximum
+                    const float os = shfl_xor(lsum, sh);
+                    float mx = best;
+                    lse_merge(mx, lsum, ov, os);
+                }
                 if (ov > best || (ov == best && oi < bidx)) { best = ov; bidx = oi; }
             }
             if (mok && g == 0) {
                 const long pi = (long)m * p.part_stride + nb * WN + wn;
                 p.part_val[pi] = best;
                 p.part_idx[pi] = bidx;
+                if constexpr (epi_has_lse(EPI)) p.part_sum[pi] = lsum;
             }
         }
     }
@@ -450,7 +480,7 @@ NTTS_D void gemm_epilogue_nat(const GemmArgs& p, f32x4 (&acc)[TM][TN], int mrow0
             float best = -INFINITY;
             int bidx = 0x7fffffff;
             const int meos = (mok && p.mask_eos) ? p.mask_eos[m] : 0;   // eos id + 1, or 0
-            if constexpr (EPI == EPI_ARGMAX_PEN) {
+            if constexpr (epi_has_pen(EPI)) {
                 // the wave's TN * 16 columns start at a multiple of 32 (nw0 = 32 * (9 nb + 3 wn) on the 256 x 288 tile): TN / 2 words of the row;
                 // column nw0 + j*16 + g*4 + r is bit (j & 1) * 16 + g*4 + r of word j >> 1
                 static_assert(TN % 2 == 0, "whole bitmap words per wave tile");
@@ -484,6 +514,7 @@ NTTS_D void gemm_epilogue_nat(const GemmArgs& p, f32x4 (&acc)[TM][TN], int mrow0
                         if (mok && p.logits) p.logits[(long)m * p.ld_logits + n] = v;
                         if (v > best) { best = v; bidx = n; }      // ascending n + strict '>' = first max wins
                     }
+                    if constexpr (epi_has_lse(EPI)) acc[a][j][r] = n < p.N ? v : -INFINITY;   // the processed value, kept for the sum below
                 }
                 if (p.logits_bf16 && mok) {
                     const int n4 = nw0 + j * 16 + g * 4;
@@ -492,16 +523,31 @@ NTTS_D void gemm_epilogue_nat(const GemmArgs& p, f32x4 (&acc)[TM][TN], int mrow0
                     else for (int e = 0; e < 4; ++e) if (n4 + e < p.N) dst[e] = lo[e];
                 }
             }
+            float lsum = 0.f;
+            if constexpr (epi_has_lse(EPI)) {
+                if (best > -INFINITY) {                            // (-inf: all padding, or only a masked EOS -- the sum stays 0)
+#pragma unroll
+                    for (int j = 0; j < TN; ++j)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) lsum += fexp(acc[a][j][r] - best);
+                }
+            }
 #pragma unroll
             for (int sh = 16; sh <= 32; sh <<= 1) {
                 const float ov = shfl_xor(best, sh);
                 const int oi = shfl_xor(bidx, sh);
+                if constexpr (epi_has_lse(EPI)) {                  // (max, sum) pairs merge by rescaling to the larger maximum
+                    const float os = shfl_xor(lsum, sh);
+                    float mx = best;
+                    lse_merge(mx, lsum, ov, os);
+                }
                 if (ov > best || (ov == best && oi < bidx)) { best = ov; bidx = oi; }
             }
             if (mok && g == 0) {
                 const long pi = (long)m * p.part_stride + nb * WN + wn;
                 p.part_val[pi] = best;
                 p.part_idx[pi] = bidx;
+                if constexpr (epi_has_lse(EPI)) p.part_sum[pi] = lsum;
             }
         } else {
             static_assert(epi_is_argmax(EPI) || EPI == EPI_BF16, "epilogues of the natural-order tile");
@@ -784,7 +830,8 @@ inline void gemm_launch(GemmArgs p, int ksplit, hipStream_t s) {
 
 // The decode lm_head (backbone.cpp k_lm_head; kapi.cpp ntts_k_head_penalty_probe runs the same launch on caller-supplied data).  head_tile: 0 = 64 x 64
 // skinny / 4-slot ring, 1 = 128 x 128, 2 = 256 x 256 (16 waves), 4 = natural-order 256 x 288 (12 waves, bf16 only); the 256-row tiles stream W with the
-// non-temporal policy (read once per step).  a.seen != null selects the kernels with the repetition penalty in their epilogue.
+// non-temporal policy (read once per step).  a.seen != null selects the kernels with the repetition penalty in their epilogue, a.part_sum != null
+// those that also reduce the row's log-sum-exp.
 template <int EPI>
 inline void lm_head_launch_epi(const GemmArgs& a, int head_tile, bool fp8, hipStream_t s) {
     switch (head_tile) {
@@ -803,7 +850,10 @@ inline void lm_head_launch_epi(const GemmArgs& a, int head_tile, bool fp8, hipSt
     }
 }
 inline void lm_head_launch(const GemmArgs& a, int head_tile, bool fp8, hipStream_t s) {
-    if (a.seen) lm_head_launch_epi<EPI_ARGMAX_PEN>(a, head_tile, fp8, s);
+    if (a.part_sum) {           // per-token log-probabilities on: the kernels whose epilogue also leaves the partial sums of exp
+        if (a.seen) lm_head_launch_epi<EPI_ARGMAX_PEN_LSE>(a, head_tile, fp8, s);
+        else lm_head_launch_epi<EPI_ARGMAX_LSE>(a, head_tile, fp8, s);
+    } else if (a.seen) lm_head_launch_epi<EPI_ARGMAX_PEN>(a, head_tile, fp8, s);
     else lm_head_launch_epi<EPI_ARGMAX>(a, head_tile, fp8, s);
 }
 // words per row of a seen bitmap for a head of N columns: every tile's padding columns (up to 287 past N) have their word, rows stay 16-byte aligned

@@ -65,6 +65,7 @@ struct GemvArgs {
     const unsigned int* seen;   // EPI_ARGMAX_PEN (gemm.h GemmArgs): [M][seen_pitch] seen-column bitmap and the per-row repetition penalty
     long seen_pitch;
     const float* rep_pen;
+    float* part_sum;            // EPI_ARGMAX_LSE / EPI_ARGMAX_PEN_LSE (gemm.h GemmArgs::part_sum): [M][part_stride] sum of exp(v - part_val) per partial
     // F8 kernels (fp8 model, gemm.h GemmArgs): X and W hold e4m3 BYTES (ldx / K count elements = bytes; a 128-byte k-tile is 128 k-values, K % 128 == 0),
     // the panel in LDS holds bytes (PRO: pro.out_fp8_inv quantises the normalised rows), out = acc * (xscale * wscale[n]); EPI_SILU_MUL emits e4m3
     // bytes when out_fp8_inv > 0 (down_proj's input).  Byte for byte the staging is the bf16 kernel's: a lane's 32 bytes per k-tile are 32 k-values
@@ -239,7 +240,7 @@ NTTS_KERNEL((FW + 4) * 64) void gemv_kernel(GemvArgs p) {
         float best = -INFINITY;
         int bidx = 0x7fffffff;
         const int meos = (mok && p.mask_eos) ? p.mask_eos[m] : 0;     // eos id + 1, or 0
-        if constexpr (EPI == EPI_ARGMAX_PEN) {                        // the wave's 16 features are one halfword of the row; this lane's 4 are bits g*4 .. g*4+3
+        if constexpr (epi_has_pen(EPI)) {                        // the wave's 16 features are one halfword of the row; this lane's 4 are bits g*4 .. g*4+3
             const float pen = mok ? p.rep_pen[m] : 1.0f;
             unsigned int sbits = 0;
             if (pen != 1.0f) sbits = (((const unsigned short*)(p.seen + (long)m * p.seen_pitch))[f0 >> 4] >> (g * 4)) & 15u;
@@ -258,18 +259,32 @@ NTTS_KERNEL((FW + 4) * 64) void gemv_kernel(GemvArgs p) {
             lo[r] = f2bf(v);
             if (mok && p.logits) p.logits[(long)m * p.ld_logits + n] = v;
             if (v > best) { best = v; bidx = n; }                     // ascending n + strict '>' = first max wins
+            if constexpr (epi_has_lse(EPI)) acc[r] = v;               // the processed value (-inf past n_valid), kept for the sum below
+        }
+        float lsum = 0.f;
+        if constexpr (epi_has_lse(EPI)) {
+            if (best > -INFINITY) {                                   // (-inf: all padding, or only a masked EOS -- the sum stays 0)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) lsum += fexp(acc[r] - best);
+            }
         }
         if (p.logits_bf16 && mok) *(u32x2*)(p.logits_bf16 + (long)m * p.ld_logits_bf16 + nf) = *(u32x2*)&lo[0];
 #pragma unroll
         for (int sh = 16; sh <= 32; sh <<= 1) {
             const float ov = shfl_xor(best, sh);
             const int oi = shfl_xor(bidx, sh);
+            if constexpr (epi_has_lse(EPI)) {                         // (max, sum) pairs merge by rescaling to the larger maximum
+                const float os = shfl_xor(lsum, sh);
+                float mx = best;
+                lse_merge(mx, lsum, ov, os);
+            }
             if (ov > best || (ov == best && oi < bidx)) { best = ov; bidx = oi; }
         }
         if (mok && g == 0) {
             const long pi = (long)m * p.part_stride + (f0 >> 4);
             p.part_val[pi] = best;
             p.part_idx[pi] = bidx;
+            if constexpr (epi_has_lse(EPI)) p.part_sum[pi] = lsum;
         }
     } else {
         static_assert(EPI == EPI_SPLITK || EPI == EPI_SILU_MUL || epi_is_argmax(EPI), "epilogues of the small-batch kernel");
@@ -310,8 +325,14 @@ inline void gemv_launch(GemvArgs p, int ksplit, hipStream_t s) {
 }
 
 // the small-batch lm_head (backbone.cpp ks_lm_head, kapi.cpp ntts_k_head_penalty_probe); a.seen != null: the kernels with the repetition penalty
+template <int EPI>
+inline void lm_head_gemv_launch_epi(const GemvArgs& a, bool fp8, hipStream_t s) {
+    if (fp8) gemv_launch<EPI, false, 4, true>(a, 1, s); else gemv_launch<EPI, false>(a, 1, s);
+}
 inline void lm_head_gemv_launch(const GemvArgs& a, bool fp8, hipStream_t s) {
-    if (a.seen) { if (fp8) gemv_launch<EPI_ARGMAX_PEN, false, 4, true>(a, 1, s); else gemv_launch<EPI_ARGMAX_PEN, false>(a, 1, s); }
+    if (a.part_sum) {   // per-token log-probabilities on
+        if (a.seen) lm_head_gemv_launch_epi<EPI_ARGMAX_PEN_LSE>(a, fp8, s); else lm_head_gemv_launch_epi<EPI_ARGMAX_LSE>(a, fp8, s);
+    } else if (a.seen) { if (fp8) gemv_launch<EPI_ARGMAX_PEN, false, 4, true>(a, 1, s); else gemv_launch<EPI_ARGMAX_PEN, false>(a, 1, s); }
     else { if (fp8) gemv_launch<EPI_ARGMAX, false, 4, true>(a, 1, s); else gemv_launch<EPI_ARGMAX, false>(a, 1, s); }
 }
 

@@ -60,6 +60,10 @@ struct SampleArgs {
     int n_range, id_base, id_tail;
     unsigned int* seen;      // [slots][seen_pitch] seen-column bitmap (gemm.h GemmArgs::seen); null while no penalised request is live
     long seen_pitch;
+    // per-token log-probabilities (ntts_backbone_set_logprobs): with both pointers non-null a live row also records log softmax(row)[token] over the
+    // WHOLE processed row (all `vocab` columns, -inf ones contributing 0) -- temperature and the warpers do not enter
+    const float* part_sum;   // [rows][n_part] sum of exp(v - part_val) per partial (gemm.h EPI_ARGMAX_LSE); null = off
+    float* out_logprobs;     // [slots][sl.out_stride], entry for entry beside sl.out_tokens
 };
 
 // one bit of a seen bitmap, from any number of workgroups at once (duplicates are the norm).  Spelled with the compiler's builtin so that the same
@@ -337,9 +341,55 @@ NTTS_D int sample_topk_row(const bf16_t* row, int V, int k, float temperature, f
     return result;
 }
 
+// The row's n_part (max, sum of exp(v - max)) pairs -> sum of exp(v - M) over the whole row, M = the row's maximum (block-uniform, from the argmax
+// reduction).  The walk is the argmax's: kU requests in flight, branch-free (an index past the end re-reads the last pair and counts it 0 times).
+// A partial whose maximum is -inf holds sum 0 and exp(-inf - M) = 0; a row without one finite logit (M = -inf) returns 0 without forming an exponent.
+// Every thread returns the total.  ss: 4 floats of LDS.  The order of the additions depends on n_part alone: a request's values do not depend on its slot
+NTTS_D float lse_merge_row(const float* pv, const float* ps, int n_part, float M, float* ss) {
+    const int tid = threadIdx.x;
+    constexpr int kU = 8;
+    float S = 0.f;
+    if (M > -INFINITY) {
+        for (int i0 = tid; i0 < n_part; i0 += 256 * kU) {
+            float v[kU], q[kU];
+#pragma unroll
+            for (int u = 0; u < kU; ++u) {
+                const int i = i0 + u * 256 < n_part ? i0 + u * 256 : n_part - 1;
+                v[u] = pv[i];
+                q[u] = ps[i];
+            }
+#pragma unroll
+            for (int u = 0; u < kU; ++u) S += (i0 + u * 256 < n_part ? q[u] : 0.f) * fexp(v[u] - M);
+        }
+    }
+#pragma unroll
+    for (int sh = 1; sh < 64; sh <<= 1) S += shfl_xor(S, sh);
+    if (lane_id() == 0) ss[wave_id()] = S;
+    sync();
+    return (ss[0] + ss[1]) + (ss[2] + ss[3]);
+}
+// (kapi.cpp ntts_k_head_logprob_probe: the merge on the partials of a probe launch; out[2 b] = M, out[2 b + 1] = log S)
+NTTS_KERNEL(256) void lse_merge_probe_kernel(const float* part_val, const float* part_sum, int n_part, float* out) {
+    NTTS_SHARED float sv[4];
+    NTTS_SHARED float ss[4];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const float* pv = part_val + (long)b * n_part;
+    float best = -INFINITY;
+    for (int i = tid; i < n_part; i += 256) best = pv[i] > best ? pv[i] : best;
+#pragma unroll
+    for (int sh = 1; sh < 64; sh <<= 1) { const float ov = shfl_xor(best, sh); best = ov > best ? ov : best; }
+    if (lane_id() == 0) sv[wave_id()] = best;
+    sync();
+    float M = sv[0];
+    for (int w = 1; w < 4; ++w) M = sv[w] > M ? sv[w] : M;
+    const float S = lse_merge_row(pv, part_sum + (long)b * n_part, n_part, M, ss);
+    if (tid == 0) { out[2 * b] = M; out[2 * b + 1] = logf(S); }
+}
+
 NTTS_KERNEL(256) void sample_greedy_kernel(SampleArgs p) {
     NTTS_SHARED float sv[4];
     NTTS_SHARED int si[4];
+    NTTS_SHARED float ss[4];
     const int b = blockIdx.x, tid = threadIdx.x;
     float best = -INFINITY;
     int bidx = 0x7fffffff;
@@ -379,12 +429,23 @@ NTTS_KERNEL(256) void sample_greedy_kernel(SampleArgs p) {
         sampled = sample_topk_row(p.logits + (long)b * p.ld_logits, p.vocab, k, p.sl.temperature[b], p.sl.top_p[b], p.sl.min_p[b],
                                   p.sl.seed[2 * b], p.sl.seed[2 * b + 1], (unsigned int)step, pv, p.n_part, p.part_width);
     }
+    const bool lse = live && p.part_sum && p.out_logprobs;      // block-uniform
+    float M = -INFINITY, S = 0.f;
+    if (lse) {
+        for (int w = 0; w < 4; ++w) M = sv[w] > M ? sv[w] : M;
+        S = lse_merge_row(pv, p.part_sum + (long)b * p.n_part, p.n_part, M, ss);
+    }
     if (tid == 0) {
         for (int w = 1; w < 4; ++w)
             if (sv[w] > best || (sv[w] == best && si[w] < bidx)) { best = sv[w]; bidx = si[w]; }
         SlotArrays& s = p.sl;
         if (live) {
             int tok = k > 0 ? sampled : bidx;
+            if (lse) {   // log softmax of the whole processed row at the chosen COLUMN: a greedy row's logit is M itself, a drawn one's is in the bf16 row
+                const float vt = (k > 0 && (unsigned int)tok < (unsigned int)p.vocab) ? bf2f(p.logits[(long)b * p.ld_logits + tok]) : M;
+                const int n0 = (p.phase == SLOT_PREFILLED) ? 0 : s.n_new[b];
+                p.out_logprobs[(long)b * s.out_stride + n0] = (vt - M) - logf(S);
+            }
             // (a COLUMN: before the compacted head's id mapping; a row without one finite logit yields no index -- nothing to mark)
             if (p.seen && s.rep_pen[b] != 1.0f && (unsigned int)tok < (unsigned int)p.vocab) seen_mark(p.seen + (long)b * p.seen_pitch, tok);
             if (p.n_range > 0) tok = tok < p.n_range ? tok + p.id_base : p.id_tail;
@@ -532,12 +593,15 @@ struct ActivateArgs {
     int max_pages;
     unsigned int* seen;      // seen bitmap (null: none allocated): the row moves with the request
     long seen_pitch;
+    float* out_logprobs;     // [slots][sl.out_stride] log-probability record (null: ntts_backbone_set_logprobs is off)
 };
 NTTS_KERNEL(64) void activate_slots_kernel(ActivateArgs p) {
     const int src = p.pairs[2 * blockIdx.x], dst = p.pairs[2 * blockIdx.x + 1];
     const int lane = threadIdx.x;
     const int nn = p.sl.n_new[src];
     for (int k = lane; k < nn; k += 64) p.sl.out_tokens[(long)dst * p.sl.out_stride + k] = p.sl.out_tokens[(long)src * p.sl.out_stride + k];
+    if (p.out_logprobs)      // (the first token's log-probability moves with it)
+        for (int k = lane; k < nn; k += 64) p.out_logprobs[(long)dst * p.sl.out_stride + k] = p.out_logprobs[(long)src * p.sl.out_stride + k];
     for (int k = lane; k < p.max_pages; k += 64) p.block_table[(long)dst * p.max_pages + k] = p.block_table[(long)src * p.max_pages + k];
     if (p.seen)              // (an unpenalised request's row is all zeros: it replaces whatever the decode slot's last occupant left)
         for (long k = lane; k < p.seen_pitch; k += 64) p.seen[(long)dst * p.seen_pitch + k] = p.seen[(long)src * p.seen_pitch + k];

@@ -141,6 +141,9 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "ntts_backbone_set_debug": (C.c_int, [p, i32]),
         "ntts_backbone_read_logits": (C.c_int, [p, i32, C.POINTER(f32), i32]),
         "ntts_backbone_read_seen": (C.c_int, [p, i32, C.POINTER(C.c_uint32), i32]),
+        "ntts_backbone_set_logprobs": (C.c_int, [p, i32]),
+        "ntts_backbone_read_logprobs": (C.c_int, [p, i32, C.POINTER(f32), i32, C.POINTER(i32)]),
+        "ntts_backbone_read_finished_logprobs": (C.c_int, [p, i32, C.POINTER(f32), i32, C.POINTER(i32)]),
         "ntts_backbone_debug_force": (C.c_int, [p, i32, i32]),
         "ntts_backbone_last_timing": (C.c_int, [p, C.POINTER(f32), C.POINTER(f32)]),
         "ntts_backbone_step_bytes": (C.c_int, [p, C.POINTER(C.c_double)]),
@@ -179,6 +182,9 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "ntts_k_head_penalty_probe": (C.c_int, [p, p, i32, i32, i32, i32, i32, f32, C.POINTER(C.c_uint32), C.POINTER(f32), C.POINTER(i32),
                                                 C.POINTER(f32), C.POINTER(C.c_uint16), C.POINTER(f32), C.POINTER(i32), i32, C.POINTER(i32),
                                                 C.POINTER(i32)]),
+        "ntts_k_head_logprob_probe": (C.c_int, [p, p, i32, i32, i32, i32, i32, f32, C.POINTER(C.c_uint32), C.POINTER(f32), C.POINTER(i32),
+                                                C.POINTER(f32), C.POINTER(C.c_uint16), C.POINTER(f32), C.POINTER(i32), C.POINTER(f32), i32,
+                                                C.POINTER(i32), C.POINTER(i32), C.POINTER(f32)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError here == header/library drift: fail loudly
@@ -257,7 +263,7 @@ HEAD_VARIANTS = {"64x64": 0, "128x128": 1, "256x256": 2, "256x288": 4, "gemv": 8
 
 
 def head_penalty_probe(lib, x_ptr: int, w_ptr: int, M: int, N: int, K: int, variant: int, seen=None, rep_pen=None, mask_eos=None,
-                       fp8: bool = False, xscale: float = 1.0):
+                       fp8: bool = False, xscale: float = 1.0, _lse: bool = False):
     """ntts_k_head_penalty_probe: the engine's lm_head launch of tile `variant` (HEAD_VARIANTS) on DEVICE bf16 X [M][K] and W [N][K] (row-major; the
     probe packs W as the engine packs the head).  seen: None (the plain lm_head) or a bool / 0-1 array [M][N] of seen columns; rep_pen: [M]
     penalties; mask_eos: [M] column + 1 to mask, 0 = none.  Returns (logits fp32 [M][N], bf16 row bit patterns uint16 [M][N],
@@ -277,16 +283,32 @@ def head_penalty_probe(lib, x_ptr: int, w_ptr: int, M: int, N: int, K: int, vari
     pi = np.zeros((M, cap), dtype=np.int32)
     n_part, width = C.c_int32(), C.c_int32()
     i32p, f32p = C.POINTER(C.c_int32), C.POINTER(C.c_float)
-    rc = lib.ntts_k_head_penalty_probe(C.c_void_p(x_ptr), C.c_void_p(w_ptr), M, N, K, variant, int(fp8), xscale,
-                                       None if words is None else words.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                       None if pen is None else pen.ctypes.data_as(f32p), None if me is None else me.ctypes.data_as(i32p),
-                                       logits.ctypes.data_as(f32p), row16.ctypes.data_as(C.POINTER(C.c_uint16)), pv.ctypes.data_as(f32p),
-                                       pi.ctypes.data_as(i32p), cap, C.byref(n_part), C.byref(width))
+    head = (C.c_void_p(x_ptr), C.c_void_p(w_ptr), M, N, K, variant, int(fp8), xscale,
+            None if words is None else words.ctypes.data_as(C.POINTER(C.c_uint32)),
+            None if pen is None else pen.ctypes.data_as(f32p), None if me is None else me.ctypes.data_as(i32p),
+            logits.ctypes.data_as(f32p), row16.ctypes.data_as(C.POINTER(C.c_uint16)), pv.ctypes.data_as(f32p), pi.ctypes.data_as(i32p))
+    if _lse:
+        ps = np.zeros((M, cap), dtype=np.float32)
+        row_lse = np.zeros((M, 2), dtype=np.float32)
+        rc = lib.ntts_k_head_logprob_probe(*head, ps.ctypes.data_as(f32p), cap, C.byref(n_part), C.byref(width), row_lse.ctypes.data_as(f32p))
+    else:
+        rc = lib.ntts_k_head_penalty_probe(*head, cap, C.byref(n_part), C.byref(width))
     if rc != 0:
-        raise NeuTTSHipError(rc, "ntts_k_head_penalty_probe")
+        raise NeuTTSHipError(rc, "ntts_k_head_logprob_probe" if _lse else "ntts_k_head_penalty_probe")
     n = n_part.value
     # (the library wrote rows of n_part entries back to back)
-    return logits, row16, pv.reshape(-1)[: M * n].reshape(M, n).copy(), pi.reshape(-1)[: M * n].reshape(M, n).copy(), width.value
+    out = (logits, row16, pv.reshape(-1)[: M * n].reshape(M, n).copy(), pi.reshape(-1)[: M * n].reshape(M, n).copy(), width.value)
+    if _lse:
+        out += (ps.reshape(-1)[: M * n].reshape(M, n).copy(), row_lse[:, 0].copy(), row_lse[:, 1].copy())
+    return out
+
+
+def head_logprob_probe(lib, x_ptr: int, w_ptr: int, M: int, N: int, K: int, variant: int, seen=None, rep_pen=None, mask_eos=None,
+                       fp8: bool = False, xscale: float = 1.0):
+    """ntts_k_head_logprob_probe: head_penalty_probe's launch with the log-sum-exp epilogue (the lm_head kernels of an engine whose set_logprobs is on).
+    Returns head_penalty_probe's five values, then part_sum [M][n_part] (sum over the partial's columns of exp(v - its maximum); 0 where that is -inf)
+    and per row M (the row maximum) and log S as the sampling kernel's own merge computes them: logsumexp(row) = M + log S."""
+    return head_penalty_probe(lib, x_ptr, w_ptr, M, N, K, variant, seen, rep_pen, mask_eos, fp8, xscale, _lse=True)
 
 
 class BackboneEngine:
@@ -321,6 +343,7 @@ class BackboneEngine:
         self.vocab_size = c.vocab_size
         self._free: List[int] = list(range(self.max_batch - 1, -1, -1))   # host-side pool of decode slots (pop -> slot 0 first)
         self.counters = {"decode_steps": 0, "prefill_calls": 0, "prefill_prompts": 0, "prefill_tokens": 0}   # diagnostics (bench.py)
+        self.logprobs = False                             # set_logprobs
 
     # -- decode-slot pool: every path that admits a request (generate, the streaming generators) draws from here, so an
     #    unfinished stream and a later call can never be handed the same slot
@@ -417,6 +440,8 @@ class BackboneEngine:
             t.adopt_arena()
         if getattr(self, "logits_range", None):
             t.set_logits_range(*self.logits_range)          # (an opt-in restricted lm_head goes along: its own compacted copy)
+        if self.logprobs:
+            t.set_logprobs(True)                            # (the switch is per engine)
         return t
 
     # -- requests
@@ -486,6 +511,26 @@ class BackboneEngine:
         n = C.c_int32()
         self._chk(self.lib.ntts_backbone_read_finished(self.h, slot, out.ctypes.data_as(C.POINTER(C.c_int32)), len(out), C.byref(n)))
         return out[: n.value].tolist()
+
+    def set_logprobs(self, enable: bool = True):
+        """Per-token log-probabilities on / off for this engine (ntts_backbone_set_logprobs; include/neutts_hip.h has the definition): while on, every
+        request records log softmax(processed logits row)[token] beside each id.  NTTS_ESTATE while a slot or parking row is in use."""
+        self._chk(self.lib.ntts_backbone_set_logprobs(self.h, int(bool(enable))))
+        self.logprobs = bool(enable)
+
+    def read_logprobs(self, slot: int) -> np.ndarray:
+        """The log-probabilities of the ids read(slot) returns, entry for entry (blocking).  NTTS_ESTATE while set_logprobs is off."""
+        out = np.empty(self.max_context, dtype=np.float32)
+        n = C.c_int32()
+        self._chk(self.lib.ntts_backbone_read_logprobs(self.h, slot, out.ctypes.data_as(C.POINTER(C.c_float)), len(out), C.byref(n)))
+        return out[: n.value].copy()
+
+    def read_finished_logprobs(self, slot: int) -> np.ndarray:
+        """read_logprobs for a slot the last completed snapshot showed finished -- copied past the decode steps still queued, like read_finished."""
+        out = np.empty(self.max_context, dtype=np.float32)
+        n = C.c_int32()
+        self._chk(self.lib.ntts_backbone_read_finished_logprobs(self.h, slot, out.ctypes.data_as(C.POINTER(C.c_float)), len(out), C.byref(n)))
+        return out[: n.value].copy()
 
     def read_all_array(self):
         """Every slot's new ids in one call, as arrays: (ids [max_batch, max_context] int32 -- row s valid up to n[s]),
@@ -677,9 +722,11 @@ class BackboneEngine:
     # -- continuous batching (host scheduler): keep every slot busy until all prompts are done
     def generate(self, prompts: Sequence[Sequence[int]], sampling, steps_per_poll: int = 16,
                  prefill_token_budget: Optional[int] = None, share_prefix: bool = False, min_admit: int = 1,
-                 on_finished=None, run_ahead: bool = True, admit_gate=None, on_admit=None) -> List[List[int]]:
+                 on_finished=None, run_ahead: bool = True, admit_gate=None, on_admit=None, return_logprobs: bool = False) -> List[List[int]]:
         """Batched equivalent of calling ref:neutts/neutts.py:338-351 once per prompt.
         Returns the NEW ids of each prompt (prompt stripped), in order.
+        return_logprobs=True (needs set_logprobs(True)): returns (ids, logprobs) -- one float32 array per prompt, entry for entry beside its ids,
+        read before the slot is released (also when on_finished is set).
         share_prefix=True: a prompt that starts like one already in flight (same speaker: chat header + reference
         text, ref:neutts/neutts.py:307,315-325) re-uses that slot's KV pages for the common whole pages.
         min_admit: waiting prompts are admitted only once that many slots are free (or nothing is running): a prompt pass over
@@ -698,7 +745,7 @@ class BackboneEngine:
         its engines' admissions (a prompt pass takes an engine's lane for ~ 0.8 us per prompt token; with nothing running the gate
         is not asked)."""
         it = self.generate_iter(prompts, sampling, steps_per_poll, prefill_token_budget, share_prefix, min_admit, on_finished, run_ahead,
-                                admit_gate, on_admit)
+                                admit_gate, on_admit, return_logprobs)
         while True:
             try:
                 next(it)
@@ -707,12 +754,14 @@ class BackboneEngine:
 
     def generate_iter(self, prompts: Sequence[Sequence[int]], sampling, steps_per_poll: int = 16,
                       prefill_token_budget: Optional[int] = None, share_prefix: bool = False, min_admit: int = 1,
-                      on_finished=None, run_ahead: bool = True, admit_gate=None, on_admit=None):
+                      on_finished=None, run_ahead: bool = True, admit_gate=None, on_admit=None, return_logprobs: bool = False):
         """generate() as a generator: yields (None) once per scheduler iteration -- after this engine's next burst and snapshot
         are enqueued -- and returns generate()'s result as the StopIteration value.  What EngineGang alternates between: while one
         engine's scheduler waits for its previous snapshot, the other engines' bursts are already queued on their own streams."""
         if isinstance(sampling, Sampling):
             sampling = [sampling] * len(prompts)
+        if return_logprobs and not self.logprobs:
+            raise NeuTTSHipError(-4, "return_logprobs: log-probabilities are not recorded, call set_logprobs(True) first")
         budget = prefill_token_budget or self.cfg.get("max_prefill_tokens", 0) or 16384
         # validate up front: a request that cannot run must not strand the ones admitted before it
         for i, (p, sp) in enumerate(zip(prompts, sampling)):
@@ -738,6 +787,7 @@ class BackboneEngine:
                 raise NeuTTSHipError(-3, f"prompt {i}: max_length {sampling[i].max_length} needs {n} KV pages, the pool has {total_pages} free of {pool_pages}")
         committed: Dict[int, int] = {}                      # slot -> pages reserved for it
         results: List[Optional[List[int]]] = [None] * len(prompts)
+        logps: List[Optional[np.ndarray]] = [None] * len(prompts)
         owner: Dict[int, int] = {}
         anchors: List[tuple] = []       # (slot, prompt as int32 array) of live slots that later prompts are compared with
         arrs = [np.asarray(p, dtype=np.int32) for p in prompts] if share_prefix else None
@@ -890,6 +940,8 @@ class BackboneEngine:
                 if st is not None:
                     for s in [s for s in list(owner) if s < self.max_batch and valid_from.get(s, 0) <= q and st[s] == 2]:
                         i = owner.pop(s)
+                        if return_logprobs:
+                            logps[i] = self.read_finished_logprobs(s) if run_ahead else self.read_logprobs(s)
                         if on_finished is not None:
                             on_finished(i, s, int(nn[s]))
                             results[i] = []
@@ -926,7 +978,10 @@ class BackboneEngine:
                         self.release(s)
                     except NeuTTSHipError:
                         pass
-        return [r if r is not None else [] for r in results]
+        ids = [r if r is not None else [] for r in results]
+        if return_logprobs:
+            return ids, [lp if lp is not None else np.zeros(0, dtype=np.float32) for lp in logps]
+        return ids
 
 
 class EngineGang:
@@ -992,13 +1047,14 @@ class EngineGang:
             e.warm_up(decode_steps)
 
     def generate(self, prompts: Sequence[Sequence[int]], sampling, on_finished=None, steps_per_poll: int = 1, admit: str = "wave",
-                 on_admit=None, **kw) -> List[List[int]]:
+                 on_admit=None, return_logprobs: bool = False, **kw) -> List[List[int]]:
         """BackboneEngine.generate over the gang: request i goes to engine i % n (prompts of one speaker that follow each other n apart
         still share their prefix pages inside an engine), the engines' schedulers advance in turn.  Bursts of `steps_per_poll` = 1 step
         by default: the engines' bursts are enqueued in turn, and the shorter the turn the closer their chains run side by side (8192
         ragged requests, round 4: 144.5 k codec-tokens/s at 1-2 steps, 132.0 k at 4, 106.7 k at 8, profiles/r04s_sweep_continuous_gang_sched.txt;
         round 5 with admission waves: 149.8 k at 1, 146.3-147.0 k at 2).  on_finished(request index, slot, n_new, engine) -- the engine is
-        passed along for the device-side hand-off.  Returns the new ids in request order.
+        passed along for the device-side hand-off.  Returns the new ids in request order; with return_logprobs=True (every engine's set_logprobs
+        on) the pair (ids, logprobs), as BackboneEngine.generate does.
         admit: how the engines' prompt passes are placed against each other once `min_admit` > 1 (a pass holds its engine's lane for
         ~ 0.8 us per prompt token while the other chains go on).  "wave[:F[:W]]" (default) -- when one engine admits `min_admit`
         prompts, the others admit within W rounds (default 1) with min_admit / F (default a third) of their slots free: all prompt
@@ -1051,8 +1107,9 @@ class EngineGang:
                     if on_admit is not None:
                         on_admit(_e, n_prompts)
             its.append((idx, e.generate_iter([prompts[i] for i in idx], [sampling[i] for i in idx], steps_per_poll=steps_per_poll, on_finished=hook,
-                                             on_admit=note, **kw)))
+                                             on_admit=note, return_logprobs=return_logprobs, **kw)))
         results: List[List[int]] = [[] for _ in prompts]
+        logps: List[np.ndarray] = [np.zeros(0, dtype=np.float32) for _ in prompts]
         try:
             while its:
                 sched["round"] += 1
@@ -1061,13 +1118,16 @@ class EngineGang:
                     try:
                         next(it)
                     except StopIteration as done:
-                        for i, r in zip(idx, done.value):
-                            results[i] = r
+                        ids, lps = done.value if return_logprobs else (done.value, None)
+                        for k, i in enumerate(idx):
+                            results[i] = ids[k]
+                            if lps is not None:
+                                logps[i] = lps[k]
                         its.remove(item)
         finally:
             for _, it in its:
                 it.close()                                # an exception in one engine: the others release their slots (generate_iter's finally)
-        return results
+        return (results, logps) if return_logprobs else results
 
     def sync(self):
         for e in self.engines:

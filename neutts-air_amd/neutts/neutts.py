@@ -176,6 +176,21 @@ def _check_repetition(repetition_penalty, repetition_ignore_prompt, who: str = "
         raise ValueError(f"{who}repetition_ignore_prompt must be True or False (got {repetition_ignore_prompt!r})")
 
 
+def _check_best_of(best_of, do_sample: bool, who: str = "") -> None:
+    """best_of: a plain integer >= 1; more than one candidate needs sampling (greedy candidates are all the same).  ValueError before anything
+    reaches the engine."""
+    if isinstance(best_of, (bool, np.bool_)) or not isinstance(best_of, (int, np.integer)) or best_of < 1:
+        raise ValueError(f"{who}best_of must be an integer >= 1 (got {best_of!r})")
+    if best_of > 1 and not do_sample:
+        raise ValueError(f"{who}best_of = {best_of} needs do_sample=True: greedy candidates are identical")
+
+
+def sequence_score(logprobs) -> float:
+    """A candidate's score: the arithmetic mean of its per-token log-probabilities (-inf for an empty one)."""
+    lp = np.asarray(logprobs, dtype=np.float64)
+    return float(lp.mean()) if lp.size else float("-inf")
+
+
 class NeuTTS:
 
     def __init__(
@@ -196,6 +211,8 @@ class NeuTTS:
         min_p: float = 0.0,
         repetition_penalty: float = 1.0,
         repetition_ignore_prompt: bool = False,
+        logprobs: bool = False,
+        best_of: int = 1,
         speech_range_head: bool = False,
         codec_precision: str = "fp16",
     ):
@@ -223,6 +240,15 @@ class NeuTTS:
         # reference codec tokens.  Both have per-call overrides too.
         _check_sampling(top_k, temperature, top_p, min_p)
         _check_repetition(repetition_penalty, repetition_ignore_prompt)
+        # logprobs=True keeps the engines' per-token log-probability record on (BackboneEngine.set_logprobs: log softmax of the processed logits row
+        # at every chosen token, reduced inside the lm_head); an instance built without it switches it on for the calls that ask for scores and off
+        # again.  best_of=N draws N candidates per utterance (one generate call, shared prompt pages) and keeps the one whose mean log-probability
+        # is highest; return_logprobs= / return_scores= / best_of= per call on generate_codes / infer / infer_batch.
+        if not isinstance(logprobs, (bool, np.bool_)):
+            raise ValueError(f"logprobs must be True or False (got {logprobs!r})")
+        _check_best_of(best_of, do_sample)
+        self.logprobs = bool(logprobs)
+        self.best_of = int(best_of)
         self.repetition_penalty = repetition_penalty
         self.repetition_ignore_prompt = repetition_ignore_prompt
         self.do_sample = do_sample
@@ -255,6 +281,9 @@ class NeuTTS:
                 raise RuntimeError("speech_range_head needs the ids of <|speech_0|> and <|SPEECH_GENERATION_END|> (tokenizer, or 'speech_base' / 'eos_token_id' with in-memory weights)")
             self.backbone.set_logits_range(int(self._speech_base), int(self._speech_base) + 65536, int(self._eos_id))
         self.gang = _hip.EngineGang(self.backbone, engines) if engines > 1 else None
+        if self.logprobs:
+            for eng in self._backbone_engines():
+                eng.set_logprobs(True)
 
         try:  # optional watermarker, as the reference (ref:neutts/neutts.py:110-121)
             import perth
@@ -394,28 +423,35 @@ class NeuTTS:
     def infer(self, text: str, ref_codes, ref_text: str, *, temperature=None, top_k=None, top_p=None, min_p=None, **repetition) -> np.ndarray:
         """Generate speech for `text` in the voice of the encoded reference (ref:neutts/neutts.py:216-243).  temperature / top_k / top_p /
         min_p override the instance's sampling attributes for this call (None = the attribute), and so do the two further keywords every entry
-        point takes behind them: repetition_penalty= and repetition_ignore_prompt= (anything else is a TypeError)."""
+        point takes behind them: repetition_penalty= and repetition_ignore_prompt= (anything else is a TypeError).
+        best_of=N: N sampled candidates, the one with the highest mean log-probability is synthesised; return_scores=True: (wav, score)."""
+        best_of, want = self._pop_scoring(1, repetition, "return_scores")
         samp = self._resolve_sampling(1, temperature, top_k, top_p, min_p, repetition)
         prompt_ids = self._apply_chat_template(ref_codes, ref_text, text)
-        new_ids = self._generate([prompt_ids], samp)[0]
-        wav = self._decode_ids(new_ids)
-        return wav if self.watermarker is None else self.watermarker.apply_watermark(wav, sample_rate=24_000)
+        ids, lps = self._generate_scored([prompt_ids], samp, best_of, want)
+        wav = self._decode_ids(ids[0])
+        if self.watermarker is not None:
+            wav = self.watermarker.apply_watermark(wav, sample_rate=24_000)
+        return (wav, sequence_score(lps[0])) if want else wav
 
     def infer_batch(self, texts: Sequence[str], ref_codes, ref_texts, *, temperature=None, top_k=None, top_p=None, min_p=None, **repetition) -> List[np.ndarray]:
         """Many utterances at once: continuous batching over the engine's decode slots (over every engine's, with engines > 1),
-        one codec pass.  The sampling overrides take one value for the call or one per utterance."""
+        one codec pass.  The sampling overrides take one value for the call or one per utterance, and so does best_of= (candidates per
+        utterance; only the winners go through the codec); return_scores=True: (wavs, scores), score = mean log-probability of the ids."""
+        best_of, want = self._pop_scoring(len(texts), repetition, "return_scores")
         samp = self._resolve_sampling(len(texts), temperature, top_k, top_p, min_p, repetition)
         if not isinstance(ref_texts, (list, tuple)):
             ref_texts = [ref_texts] * len(texts)
             ref_codes = [ref_codes] * len(texts)
         prompts = [self._apply_chat_template(rc, rt, t) for rc, rt, t in zip(ref_codes, ref_texts, texts)]
-        codes = [self._ids_to_codes(ids) for ids in self._generate(prompts, samp)]
+        ids, lps = self._generate_scored(prompts, samp, best_of, want)
+        codes = [self._ids_to_codes(x) for x in ids]
         if any(len(c) == 0 for c in codes):
             raise ValueError("No valid speech tokens found in the output.")
         wavs = self.codec.engine.decode(codes)
         if self.watermarker is not None:
             wavs = [self.watermarker.apply_watermark(w, sample_rate=24_000) for w in wavs]
-        return wavs
+        return (wavs, [sequence_score(lp) for lp in lps]) if want else wavs
 
     def infer_stream(self, text: str, ref_codes, ref_text: str, *, temperature=None, top_k=None, top_p=None, min_p=None, **repetition) -> Generator[np.ndarray, None, None]:
         """Streaming synthesis with the reference's window / cross-fade semantics (ref:neutts/neutts.py:373-465).  Sampling overrides as `infer`
@@ -481,11 +517,14 @@ class NeuTTS:
             _check_repetition(pen, ign, f"utterance {i}: " if n > 1 else "")
         return [(int(k), float(t), float(tp), float(mp), float(pen), bool(ign)) for k, t, tp, mp, pen, ign in out]
 
+    def _request_seed(self, index: int) -> int:
+        # one Philox key per request: (call counter, index within the call)
+        return (self._seed * 0x9E3779B97F4A7C15 + index * 0xD1B54A32D192ED03 + 1) & 0xFFFFFFFFFFFFFFFF
+
     def _sampling(self, prompt_len: int, index: int = 0, samp: Optional[Sequence[tuple]] = None) -> _hip.Sampling:
         if self._eos_id is None:
             raise RuntimeError("eos token id unknown: supply 'eos_token_id' with in-memory weights")
-        # one Philox key per request: (call counter, index within the call)
-        seed = (self._seed * 0x9E3779B97F4A7C15 + index * 0xD1B54A32D192ED03 + 1) & 0xFFFFFFFFFFFFFFFF
+        seed = self._request_seed(index)
         top_k, temperature, top_p, min_p, pen, ign = samp[index] if samp is not None else (
             self.top_k, self.temperature, self.top_p, self.min_p, self.repetition_penalty, self.repetition_ignore_prompt)
         return _hip.Sampling(max_length=self.max_context, min_new_tokens=self.min_new_tokens, eos_token_id=self._eos_id,
@@ -494,14 +533,81 @@ class NeuTTS:
 
     def generate_codes(self, prompts: Sequence[Sequence[int]], *, temperature=None, top_k=None, top_p=None, min_p=None, **repetition) -> List[List[int]]:
         """Batched equivalent of `_infer_torch` (ref:neutts/neutts.py:334-352): new token ids per prompt.  The sampling overrides take one
-        value for the call or one per prompt."""
-        return self._generate(prompts, self._resolve_sampling(len(prompts), temperature, top_k, top_p, min_p, repetition))
+        value for the call or one per prompt.  return_logprobs=True: (ids, logprobs), one float32 array per prompt beside its ids (the model's own
+        log-probability of each token over the whole processed logits row: include/neutts_hip.h); best_of=N: the best of N candidates per prompt."""
+        best_of, want = self._pop_scoring(len(prompts), repetition, "return_logprobs")
+        samp = self._resolve_sampling(len(prompts), temperature, top_k, top_p, min_p, repetition)
+        ids, lps = self._generate_scored(prompts, samp, best_of, want)
+        return (ids, lps) if want else ids
 
-    def _generate(self, prompts: Sequence[Sequence[int]], samp: Sequence[tuple]) -> List[List[int]]:
+    def _pop_scoring(self, n: int, kw: dict, flag: str):
+        """The scoring keywords of an entry point's catch-all, taken out ahead of _resolve_sampling: best_of (one value or one per utterance;
+        None = the attribute) and the entry point's own flag.  -> ([best_of per utterance], flag).  ValueError on a bad value."""
+        want = kw.pop(flag, False)
+        if not isinstance(want, (bool, np.bool_)):
+            raise ValueError(f"{flag} must be True or False (got {want!r})")
+        v = kw.pop("best_of", None)
+        if isinstance(v, (list, tuple, np.ndarray)):
+            v = list(v)
+            if len(v) != n:
+                raise ValueError(f"best_of: {len(v)} values for {n} utterances")
+            v = [self.best_of if x is None else x for x in v]
+        else:
+            v = [self.best_of if v is None else v] * n
+        for i, b in enumerate(v):
+            _check_best_of(b, self.do_sample, f"utterance {i}: " if n > 1 else "")
+        return [int(b) for b in v], bool(want)
+
+    def _backbone_engines(self):
+        return list(self.gang.engines) if self.gang is not None else [self.backbone]
+
+    def _generate_scored(self, prompts, samp, best_of: Sequence[int], want: bool):
+        """_generate with candidates and scores: utterance i is submitted best_of[i] times in ONE generate call (request index i * N + j with N the
+        call's largest best_of, so every candidate has a seed of its own; the copies share the prompt's KV pages through prefix sharing) and the
+        candidate with at least one speech token and the highest mean log-probability wins, ties to the lowest j.  -> (ids, logprobs) of the
+        winners; logprobs is None unless scores were needed."""
+        if not want and all(b == 1 for b in best_of):
+            return self._generate(prompts, samp), None
+        engines = self._backbone_engines()
+        turned_on = [e for e in engines if not e.logprobs]
+        if any(e.free_slots() != e.max_batch for e in turned_on):
+            raise RuntimeError("log-probabilities cannot be switched on while a suspended stream holds a decode slot: finish or close the stream, "
+                               "or build the instance with logprobs=True")
+        N = max(best_of) if len(best_of) else 1
+        rows, index, cand_prompts, cand_samp = [], [], [], []
+        for i, p in enumerate(prompts):
+            for j in range(best_of[i]):
+                rows.append(i)
+                index.append(i * N + j)
+                cand_prompts.append(p)
+                cand_samp.append(samp[i])
+        try:
+            for e in turned_on:
+                e.set_logprobs(True)
+            ids, lps = self._generate(cand_prompts, cand_samp, index=index, return_logprobs=True)
+        finally:
+            for e in turned_on:
+                if e.logprobs:
+                    e.set_logprobs(False)
+        out_ids, out_lps = [None] * len(prompts), [None] * len(prompts)
+        best = [None] * len(prompts)
+        for r, i in enumerate(rows):
+            score = sequence_score(lps[r]) if (best_of[i] == 1 or len(self._ids_to_codes(ids[r])) > 0) else float("-inf")
+            if best[i] is None or score > best[i]:
+                best[i], out_ids[i], out_lps[i] = score, ids[r], lps[r]
+        return out_ids, out_lps
+
+    def _generate(self, prompts: Sequence[Sequence[int]], samp: Sequence[tuple], index: Optional[Sequence[int]] = None,
+                  return_logprobs: bool = False) -> List[List[int]]:
+        """index: the request index each prompt's seed is derived from (default: its position); samp is indexed by position either way."""
         self._seed += 1
         # utterances of one speaker start with the same tokens (chat header + reference-text phones, ref :307,:315-325):
         # the engine keeps one copy of those KV pages and computes only what differs
         sampling = [self._sampling(len(p), i, samp) for i, p in enumerate(prompts)]
+        if index is not None:
+            for sp, k in zip(sampling, index):
+                sp.seed = self._request_seed(k)
+        kw = dict(return_logprobs=True) if return_logprobs else {}
         # more utterances than decode slots: freed slots are refilled about a tenth of an engine's slots at a time (24 of 256) -- a prompt
         # pass over a handful of prompts costs 1.5-2 us per token against 0.84 for 32 and more, an idle slot a step each
         # (profiles/r05m_probe_prefill_size.txt); scheduling only, the ids do not depend on it
@@ -509,8 +615,8 @@ class NeuTTS:
         slots = eng_slots * (len(self.gang.engines) if self.gang is not None else 1)
         min_admit = max(1, min(24, eng_slots // 10)) if len(prompts) > slots else 1
         if self.gang is not None and len(prompts) > 1:
-            return self.gang.generate(prompts, sampling, share_prefix=True, min_admit=min_admit)
-        return self.backbone.generate(prompts, sampling, share_prefix=len(prompts) > 1, min_admit=min_admit)
+            return self.gang.generate(prompts, sampling, share_prefix=True, min_admit=min_admit, **kw)
+        return self.backbone.generate(prompts, sampling, share_prefix=len(prompts) > 1, min_admit=min_admit, **kw)
 
     def _ids_to_codes(self, ids: Sequence[int]) -> List[int]:
         """ref :349 (tokenizer.decode) + :276 (regex): keep `<|speech_N|>` tokens, N = id - id(<|speech_0|>)."""
