@@ -603,6 +603,44 @@ int ntts_k_head_logprob_probe(const void* X_dev, const void* W_dev, int32_t M, i
                               float* part_val, int32_t* part_idx, float* part_sum, int32_t part_cap, int32_t* n_part, int32_t* part_width,
                               float* row_lse);
 
+/* Paged-attention probes (parity tests against tests/attention_spec.py; no ABI bump).  The KV page layout they read and write, per layer:
+ *   K   [page][kv_head][32 tokens][head_dim]          token t of a page in row t
+ *   V^T [page][kv_head][head_dim][32 token slots]     token t of a page in slot ((t & 15) >> 2) * 8 + (t >> 4) * 4 + (t & 3)
+ * block_table_dev = DEVICE int32 [rows][max_pages] page numbers; EVERY entry must name a page of the pool (0 <= entry < num_pages: checked),
+ * because the kernels may request any entry of a row ahead of knowing the context length.
+ *
+ * ntts_k_attn_decode_form: the decode-attention instantiation ("form") the engine's launchers pick for a decode batch -- 0 = 8 waves, 4 workgroups
+ * per (sequence, kv-head); 1 = 8 waves, 2 workgroups; 2 = 8 waves; 3 / 4 = 4 waves with non-temporal page loads, 1024 / 2048 score rows; 5 / 6 = 4
+ * waves, 1024 / 2048 score rows; 7 / 8 = head_dim 128, 1024 / 2048 score rows (form 9 = the context-split path, which the engine switches on by
+ * itself and this function never returns).  Pure host arithmetic. */
+int ntts_k_attn_decode_form(int32_t batch, int32_t nkv, int32_t max_ctx, int32_t nt_pages, int32_t head_dim);
+/* One decode-attention launch of `form` through the engine's own launcher.  qkv_dev = DEVICE bf16 [batch][ld_qkv] rows q heads (ALREADY rotated) | k
+ * heads (ignored: the K entry of this step is already in its page) | v heads (raw; the kernel places them in the V^T page of position pos[b]).
+ * out_dev = [batch][nh * head_dim] bf16, or e4m3 bytes = bf16 result * out_fp8_inv when out_fp8_inv > 0.  pos_dev / state_dev = DEVICE int32 [batch]
+ * (tokens already cached, 0 <= pos < max_ctx: checked; 1 = running, other rows are left untouched).  max_ctx <= 1024 for forms 3, 5, 7, <= 2048 else,
+ * and max_pages * 32 >= max_ctx.  form 9: nsplit = chunks per (sequence, kv-head), 2 .. 64 (head_dim 64, bf16 out); the probe allocates the score /
+ * statistics / slab scratch itself, fills it with 0xFF bytes (NaN) and runs scores, PV and combine; slabs_out_dev (may be NULL) receives the fp32
+ * chunk slabs [nsplit][batch][nh * 64].  Other forms: nsplit = 0, slabs_out_dev = NULL.  xcd_rows = 0, or xps in {1, 2, 4, 8} with batch = 512 / xps
+ * (workgroup x takes row xcd_row(x, xps)). */
+int ntts_k_attn_decode_probe(const void* qkv_dev, int64_t ld_qkv, void* out_dev, float out_fp8_inv, void* kpool_dev, void* vpool_dev,
+                             int32_t num_pages, const int32_t* block_table_dev, int32_t max_pages, const int32_t* pos_dev,
+                             const int32_t* state_dev, int32_t batch, int32_t nh, int32_t nkv, int32_t head_dim, int32_t max_ctx,
+                             int32_t form, int32_t nsplit, int32_t xcd_rows, float* slabs_out_dev);
+/* What one layer of ntts_backbone_prefill does between the QKV GEMM and o_proj: the RoPE / KV-page writer, then causal attention over the pages by the
+ * two-sweep, resident and deep kernels over the engine's own work lists.  qkv_dev = DEVICE bf16 [T][ld_qkv] packed RAW q | k | v rows of n prompts
+ * (prompt i: rows of positions pos0[i] .. lens[i] - 1; HOST arrays lens = total context after the pass, pos0 = tokens already in the pages, a
+ * multiple of 32, slots = block-table row, 0 <= slot < bt_rows).  rope_cos_dev / rope_sin_dev = DEVICE bf16 [max_ctx][head_dim / 2].  head_dim 128, or
+ * q_norm_dev / k_norm_dev (DEVICE bf16 [head_dim], may be NULL) given: the generic writer (per-head RMSNorm with eps, RoPE; q rows rotated IN PLACE)
+ * and the two-sweep kernel alone; else the head_dim-64 writer (k, v only) and attention kernels that rotate q as they load it.  res_cap / deep_cap:
+ * queries below res_cap take the resident kernel, below deep_cap the deep one, clamped as ntts_backbone_create clamps NTTS_PF_RES_CAP / NTTS_PF_DEEP_CAP
+ * (whole pages, at most 512 / 1024, deep >= res).  only_last != 0: the last layer's work lists (only the block that holds each prompt's last position
+ * is computed; other rows of out_dev are left untouched).  out_dev as in the decode probe, [T][nh * head_dim]. */
+int ntts_k_attn_prefill_probe(void* qkv_dev, int64_t ld_qkv, void* out_dev, float out_fp8_inv, void* kpool_dev, void* vpool_dev,
+                              int32_t num_pages, const int32_t* block_table_dev, int32_t bt_rows, int32_t max_pages, int32_t n,
+                              const int32_t* lens, const int32_t* pos0, const int32_t* slots, int32_t nh, int32_t nkv, int32_t head_dim,
+                              const void* rope_cos_dev, const void* rope_sin_dev, int32_t max_ctx, const void* q_norm_dev,
+                              const void* k_norm_dev, float eps, int32_t res_cap, int32_t deep_cap, int32_t only_last);
+
 #ifdef __cplusplus
 }
 #endif

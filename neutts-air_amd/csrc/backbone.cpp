@@ -514,11 +514,7 @@ extern "C" int ntts_backbone_create(const ntts_backbone_config* c, int device, n
     if (e->wide && e->wide_down == 1 && !e->fp8 && env_int("NTTS_KS_D", 0) <= 0) e->ks_d = 4;   // 8 x 7 tiles of 128 x 128 x 4 K slices = 224 workgroups
     e->xl_min_m = env_int("NTTS_XL_MIN_M", 0);
     {   // 0 = every query on the two-sweep kernel; whole pages, at most what the resident kernel holds
-        int cap = env_int("NTTS_PF_RES_CAP", kPfResPages * kPage) / kPage * kPage;
-        e->pf_res_cap = cap < 0 ? 0 : cap > kPfResPages * kPage ? kPfResPages * kPage : cap;
-        int dcap = env_int("NTTS_PF_DEEP_CAP", kPfDeepPages * kPage) / kPage * kPage;
-        dcap = dcap > kPfDeepPages * kPage ? kPfDeepPages * kPage : dcap;
-        e->pf_deep_cap = dcap < e->pf_res_cap ? e->pf_res_cap : dcap;
+        prefill_clamp_caps(env_int("NTTS_PF_RES_CAP", kPfResPages * kPage), env_int("NTTS_PF_DEEP_CAP", kPfDeepPages * kPage), &e->pf_res_cap, &e->pf_deep_cap);
         if (e->generic) e->pf_res_cap = e->pf_deep_cap = 0;     // every query on the (head_dim-templated) two-sweep kernel
     }
     e->xcd_xps = (D == 64 || D == 128 || D == 256 || D == 512) ? 8 / (D / 64) : 0;
@@ -1655,45 +1651,16 @@ static int prefill_impl(ntts_backbone* e, int32_t n, const int32_t* ids, const i
     }
     // ---- meta block: [ids T][tok_seq T][tok_base n][seq_len n][slot n][min_new n][max_len n][eos n][last_row n]
     //                  [tile_seq nt][tile_q0 nt][bt_rows n*max_pages]
-    std::vector<int> tile_seq, tile_q0, rtile_seq, rtile_q0, rtile_key, dtile_seq, dtile_q0, dtile_key;
+    // (the attention work lists -- three tiers by position, deepest first, and the last layer's -- are built by attn_prefill.h prefill_work_lists)
+    const PrefillWorkLists wl = prefill_work_lists(n, lens, pos0.data(), e->pf_res_cap, e->pf_deep_cap);
+    const std::vector<int>&tile_seq = wl.tile_seq, &tile_q0 = wl.tile_q0, &rtile_seq = wl.rtile_seq, &rtile_q0 = wl.rtile_q0, &dtile_seq = wl.dtile_seq, &dtile_q0 = wl.dtile_q0;
     std::vector<int> m;
     m.reserve(2 * T + 16 * n);
     for (int i = 0; i < n; ++i) m.insert(m.end(), ids + id_off[i] + pos0[i], ids + id_off[i] + lens[i]);   // packed: new tokens only
     const size_t o_tok_seq = m.size();
-    for (int i = 0; i < n; ++i) m.insert(m.end(), lens[i] - pos0[i], i);
+    m.insert(m.end(), wl.tok_seq.begin(), wl.tok_seq.end());
     const size_t o_base = m.size();
-    long acc = 0;
-    for (int i = 0; i < n; ++i) {
-        m.push_back((int)acc);
-        // attention work lists, split by POSITION into three tiers (attn_prefill.h): queries below pf_res_cap (512) go to the resident kernel, those
-        // below pf_deep_cap (1024) to the deep one -- both take work items (prompt, k) of 256 queries whose 16-query blocks the kernel deals out from
-        // both ends of the tier -- the rest to the two-sweep kernel in 64-query tiles.  Which kernel computes a query depends on nothing but its position
-        const int cap = e->pf_res_cap, dcap = e->pf_deep_cap;
-        auto items = [&](int lo, int hi, std::vector<int>& seq, std::vector<int>& q0, std::vector<int>& key) {
-            const int b0 = pos0[i] > lo ? pos0[i] : lo, a_end = lens[i] < hi ? lens[i] : hi;
-            if (a_end <= b0) return;
-            const int nb = (a_end - b0 + 15) / 16, nwg = (nb + 15) / 16;
-            for (int k = 0; k < nwg; ++k) { seq.push_back(i); q0.push_back(k); key.push_back(nb); }
-        };
-        items(0, cap, rtile_seq, rtile_q0, rtile_key);
-        items(cap, dcap, dtile_seq, dtile_q0, dtile_key);
-        for (int q = pos0[i] > dcap ? pos0[i] : dcap; q < lens[i]; q += 64) { tile_seq.push_back(i); tile_q0.push_back(q); }
-        acc += lens[i] - pos0[i];
-    }
-    // Causal attention: a 64-query tile that starts at position q0 sweeps (q0 + 64) / 32 KV pages, 2 .. 16 for a 500-token
-    // prompt.  In prompt order the LAST workgroups dispatched are the deepest tiles of the last prompt and the pass ends on
-    // them; sorted by descending depth (stable: ties keep prompt order) the shallow tiles fill the tail instead.
-    auto deepest_first = [](std::vector<int>& seq, std::vector<int>& q0, const std::vector<int>& key) {
-        std::vector<int> ord(seq.size());
-        for (size_t k = 0; k < ord.size(); ++k) ord[k] = (int)k;
-        std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) { return key[a] > key[b]; });
-        std::vector<int> ts(ord.size()), tq(ord.size());
-        for (size_t k = 0; k < ord.size(); ++k) { ts[k] = seq[ord[k]]; tq[k] = q0[ord[k]]; }
-        seq.swap(ts); q0.swap(tq);
-    };
-    deepest_first(tile_seq, tile_q0, std::vector<int>(tile_q0));
-    deepest_first(rtile_seq, rtile_q0, rtile_key);   // (the work items of one prompt weigh the same: longest prompts first)
-    deepest_first(dtile_seq, dtile_q0, dtile_key);
+    m.insert(m.end(), wl.tok_base.begin(), wl.tok_base.end());
     const size_t o_len = m.size();   m.insert(m.end(), lens, lens + n);
     const size_t o_pos0 = m.size();  m.insert(m.end(), pos0.begin(), pos0.end());
     const size_t o_slot = m.size();  m.insert(m.end(), slots, slots + n);
@@ -1728,29 +1695,14 @@ static int prefill_impl(ntts_backbone* e, int32_t n, const int32_t* ids, const i
     m.push_back((int)mark_cols.size());
     const size_t o_seed = m.size();
     for (int i = 0; i < n; ++i) { m.push_back((int)(uint32_t)samp[i].seed); m.push_back((int)(uint32_t)(samp[i].seed >> 32)); }
-    const size_t o_last = m.size();
-    acc = 0;
-    for (int i = 0; i < n; ++i) { acc += lens[i] - pos0[i]; m.push_back((int)acc - 1); }
+    const size_t o_last = m.size();  m.insert(m.end(), wl.last_row.begin(), wl.last_row.end());
     const size_t o_tseq = m.size();  m.insert(m.end(), tile_seq.begin(), tile_seq.end());
     const size_t o_tq0 = m.size();   m.insert(m.end(), tile_q0.begin(), tile_q0.end());
     const size_t o_rtseq = m.size(); m.insert(m.end(), rtile_seq.begin(), rtile_seq.end());
     const size_t o_rtq0 = m.size();  m.insert(m.end(), rtile_q0.begin(), rtile_q0.end());
     const size_t o_dtseq = m.size(); m.insert(m.end(), dtile_seq.begin(), dtile_seq.end());
     const size_t o_dtq0 = m.size();  m.insert(m.end(), dtile_q0.begin(), dtile_q0.end());
-    // work lists of the LAST layer's attention: the one tile / work item per prompt that holds its last position (same split by position)
-    std::vector<int> lt_seq, lt_q0, lrt_seq, lrt_q0, ldt_seq, ldt_q0;
-    for (int i = 0; i < n; ++i) {
-        const int last = lens[i] - 1, cap = e->pf_res_cap, dcap = e->pf_deep_cap;
-        // the work item that holds a tier's last 16-query block: blocks below nbp / 2 are "lo" blocks of item b / 8, the others "hi" blocks
-        auto last_item = [&](int lo, int hi) {
-            const int b0 = pos0[i] > lo ? pos0[i] : lo, a_end = lens[i] < hi ? lens[i] : hi;
-            const int nb = (a_end - b0 + 15) / 16, nbp = (nb + 15) / 16 * 16, b = nb - 1;
-            return b < nbp / 2 ? b / 8 : (nbp - 1 - b) / 8;
-        };
-        if (last < cap) { lrt_seq.push_back(i); lrt_q0.push_back(last_item(0, cap)); }
-        else if (last < dcap) { ldt_seq.push_back(i); ldt_q0.push_back(last_item(cap, dcap)); }
-        else { const int b0 = pos0[i] > dcap ? pos0[i] : dcap; lt_seq.push_back(i); lt_q0.push_back(b0 + (last - b0) / 64 * 64); }
-    }
+    const std::vector<int>&lt_seq = wl.lt_seq, &lt_q0 = wl.lt_q0, &lrt_seq = wl.lrt_seq, &lrt_q0 = wl.lrt_q0, &ldt_seq = wl.ldt_seq, &ldt_q0 = wl.ldt_q0;
     const size_t o_ltseq = m.size();  m.insert(m.end(), lt_seq.begin(), lt_seq.end());
     const size_t o_ltq0 = m.size();   m.insert(m.end(), lt_q0.begin(), lt_q0.end());
     const size_t o_lrtseq = m.size(); m.insert(m.end(), lrt_seq.begin(), lrt_seq.end());

@@ -3,6 +3,7 @@
 #include <ntts/dev.h>
 
 #include "../../include/neutts_hip.h"
+#include "kernels/attn_prefill.h"
 #include "kernels/gemm.h"
 #include "kernels/gemv.h"
 #include "kernels/norm.h"
@@ -543,4 +544,139 @@ extern "C" int ntts_k_head_logprob_probe(const void* X_dev, const void* W_dev, i
     if (!part_sum || !row_lse) return NTTS_EINVAL;
     return head_probe(X_dev, W_dev, M, N, K, variant, fp8, xscale, seen, rep_pen, mask_eos, logits_out, logits_bf16_out, part_val, part_idx, part_cap,
                       n_part, part_width, part_sum, row_lse);
+}
+
+// ---- attention probes: the decode launch of one form and one layer's prompt-pass attention (writer + the three tiers over the engine's own work
+//      lists) on caller-supplied pools and block tables, against tests/attention_spec.py.  Argument structs and launches only: the instantiations,
+//      grids and work lists are attn_decode.h's / attn_prefill.h's own (attn_decode_launch_form, prefill_work_lists), the ones the engine calls.
+extern "C" int ntts_k_attn_decode_form(int32_t batch, int32_t nkv, int32_t max_ctx, int32_t nt_pages, int32_t head_dim) {
+    if (batch < 1 || nkv < 1 || max_ctx < 1 || (head_dim != 64 && head_dim != 128)) return NTTS_EINVAL;
+    return attn_decode_form(batch, nkv, max_ctx, nt_pages, head_dim);
+}
+
+namespace {
+struct DevBuf { void* p = nullptr; ~DevBuf() { if (p) (void)hipFree(p); } };
+// every block-table entry names a page of the pool (the kernels may request any entry of a row, used or not)
+bool block_table_ok(const int32_t* bt_dev, long entries, int num_pages) {
+    std::vector<int> bt((size_t)entries);
+    if (hipMemcpy(bt.data(), bt_dev, (size_t)entries * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return false;
+    for (long i = 0; i < entries; ++i)
+        if (bt[i] < 0 || bt[i] >= num_pages) return false;
+    return true;
+}
+}  // namespace
+
+extern "C" int ntts_k_attn_decode_probe(const void* qkv_dev, int64_t ld_qkv, void* out_dev, float out_fp8_inv, void* kpool_dev, void* vpool_dev,
+                                        int32_t num_pages, const int32_t* block_table_dev, int32_t max_pages, const int32_t* pos_dev,
+                                        const int32_t* state_dev, int32_t batch, int32_t nh, int32_t nkv, int32_t head_dim, int32_t max_ctx,
+                                        int32_t form, int32_t nsplit, int32_t xcd_rows, float* slabs_out_dev) {
+    if (!qkv_dev || !out_dev || !kpool_dev || !vpool_dev || !block_table_dev || !pos_dev || !state_dev) return NTTS_EINVAL;
+    if (batch < 1 || nh < 1 || nkv < 1 || (nh % nkv) || nh / nkv > kGroupMax || num_pages < 1 || max_pages < 1) return NTTS_EINVAL;
+    if (form < 0 || form >= kAttnFormCount) return NTTS_EINVAL;
+    const bool hd128 = form == kAttnFormHD128_1024 || form == kAttnFormHD128_2048;
+    const bool lmax1024 = form == kAttnFormNT1024 || form == kAttnFormW4_1024 || form == kAttnFormHD128_1024;
+    if (head_dim != (hd128 ? 128 : 64)) return NTTS_EINVAL;
+    if (max_ctx < 1 || max_ctx > (lmax1024 ? 1024 : kAttnLMax) || (long)max_pages * kPage < max_ctx) return NTTS_EINVAL;
+    if (ld_qkv < (long)(nh + 2 * nkv) * head_dim || (ld_qkv % 8) || ((uintptr_t)qkv_dev & 15)) return NTTS_EINVAL;
+    if (xcd_rows && (form == kAttnFormSplit || hd128 || (xcd_rows != 1 && xcd_rows != 2 && xcd_rows != 4 && xcd_rows != 8) || batch != 512 / xcd_rows)) return NTTS_EINVAL;
+    if (form == kAttnFormSplit ? (nsplit < 2 || nsplit > 64 || out_fp8_inv > 0.f) : (nsplit != 0 || slabs_out_dev)) return NTTS_EINVAL;
+    {   // positions inside the context, pages inside the pool
+        std::vector<int> pos(batch);
+        if (hipMemcpy(pos.data(), pos_dev, (size_t)batch * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return NTTS_EHIP;
+        for (int b = 0; b < batch; ++b)
+            if (pos[b] < 0 || pos[b] >= max_ctx) return NTTS_EINVAL;
+        if (!block_table_ok(block_table_dev, (long)batch * max_pages, num_pages)) return NTTS_EINVAL;
+    }
+    AttnDecodeArgs a{};
+    a.qkv = (const bf16_t*)qkv_dev; a.ld_qkv = ld_qkv; a.out = (bf16_t*)out_dev; a.ld_out = (long)nh * head_dim; a.out_fp8_inv = out_fp8_inv;
+    a.kpool = (bf16_t*)kpool_dev; a.vpool = (bf16_t*)vpool_dev; a.block_table = block_table_dev; a.max_pages = max_pages;
+    a.pos = pos_dev; a.state = state_dev; a.nh = nh; a.nkv = nkv;
+    a.xcd_rows = xcd_rows;
+    a.nt_pages = form == kAttnFormNT1024 || form == kAttnFormNT2048;
+    const hipStream_t st = (hipStream_t)0;
+    if (form != kAttnFormSplit) {
+        attn_decode_launch_form(a, batch, st, form);
+        return hipDeviceSynchronize() == hipSuccess && hipGetLastError() == hipSuccess ? NTTS_OK : NTTS_EHIP;
+    }
+    // context-split with the combine pass (the tile path's form); the scratch is the probe's own, NaN-filled: a slab or a statistic that a kernel
+    // should have written and did not reaches the output
+    AttnSplitArgs q{};
+    q.a = a; q.a.slab_rows = batch; q.ld_scores = max_ctx + 16; q.nsplit = nsplit;
+    const size_t n_sc = (size_t)batch * nkv * kGroupMax * q.ld_scores * sizeof(bf16_t), n_st = (size_t)batch * nkv * nsplit * kGroupMax * 2 * sizeof(float),
+                 n_os = (size_t)nsplit * batch * a.ld_out * sizeof(float);
+    DevBuf sc, stt, os;
+    if (hipMalloc(&sc.p, n_sc) != hipSuccess || hipMalloc(&stt.p, n_st) != hipSuccess || hipMalloc(&os.p, n_os) != hipSuccess) return NTTS_ENOMEM;
+    if (hipMemset(sc.p, 0xFF, n_sc) != hipSuccess || hipMemset(stt.p, 0xFF, n_st) != hipSuccess || hipMemset(os.p, 0xFF, n_os) != hipSuccess) return NTTS_EHIP;
+    q.scores = (bf16_t*)sc.p; q.stats = (float*)stt.p; q.oslabs = (float*)os.p;
+    attn_split_launch(q, batch, st, true);
+    if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess) return NTTS_EHIP;
+    if (slabs_out_dev && hipMemcpy(slabs_out_dev, os.p, n_os, hipMemcpyDeviceToDevice) != hipSuccess) return NTTS_EHIP;
+    return NTTS_OK;
+}
+
+extern "C" int ntts_k_attn_prefill_probe(void* qkv_dev, int64_t ld_qkv, void* out_dev, float out_fp8_inv, void* kpool_dev, void* vpool_dev,
+                                         int32_t num_pages, const int32_t* block_table_dev, int32_t bt_rows, int32_t max_pages, int32_t n,
+                                         const int32_t* lens, const int32_t* pos0, const int32_t* slots, int32_t nh, int32_t nkv, int32_t head_dim,
+                                         const void* rope_cos_dev, const void* rope_sin_dev, int32_t max_ctx, const void* q_norm_dev,
+                                         const void* k_norm_dev, float eps, int32_t res_cap, int32_t deep_cap, int32_t only_last) {
+    if (!qkv_dev || !out_dev || !kpool_dev || !vpool_dev || !block_table_dev || !lens || !pos0 || !slots || !rope_cos_dev || !rope_sin_dev) return NTTS_EINVAL;
+    if (n < 1 || nh < 1 || nkv < 1 || (nh % nkv) || nh / nkv > kGroupMax || num_pages < 1 || bt_rows < 1 || max_pages < 1) return NTTS_EINVAL;
+    if ((head_dim != 64 && head_dim != 128) || max_ctx < 1 || (long)max_pages * kPage < max_ctx) return NTTS_EINVAL;
+    if (ld_qkv < (long)(nh + 2 * nkv) * head_dim || (ld_qkv % 8) || ((uintptr_t)qkv_dev & 15)) return NTTS_EINVAL;
+    if (((uintptr_t)rope_cos_dev & 15) || ((uintptr_t)rope_sin_dev & 15)) return NTTS_EINVAL;
+    long T = 0;
+    for (int i = 0; i < n; ++i) {
+        if (pos0[i] < 0 || (pos0[i] % kPage) || lens[i] <= pos0[i] || lens[i] > max_ctx || slots[i] < 0 || slots[i] >= bt_rows) return NTTS_EINVAL;
+        T += lens[i] - pos0[i];
+    }
+    if (T > 0x7fffffffL / (long)ld_qkv) return NTTS_EINVAL;
+    if (!block_table_ok(block_table_dev, (long)bt_rows * max_pages, num_pages)) return NTTS_EINVAL;
+    const bool generic = head_dim == 128 || q_norm_dev || k_norm_dev;   // (ntts_backbone_create: head_dim 128 and / or qk-norm)
+    int cap = 0, dcap = 0;
+    prefill_clamp_caps(res_cap, deep_cap, &cap, &dcap);
+    if (generic) cap = dcap = 0;                                        // every query on the (head_dim-templated) two-sweep kernel
+    const PrefillWorkLists wl = prefill_work_lists(n, lens, pos0, cap, dcap);
+    std::vector<int> m;
+    auto put = [&](const std::vector<int>& v) { const size_t o = m.size(); m.insert(m.end(), v.begin(), v.end()); return o; };
+    const size_t o_tok_seq = put(wl.tok_seq), o_base = put(wl.tok_base), o_len = put(std::vector<int>(lens, lens + n)),
+                 o_pos0 = put(std::vector<int>(pos0, pos0 + n)), o_slot = put(std::vector<int>(slots, slots + n));
+    const bool prune = only_last != 0;
+    const size_t o_tseq = put(prune ? wl.lt_seq : wl.tile_seq), o_tq0 = put(prune ? wl.lt_q0 : wl.tile_q0);
+    const size_t o_rtseq = put(prune ? wl.lrt_seq : wl.rtile_seq), o_rtq0 = put(prune ? wl.lrt_q0 : wl.rtile_q0);
+    const size_t o_dtseq = put(prune ? wl.ldt_seq : wl.dtile_seq), o_dtq0 = put(prune ? wl.ldt_q0 : wl.dtile_q0);
+    const int n_tiles = (int)(prune ? wl.lt_seq : wl.tile_seq).size(), n_rtiles = (int)(prune ? wl.lrt_seq : wl.rtile_seq).size(),
+              n_dtiles = (int)(prune ? wl.ldt_seq : wl.dtile_seq).size();
+    DevBuf mb;
+    if (hipMalloc(&mb.p, m.size() * sizeof(int)) != hipSuccess) return NTTS_ENOMEM;
+    if (hipMemcpy(mb.p, m.data(), m.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) return NTTS_EHIP;
+    const int* md = (const int*)mb.p;
+    const PrefillMeta meta{md + o_base, md + o_len, md + o_pos0, md + o_slot, md + o_tok_seq, md + o_tseq, md + o_tq0};
+    const hipStream_t st = (hipStream_t)0;
+    const int Ti = (int)T;
+    if (generic) {   // q AND k normalised + rotated by the writer (q in place), v scattered
+        RopeNormArgs g{};
+        g.qkv = (bf16_t*)qkv_dev; g.ld_qkv = ld_qkv; g.kpool = (bf16_t*)kpool_dev; g.vpool = (bf16_t*)vpool_dev; g.block_table = block_table_dev;
+        g.max_pages = max_pages; g.meta = meta; g.rope_cos = (const bf16_t*)rope_cos_dev; g.rope_sin = (const bf16_t*)rope_sin_dev;
+        g.q_norm = (const bf16_t*)q_norm_dev; g.k_norm = (const bf16_t*)k_norm_dev; g.eps = eps; g.nh = nh; g.nkv = nkv; g.rows = Ti; g.write_v = 1;
+        const long items = (long)Ti * (nh + 2 * nkv);
+        if (head_dim == 128) NTTS_LAUNCH((rope_norm_kv_write_kernel<128>), dim3((unsigned)((items + 3) / 4)), dim3(256), st, g);
+        else NTTS_LAUNCH((rope_norm_kv_write_kernel<64>), dim3((unsigned)((items + 3) / 4)), dim3(256), st, g);
+    } else {         // k rotated into its page, v scattered; the attention kernels rotate q as they load it
+        RopeWriteArgs r{};
+        r.qkv = (bf16_t*)qkv_dev; r.ld_qkv = ld_qkv; r.kpool = (bf16_t*)kpool_dev; r.vpool = (bf16_t*)vpool_dev; r.block_table = block_table_dev;
+        r.max_pages = max_pages; r.meta = meta; r.rope_cos = (const bf16_t*)rope_cos_dev; r.rope_sin = (const bf16_t*)rope_sin_dev;
+        r.nh = nh; r.nkv = nkv; r.T = Ti; r.skip_q = 1;
+        NTTS_LAUNCH((rope_kv_write_vec_kernel), dim3((Ti + kRopeTokPerBlock - 1) / kRopeTokPerBlock), dim3(256), st, r);
+    }
+    AttnPrefillArgs a{};
+    a.qkv = (const bf16_t*)qkv_dev; a.ld_qkv = ld_qkv; a.out = (bf16_t*)out_dev; a.ld_out = (long)nh * head_dim; a.out_fp8_inv = out_fp8_inv;
+    a.kpool = (const bf16_t*)kpool_dev; a.vpool = (const bf16_t*)vpool_dev; a.block_table = block_table_dev; a.max_pages = max_pages;
+    a.meta = meta; a.nh = nh; a.nkv = nkv;
+    if (!generic) { a.rope_cos = (const bf16_t*)rope_cos_dev; a.rope_sin = (const bf16_t*)rope_sin_dev; }
+    if (n_tiles) { if (head_dim == 128) attn_prefill_launch_hd128(a, n_tiles, st); else attn_prefill_launch(a, n_tiles, st); }
+    a.meta.tile_seq = md + o_rtseq; a.meta.tile_q0 = md + o_rtq0;
+    if (n_rtiles) attn_prefill_res_launch(a, n_rtiles, cap, prune, st);
+    a.meta.tile_seq = md + o_dtseq; a.meta.tile_q0 = md + o_dtq0;
+    if (n_dtiles) attn_prefill_deep_launch(a, n_dtiles, cap, dcap, prune, st);
+    return hipDeviceSynchronize() == hipSuccess && hipGetLastError() == hipSuccess ? NTTS_OK : NTTS_EHIP;
 }

@@ -526,43 +526,68 @@ inline void attn_split_launch(const AttnSplitArgs& q, int batch, hipStream_t s, 
     if (combine) NTTS_LAUNCH((attn_split_combine_kernel), dim3(batch), block, s, q);
 }
 
+// ---- The product instantiations by name.  attn_decode_form is the choice the three launchers below make, as a pure host function, and
+// attn_decode_launch_form the one place a product instantiation is launched from: the engine and the parity probe (kapi.cpp
+// ntts_k_attn_decode_probe) go through both, so a probe can never run a kernel or a grid the engine does not.
+enum AttnDecodeForm {
+    kAttnFormDS4 = 0,          // 8 waves, V^T requested next to K, four workgroups per (sequence, kv-head) with 16 output dimensions each
+    kAttnFormDS2 = 1,          // ... two workgroups, 32 dimensions each
+    kAttnFormW8 = 2,           // 8 waves, one workgroup per (sequence, kv-head)
+    kAttnFormNT1024 = 3,       // 4 waves, non-temporal page loads, 1024 score rows
+    kAttnFormNT2048 = 4,       // ... 2048 score rows
+    kAttnFormW4_1024 = 5,      // 4 waves, 1024 score rows
+    kAttnFormW4_2048 = 6,      // 4 waves, 2048 score rows
+    kAttnFormHD128_1024 = 7,   // head_dim 128, 4 waves, 1024 score rows
+    kAttnFormHD128_2048 = 8,   // ... 2048 score rows
+    kAttnFormSplit = 9,        // context-split (attn_split_launch); never returned by attn_decode_form: the engine turns it on by itself
+    kAttnFormCount = 10
+};
 // large batch (tile path): one KV page per wave in flight, V^T pages requested after the score pass; engines with
 // max_context <= 1024 take the instantiation with half the score rows
-inline void attn_decode_launch(const AttnDecodeArgs& p, int batch, hipStream_t s, int max_ctx) {
-    const dim3 grid(batch, p.nkv), block(256);
+inline int attn_decode_form(int batch, int nkv, int max_ctx, int nt_pages, int head_dim) {
+    // head_dim 128 (round 6; the generic attention geometry): one instantiation per score-row length, 4 waves, one page per wave in flight
+    if (head_dim == 128) return max_ctx <= 1024 ? kAttnFormHD128_1024 : kAttnFormHD128_2048;
     // Few sequences (at most 256 workgroups after the split: batch 9 .. 32 with 2 kv-heads): the small-batch form -- 8 waves, V^T requested next to K,
     // four workgroups per (sequence, kv-head) with 16 output dimensions each (DS = 4).  Batch 16 / 32: 11.5 / 11.8 -> 8.1 / 8.4 us per launch, step
     // 1.212 / 1.259 -> 1.129 / 1.177 ms; from 512 workgroups on (batch 64) it is equal, at batch 128 twice as slow (one sweep, one box).
-    if (!p.tl && batch * p.nkv * 4 <= 256) {
-        NTTS_LAUNCH((attn_decode_kernel<1, false, 5, 8, kAttnLMax, 4>), dim3(batch, p.nkv, 4), dim3(512), s, p);
-        return;
-    }
-    if (!p.tl && batch * p.nkv * 2 <= 256) {           // up to 256 workgroups with TWO per (sequence, kv-head), 32 dimensions each: batch 40 / 48 / 64
-        NTTS_LAUNCH((attn_decode_kernel<1, false, 5, 8, kAttnLMax, 2>), dim3(batch, p.nkv, 2), dim3(512), s, p);   // step 1.263 / 1.277 / 1.304 -> 1.191 / 1.203 / 1.236 ms;
-        return;                                                                                                 // batch 96 (384 workgroups): no gain, not used
-    }
-    if (!p.tl && batch * p.nkv <= 256) {               // at most one workgroup per CU: 8 waves (batch 96 / 128: 13.1 / 14.0 -> 10.3 / 11.6 us, step 1.322 / 1.384 ->
-        NTTS_LAUNCH((attn_decode_kernel<1, false, 1, 8, kAttnLMax, 1>), grid, dim3(512), s, p);   // 1.269 / 1.345 ms; batch 192 / 256, two per CU: equal or slower)
-        return;
-    }
-    if (p.tl) NTTS_LAUNCH((attn_decode_kernel<1, true, 1, 4, kAttnLMax>), grid, block, s, p);   // diagnostics: phase timestamps
-    else if (max_ctx <= 1024 && p.nt_pages) NTTS_LAUNCH((attn_decode_kernel<1, false, 3, 4, 1024>), grid, block, s, p);
-    else if (p.nt_pages) NTTS_LAUNCH((attn_decode_kernel<1, false, 3, 4, kAttnLMax>), grid, block, s, p);
-    else if (max_ctx <= 1024) NTTS_LAUNCH((attn_decode_kernel<1, false, 1, 4, 1024>), grid, block, s, p);
-    else NTTS_LAUNCH((attn_decode_kernel<1, false, 1, 4, kAttnLMax>), grid, block, s, p);
+    if (batch * nkv * 4 <= 256) return kAttnFormDS4;
+    // up to 256 workgroups with TWO per (sequence, kv-head), 32 dimensions each: batch 40 / 48 / 64: step 1.263 / 1.277 / 1.304 -> 1.191 / 1.203 / 1.236 ms;
+    // batch 96 (384 workgroups): no gain, not used
+    if (batch * nkv * 2 <= 256) return kAttnFormDS2;
+    // at most one workgroup per CU: 8 waves (batch 96 / 128: 13.1 / 14.0 -> 10.3 / 11.6 us, step 1.322 / 1.384 -> 1.269 / 1.345 ms; batch 192 / 256,
+    // two per CU: equal or slower)
+    if (batch * nkv <= 256) return kAttnFormW8;
+    if (max_ctx <= 1024 && nt_pages) return kAttnFormNT1024;
+    if (nt_pages) return kAttnFormNT2048;
+    return max_ctx <= 1024 ? kAttnFormW4_1024 : kAttnFormW4_2048;
 }
-// head_dim 128 (round 6; the generic attention geometry): one instantiation per score-row length, 4 waves, one page per wave in flight
-inline void attn_decode_launch_hd128(const AttnDecodeArgs& p, int batch, hipStream_t s, int max_ctx) {
+inline void attn_decode_launch_form(const AttnDecodeArgs& p, int batch, hipStream_t s, int form) {
     const dim3 grid(batch, p.nkv), block(256);
-    if (max_ctx <= 1024) NTTS_LAUNCH((attn_decode_kernel<1, false, 1, 4, 1024, 1, 128>), grid, block, s, p);
-    else NTTS_LAUNCH((attn_decode_kernel<1, false, 1, 4, kAttnLMax, 1, 128>), grid, block, s, p);
+    switch (form) {
+        case kAttnFormDS4: NTTS_LAUNCH((attn_decode_kernel<1, false, 5, 8, kAttnLMax, 4>), dim3(batch, p.nkv, 4), dim3(512), s, p); break;
+        case kAttnFormDS2: NTTS_LAUNCH((attn_decode_kernel<1, false, 5, 8, kAttnLMax, 2>), dim3(batch, p.nkv, 2), dim3(512), s, p); break;
+        case kAttnFormW8: NTTS_LAUNCH((attn_decode_kernel<1, false, 1, 8, kAttnLMax, 1>), grid, dim3(512), s, p); break;
+        case kAttnFormNT1024: NTTS_LAUNCH((attn_decode_kernel<1, false, 3, 4, 1024>), grid, block, s, p); break;
+        case kAttnFormNT2048: NTTS_LAUNCH((attn_decode_kernel<1, false, 3, 4, kAttnLMax>), grid, block, s, p); break;
+        case kAttnFormW4_1024: NTTS_LAUNCH((attn_decode_kernel<1, false, 1, 4, 1024>), grid, block, s, p); break;
+        case kAttnFormW4_2048: NTTS_LAUNCH((attn_decode_kernel<1, false, 1, 4, kAttnLMax>), grid, block, s, p); break;
+        case kAttnFormHD128_1024: NTTS_LAUNCH((attn_decode_kernel<1, false, 1, 4, 1024, 1, 128>), grid, block, s, p); break;
+        case kAttnFormHD128_2048: NTTS_LAUNCH((attn_decode_kernel<1, false, 1, 4, kAttnLMax, 1, 128>), grid, block, s, p); break;
+        default: break;
+    }
+}
+inline void attn_decode_launch(const AttnDecodeArgs& p, int batch, hipStream_t s, int max_ctx) {
+    if (p.tl) { NTTS_LAUNCH((attn_decode_kernel<1, true, 1, 4, kAttnLMax>), dim3(batch, p.nkv), dim3(256), s, p); return; }   // diagnostics: phase timestamps
+    attn_decode_launch_form(p, batch, s, attn_decode_form(batch, p.nkv, max_ctx, p.nt_pages, 64));
+}
+inline void attn_decode_launch_hd128(const AttnDecodeArgs& p, int batch, hipStream_t s, int max_ctx) {
+    attn_decode_launch_form(p, batch, s, attn_decode_form(batch, p.nkv, max_ctx, p.nt_pages, 128));
 }
 // small batch (gemv.h path): 8 waves, one page each in flight, V^T requested next to K (kVar 5): at batch 1 the kernel is one
 // chain of dependent round trips through ONE CU's load path
 inline void attn_decode_launch_small(const AttnDecodeArgs& p, int batch, hipStream_t s) {
-    const dim3 grid(batch, p.nkv);
-    if (p.tl) NTTS_LAUNCH((attn_decode_kernel<1, true, 5, 8>), grid, dim3(512), s, p);   // diagnostics: phase timestamps (waves 0..3)
-    else NTTS_LAUNCH((attn_decode_kernel<1, false, 5, 8, kAttnLMax, 4>), dim3(batch, p.nkv, 4), dim3(512), s, p);   // four workgroups per (sequence, kv-head): 16 output dimensions each
+    if (p.tl) NTTS_LAUNCH((attn_decode_kernel<1, true, 5, 8>), dim3(batch, p.nkv), dim3(512), s, p);   // diagnostics: phase timestamps (waves 0..3)
+    else attn_decode_launch_form(p, batch, s, kAttnFormDS4);   // four workgroups per (sequence, kv-head): 16 output dimensions each
 }
 
 }  // namespace ntts

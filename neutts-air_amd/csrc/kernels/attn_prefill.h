@@ -9,7 +9,9 @@
 // the rope kernel just wrote (L2/MALL resident), so prefill exercises exactly the layout decode reads.
 #pragma once
 #include <ntts/dev.h>
+#include <algorithm>
 #include <type_traits>
+#include <vector>
 #include "attn_decode.h"
 
 namespace ntts {
@@ -961,6 +963,79 @@ NTTS_KERNEL(512) void attn_prefill_deep_kernel(AttnPrefillArgs p) {
         }
     }
     }
+}
+
+// ---- host side: the work lists of one prompt pass, from the prompts' lengths alone (plain vectors in and out: ntts_backbone_prefill and the parity
+// probe kapi.cpp ntts_k_attn_prefill_probe both call this, so the probe runs the kernels over exactly the lists the engine would build).
+struct PrefillWorkLists {
+    std::vector<int> tok_seq, tok_base, last_row;                                   // PrefillMeta arrays ([T], [n]) and each prompt's last packed row
+    std::vector<int> tile_seq, tile_q0, rtile_seq, rtile_q0, dtile_seq, dtile_q0;   // two-sweep tiles, resident and deep work items (deepest first)
+    std::vector<int> lt_seq, lt_q0, lrt_seq, lrt_q0, ldt_seq, ldt_q0;               // the LAST layer's lists: the one tile / item per prompt that holds its last position
+};
+// lens[i] = total context of prompt i after the pass, pos0[i] = tokens already in its pages; res_cap / deep_cap = the engine's pf_res_cap / pf_deep_cap
+inline PrefillWorkLists prefill_work_lists(int n, const int* lens, const int* pos0, int res_cap, int deep_cap) {
+    PrefillWorkLists w;
+    std::vector<int>&tile_seq = w.tile_seq, &tile_q0 = w.tile_q0, &rtile_seq = w.rtile_seq, &rtile_q0 = w.rtile_q0, &dtile_seq = w.dtile_seq, &dtile_q0 = w.dtile_q0;
+    std::vector<int> rtile_key, dtile_key;
+    for (int i = 0; i < n; ++i) w.tok_seq.insert(w.tok_seq.end(), lens[i] - pos0[i], i);
+    long acc = 0;
+    for (int i = 0; i < n; ++i) {
+        w.tok_base.push_back((int)acc);
+        // attention work lists, split by POSITION into three tiers (attn_prefill.h): queries below pf_res_cap (512) go to the resident kernel, those
+        // below pf_deep_cap (1024) to the deep one -- both take work items (prompt, k) of 256 queries whose 16-query blocks the kernel deals out from
+        // both ends of the tier -- the rest to the two-sweep kernel in 64-query tiles.  Which kernel computes a query depends on nothing but its position
+        const int cap = res_cap, dcap = deep_cap;
+        auto items = [&](int lo, int hi, std::vector<int>& seq, std::vector<int>& q0, std::vector<int>& key) {
+            const int b0 = pos0[i] > lo ? pos0[i] : lo, a_end = lens[i] < hi ? lens[i] : hi;
+            if (a_end <= b0) return;
+            const int nb = (a_end - b0 + 15) / 16, nwg = (nb + 15) / 16;
+            for (int k = 0; k < nwg; ++k) { seq.push_back(i); q0.push_back(k); key.push_back(nb); }
+        };
+        items(0, cap, rtile_seq, rtile_q0, rtile_key);
+        items(cap, dcap, dtile_seq, dtile_q0, dtile_key);
+        for (int q = pos0[i] > dcap ? pos0[i] : dcap; q < lens[i]; q += 64) { tile_seq.push_back(i); tile_q0.push_back(q); }
+        acc += lens[i] - pos0[i];
+    }
+    // Causal attention: a 64-query tile that starts at position q0 sweeps (q0 + 64) / 32 KV pages, 2 .. 16 for a 500-token
+    // prompt.  In prompt order the LAST workgroups dispatched are the deepest tiles of the last prompt and the pass ends on
+    // them; sorted by descending depth (stable: ties keep prompt order) the shallow tiles fill the tail instead.
+    auto deepest_first = [](std::vector<int>& seq, std::vector<int>& q0, const std::vector<int>& key) {
+        std::vector<int> ord(seq.size());
+        for (size_t k = 0; k < ord.size(); ++k) ord[k] = (int)k;
+        std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) { return key[a] > key[b]; });
+        std::vector<int> ts(ord.size()), tq(ord.size());
+        for (size_t k = 0; k < ord.size(); ++k) { ts[k] = seq[ord[k]]; tq[k] = q0[ord[k]]; }
+        seq.swap(ts); q0.swap(tq);
+    };
+    deepest_first(tile_seq, tile_q0, std::vector<int>(tile_q0));
+    deepest_first(rtile_seq, rtile_q0, rtile_key);   // (the work items of one prompt weigh the same: longest prompts first)
+    deepest_first(dtile_seq, dtile_q0, dtile_key);
+    acc = 0;
+    for (int i = 0; i < n; ++i) { acc += lens[i] - pos0[i]; w.last_row.push_back((int)acc - 1); }
+    // work lists of the LAST layer's attention: the one tile / work item per prompt that holds its last position (same split by position)
+    std::vector<int>&lt_seq = w.lt_seq, &lt_q0 = w.lt_q0, &lrt_seq = w.lrt_seq, &lrt_q0 = w.lrt_q0, &ldt_seq = w.ldt_seq, &ldt_q0 = w.ldt_q0;
+    for (int i = 0; i < n; ++i) {
+        const int last = lens[i] - 1, cap = res_cap, dcap = deep_cap;
+        // the work item that holds a tier's last 16-query block: blocks below nbp / 2 are "lo" blocks of item b / 8, the others "hi" blocks
+        auto last_item = [&](int lo, int hi) {
+            const int b0 = pos0[i] > lo ? pos0[i] : lo, a_end = lens[i] < hi ? lens[i] : hi;
+            const int nb = (a_end - b0 + 15) / 16, nbp = (nb + 15) / 16 * 16, b = nb - 1;
+            return b < nbp / 2 ? b / 8 : (nbp - 1 - b) / 8;
+        };
+        if (last < cap) { lrt_seq.push_back(i); lrt_q0.push_back(last_item(0, cap)); }
+        else if (last < dcap) { ldt_seq.push_back(i); ldt_q0.push_back(last_item(cap, dcap)); }
+        else { const int b0 = pos0[i] > dcap ? pos0[i] : dcap; lt_seq.push_back(i); lt_q0.push_back(b0 + (last - b0) / 64 * 64); }
+    }
+    return w;
+}
+// the caps as ntts_backbone_create clamps them: whole pages, at most kPfResPages / kPfDeepPages pages, deep >= res
+inline void prefill_clamp_caps(int res_cap, int deep_cap, int* res_out, int* deep_out) {
+    int cap = res_cap / kPage * kPage;
+    cap = cap < 0 ? 0 : cap > kPfResPages * kPage ? kPfResPages * kPage : cap;
+    int dcap = deep_cap / kPage * kPage;
+    dcap = dcap > kPfDeepPages * kPage ? kPfDeepPages * kPage : dcap;
+    *res_out = cap;
+    *deep_out = dcap < cap ? cap : dcap;
 }
 
 inline void attn_prefill_deep_launch(AttnPrefillArgs p, int n_tiles, int q_lo, int q_cap, bool only_last, hipStream_t s) {

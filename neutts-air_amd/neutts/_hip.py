@@ -185,6 +185,10 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "ntts_k_head_logprob_probe": (C.c_int, [p, p, i32, i32, i32, i32, i32, f32, C.POINTER(C.c_uint32), C.POINTER(f32), C.POINTER(i32),
                                                 C.POINTER(f32), C.POINTER(C.c_uint16), C.POINTER(f32), C.POINTER(i32), C.POINTER(f32), i32,
                                                 C.POINTER(i32), C.POINTER(i32), C.POINTER(f32)]),
+        "ntts_k_attn_decode_form": (C.c_int, [i32, i32, i32, i32, i32]),
+        "ntts_k_attn_decode_probe": (C.c_int, [p, i64, p, f32, p, p, i32, p, i32, p, p, i32, i32, i32, i32, i32, i32, i32, i32, p]),
+        "ntts_k_attn_prefill_probe": (C.c_int, [p, i64, p, f32, p, p, i32, p, i32, i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32),
+                                                i32, i32, i32, p, p, i32, p, p, f32, i32, i32, i32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError here == header/library drift: fail loudly
