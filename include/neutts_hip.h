@@ -335,6 +335,36 @@ int ntts_backbone_set_logprobs(ntts_backbone* e, int32_t enable);
 int ntts_backbone_read_logprobs(ntts_backbone* e, int32_t slot, float* out, int32_t cap, int32_t* n_out);
 /* The same for a slot the last completed snapshot showed FINISHED, on the side copy stream, under the rule of ntts_backbone_read_finished. */
 int ntts_backbone_read_finished_logprobs(ntts_backbone* e, int32_t slot, float* out, int32_t cap, int32_t* n_out);
+/* Teacher-forced scoring of GIVEN sequences.  NEW SYMBOLS ONLY: NTTS_ABI_VERSION stays 11.
+ * DEFINITION.  Sequence i has tokens ids_i[0 .. len_i).  For every j in [score_from_i, len_i), with 1 <= score_from_i < len_i,
+ *     logprob_i[j] = r_{j-1}[ids_i[j]] - logsumexp(r_{j-1})
+ * where r_{j-1} is the bf16-valued lm_head row of position j-1 as the prompt pass computes it, over all V columns.  No processor enters: no
+ * repetition penalty, no MinNewTokens EOS mask, no temperature, no warper -- this is log_softmax(model(ids).logits)[j-1, ids[j]] of transformers, and
+ * what ntts_backbone_read_logprobs records for a request that ran with repetition_penalty = 1 and min_new_tokens = 0, up to the arithmetic difference
+ * between the prompt pass and the decode step.  Per scored position the call also returns argmax[j], the first index of the row maximum (what greedy
+ * decoding would have emitted there), and argmax_logprob[j] = max - logsumexp.  fp32 throughout, within 1e-4 absolute of the float64 value on the
+ * tapped row.
+ * ntts_backbone_score: blocking.  ids = the n sequences back to back, lens[i] tokens each; slots[i] = a FREE slot per sequence -- they and their KV
+ * pages are free again on return, on success and on error alike (ntts_backbone_kv_stats shows the same free-page count before and after).  The prompt
+ * pass runs as for ntts_backbone_prefill, without pruning the last layer and without a first token; the final norm and the lm_head run over the scored
+ * source positions only (score_from_i - 1 .. len_i - 2), in chunks of chunk_rows rows -- 0 = the engine's default, 2048: a chunk streams the head once,
+ * which is ~10 % of its time there, and the partial arrays cost 12 bytes x (V / 96) per chunk row (56 MB at V = 217 488; V / 64 on an fp8 engine); a value above 8192 or above
+ * max_prefill_tokens is taken as the smaller of the two (larger chunks only cost scratch: measured no faster); negative: NTTS_EINVAL.  The [rows][V] logits are
+ * never materialised: the lm_head epilogue keeps (max, first index, sum of exp) partials and the one logit of the given next token.  The scratch is
+ * sized for ONE chunk, allocated by the first call and freed at destroy.  The head tile is the engine's 256-row one (256 x 288 bf16, 256 x 256 fp8)
+ * whatever the call holds: a sequence's results are bit-identical for every chunking and whichever sequences share its call.  Outputs are packed sequence after sequence, len_i - score_from_i entries each; *n_out = their total.  cap
+ * smaller than that: NTTS_EINVAL with the needed count in *n_out, nothing run.
+ * Works on bf16 and fp8 engines of every shape (small-batch ones included) and on the general attention path.  No running or parked request is
+ * touched (nothing of the decode step's workspaces or slot state is written) and no captured step graph is disturbed.
+ * Refusals (nothing is touched): NTTS_ESTATE while ntts_backbone_set_logits_range or calibration mode is on; NTTS_EINVAL, naming the sequence, for a
+ * busy or repeated slot, score_from outside [1, len), len > max_context, an id outside [0, V), sum(lens) above max_prefill_tokens; NTTS_ENOMEM when
+ * the KV pages do not fit.
+ * Debug tap: with ntts_backbone_set_debug(e, 1) the call also keeps the fp32 rows of the scored positions (NTTS_EINVAL if rows x V x 4 exceeds
+ * 64 MB); ntts_backbone_read_score_logits reads row `row` (in output order) of the most recent call, n <= V values. */
+int ntts_backbone_score(ntts_backbone* e, int32_t n, const int32_t* ids, const int32_t* lens, const int32_t* slots,
+                        const int32_t* score_from, int32_t chunk_rows,
+                        float* out_logprobs, int32_t* out_argmax, float* out_argmax_logprobs, int64_t cap, int64_t* n_out);
+int ntts_backbone_read_score_logits(ntts_backbone* e, int64_t row, float* out, int32_t n);
 /* Teacher forcing for the margin-aware parity tests: replace the token slot `slot` emitted last
  * (and will feed to the next step) by `token`. */
 int ntts_backbone_debug_force(ntts_backbone* e, int32_t slot, int32_t token);
@@ -602,6 +632,15 @@ int ntts_k_head_logprob_probe(const void* X_dev, const void* W_dev, int32_t M, i
                               const uint32_t* seen, const float* rep_pen, const int32_t* mask_eos, float* logits_out, uint16_t* logits_bf16_out,
                               float* part_val, int32_t* part_idx, float* part_sum, int32_t part_cap, int32_t* n_part, int32_t* part_width,
                               float* row_lse);
+
+/* The scoring launch (ntts_backbone_score: the lm_head tile with the EPI_ARGMAX_LSE_TGT epilogue, then score.h's merge) on caller-supplied data: X_dev,
+ * W_dev, variant (0, 1, 2, 4: the tiles; no GEMV form), fp8 and xscale as for ntts_k_head_penalty_probe; target = HOST [M] columns in [0, N) (checked).
+ * HOST outputs: logits_out, part_val, part_idx, part_sum as for ntts_k_head_logprob_probe, target_val [M] = the processed logit of the target column,
+ * and the merged logprob / argmax / argmax_logprob [M].  target_val and the three merged arrays are filled with NaN (argmax: -1) before the launch,
+ * so that a missed capture shows. */
+int ntts_k_head_score_probe(const void* X_dev, const void* W_dev, int32_t M, int32_t N, int32_t K, int32_t variant, int32_t fp8, float xscale,
+                            const int32_t* target, float* logits_out, float* part_val, int32_t* part_idx, float* part_sum, int32_t part_cap,
+                            int32_t* n_part, int32_t* part_width, float* target_val, float* logprob, int32_t* argmax, float* argmax_logprob);
 
 /* Paged-attention probes (parity tests against tests/attention_spec.py; no ABI bump).  The KV page layout they read and write, per layer:
  *   K   [page][kv_head][32 tokens][head_dim]          token t of a page in row t

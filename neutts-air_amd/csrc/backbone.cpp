@@ -26,6 +26,7 @@
 #include "kernels/norm.h"
 #include "kernels/qkv_rope.h"
 #include "kernels/sample.h"
+#include "kernels/score.h"
 
 using namespace ntts;
 
@@ -148,6 +149,15 @@ struct ntts_backbone {
     float* part_sum = nullptr;       // [B][n_part_full], beside part_val
     float* out_logprobs = nullptr;   // [B][max_context], entry for entry beside sl.out_tokens
     bool graph_has_lse = false;
+    // Teacher-forced scoring (ntts_backbone_score): scratch of its own, allocated by the first score call and freed at destroy -- nothing of the decode
+    // step's (part_val, xn_dec, the slot arrays) is written, and no captured step names any of it.  The partial arrays hold ONE chunk of scored rows.
+    float *sc_part_val = nullptr, *sc_part_sum = nullptr, *sc_target_val = nullptr;   // [sc_chunk_cap][n_part of the score tile] x 2, [sc_chunk_cap]
+    int* sc_part_idx = nullptr;
+    int sc_chunk_cap = 0;
+    int* sc_rows = nullptr;          // [2][Tmax]: packed row of every scored source position, then its target (the following token id)
+    float* sc_out = nullptr;         // [3][Tmax]: logprob, argmax (int bits), argmax_logprob of the whole call
+    float* sc_logits = nullptr;      // debug tap (ntts_backbone_set_debug): fp32 [sc_logits_rows][V] rows of the most recent score call
+    long sc_logits_rows = 0;
     // ---- decode-step shape, fixed at create() from the batch size (every constant below was swept on MI355X; the losing variants and
     //      their knobs are gone -- DESIGN.md section 4 keeps the numbers, the git history the code)
     int ks_o = 1, ks_d = 1;          // split-K of o_proj / down_proj (fp32 slabs reduced by the norm kernel behind them)
@@ -607,7 +617,8 @@ extern "C" void ntts_backbone_destroy(ntts_backbone* e) {
     bool last_reader = true;
     if (e->share) { last_reader = e->share->refs.fetch_sub(1) == 1; if (last_reader) delete e->share; else e->share->last_decode_ns[e->share_idx].store(0); }
     void* bufs[] = {last_reader ? e->arena : nullptr, e->gu_map_gate, e->gu_map_up, e->kv, e->ibuf, e->h_dec, e->xn_dec, e->qkv_dec, e->attn_dec,
-                    e->act_dec, e->slabs, e->slabs2, e->h_alt, e->part_val, e->part_idx, e->logits, e->logits_bf16, e->seen, e->seen_cols, e->part_sum, e->out_logprobs, e->h_pf, e->xn_pf, e->qkv_pf, e->attn_pf,
+                    e->act_dec, e->slabs, e->slabs2, e->h_alt, e->part_val, e->part_idx, e->logits, e->logits_bf16, e->seen, e->seen_cols, e->part_sum, e->out_logprobs,
+                    e->sc_part_val, e->sc_part_idx, e->sc_part_sum, e->sc_target_val, e->sc_rows, e->sc_out, e->sc_logits, e->h_pf, e->xn_pf, e->qkv_pf, e->attn_pf,
                     e->o_pf, e->act_pf, e->meta_dev, e->as_scores, e->as_stats, e->as_oslabs, e->step_meta, e->rope_rows};
     for (void* b : bufs)
         if (b) hipFree(b);
@@ -1570,6 +1581,140 @@ static hipError_t upload_meta(ntts_backbone* e, const int* src, size_t n, hipStr
 // the penalty a request runs with: a zeroed field means off, like 1
 static float rep_penalty_of(const ntts_sampling& s) { return s.repetition_penalty == 0.f ? 1.0f : s.repetition_penalty; }
 
+// fp8 calibration (ntts_backbone_calibrate, bf16 engines): running max |x| of every GEMM's input rows, slot = 4 * layer + {0: QKV, 1: o_proj,
+// 2: gate/up, 3: down_proj}, last slot = lm_head.  One small launch behind each producer, in calibration mode only.
+// x: DENSE rows (leading dimension == cols, as every workspace tapped is)
+static void calib_tap(ntts_backbone* e, const bf16_t* x, long rows, int cols, int slot, hipStream_t st) {
+    if (!e->calib || rows <= 0) return;
+    const long nvec = rows * cols / 8;
+    float* dst = e->calib + slot;
+    NTTS_LAUNCH((amax_bf16_kernel), dim3((unsigned)std::min<long>((nvec + 255) / 256, 1024)), dim3(256), st, x, nvec, dst);
+}
+
+// The embedding and the layers of a prompt pass over Ti packed rows of n sequences (the meta block is on the device), shared by prefill_impl and
+// ntts_backbone_score.  What follows the last layer's MLP differs: the prompt pass gathers each prompt's last position into its decode-slot row
+// (h_dec / xn_dec), a score call (score_rows != null) normalises the R scored source positions into rows 0 .. R - 1 of xn_pf.
+struct PromptPass {
+    const int* md;                 // the meta block (its first Ti entries are the packed token ids)
+    PrefillMeta meta;              // with the two-sweep tile list of every layer
+    int Ti, n, n_tiles;
+    const int *rt_seq, *rt_q0, *dt_seq, *dt_q0;      // resident / deep work lists of every layer
+    int n_rt, n_dt;
+    bool prune;                    // last layer: attention, o_proj and the MLP on each prompt's last position alone, by the lists below
+    const int *lt_seq, *lt_q0, *lrt_seq, *lrt_q0, *ldt_seq, *ldt_q0;
+    int n_lt, n_lrt, n_ldt;
+    const int *last_row, *slot;    // [n] each prompt's last packed row and its decode slot
+    const int* score_rows;         // [R] packed rows of the scored source positions, or null
+    int R;
+};
+static void prompt_pass_layers(ntts_backbone* e, const PromptPass& P, hipStream_t st) {
+    const ntts_backbone_config& c = e->cfg;
+    const int H = e->H, F = e->F, QD = c.num_heads * e->HD, Ti = P.Ti, n = P.n;
+    const int* md = P.md;
+    const PrefillMeta& meta = P.meta;
+    NormArgs n0{};
+    n0.gather_ids = md; n0.embed = e->embed; n0.resid_out = e->h_pf; n0.norm_w = e->layers[0].ln1; n0.normed_out = e->xn_pf;
+    n0.M = Ti; n0.H = H; n0.eps = c.rms_eps;
+    if (e->fp8) n0.out_fp8_inv = 1.0f / e->layers[0].xs[0];
+    add_rmsnorm_launch(n0, st);
+    for (int i = 0; i < c.num_layers; ++i) {
+        const LayerW& w = e->layers[i];
+        const bool last = i + 1 == c.num_layers;
+        calib_tap(e, e->xn_pf, Ti, H, 4 * i, st);
+        gemm_large<EPI_BF16>(e, gemm_args(e, e->xn_pf, H, w.wqkv, H, w.bqkv, e->qkv_pf, e->NQKV, Ti, e->NQKV, H, w.sqkv, w.xs[0]), st);
+        RopeWriteArgs r{};
+        r.qkv = e->qkv_pf; r.ld_qkv = e->NQKV; r.kpool = e->kv + (size_t)i * e->layer_stride; r.vpool = r.kpool + e->kv_half;
+        r.block_table = e->block_table; r.max_pages = e->max_pages; r.meta = meta; r.rope_cos = e->rope_cos; r.rope_sin = e->rope_sin;
+        r.nh = c.num_heads; r.nkv = c.num_kv_heads; r.T = Ti;
+        // the q heads are rotated by the attention kernel as it loads them (one read + one write of T x 896 values less per layer:
+        // prompt pass 28.16 -> 27.94 ms per chunk, profiles/r02k_sweep_pf_rope_q_fused.log); this kernel rotates k and scatters v
+        r.skip_q = 1;
+        if (e->generic) {   // head_dim 128 and / or qk-norm: q AND k normalised + rotated here (q in place), v scattered (attn_prefill.h)
+            RopeNormArgs g{};
+            g.qkv = e->qkv_pf; g.ld_qkv = e->NQKV; g.kpool = r.kpool; g.vpool = r.vpool; g.block_table = e->block_table; g.max_pages = e->max_pages;
+            g.meta = meta; g.rope_cos = e->rope_cos; g.rope_sin = e->rope_sin; g.q_norm = w.qn; g.k_norm = w.kn; g.eps = c.rms_eps;
+            g.nh = c.num_heads; g.nkv = c.num_kv_heads; g.rows = Ti; g.write_v = 1;
+            const long items = (long)Ti * (c.num_heads + 2 * c.num_kv_heads);
+            if (e->HD == 128) NTTS_LAUNCH((rope_norm_kv_write_kernel<128>), dim3((unsigned)((items + 3) / 4)), dim3(256), st, g);
+            else NTTS_LAUNCH((rope_norm_kv_write_kernel<64>), dim3((unsigned)((items + 3) / 4)), dim3(256), st, g);
+        } else
+        NTTS_LAUNCH((rope_kv_write_vec_kernel), dim3((Ti + kRopeTokPerBlock - 1) / kRopeTokPerBlock), dim3(256), st, r);
+        AttnPrefillArgs a{};
+        a.qkv = e->qkv_pf; a.ld_qkv = e->NQKV; a.out = e->attn_pf; a.ld_out = QD; a.kpool = r.kpool; a.vpool = r.vpool;
+        a.block_table = e->block_table; a.max_pages = e->max_pages; a.meta = meta; a.nh = c.num_heads; a.nkv = c.num_kv_heads;
+        if (e->fp8) a.out_fp8_inv = 1.0f / w.xs[1];     // attn_pf rows hold QD e4m3 BYTES (ld_out counts bytes then)
+        a.rope_cos = e->rope_cos; a.rope_sin = e->rope_sin;
+        if (e->generic) a.rope_cos = a.rope_sin = nullptr;   // (q is already normalised and rotated)
+        // Last layer: the KV pages are complete after the rope/KV-write above, and nothing but each prompt's LAST position
+        // is read afterwards (it alone feeds the lm_head).  Attention runs on the one query tile per prompt that holds
+        // it, then that row and its residual row are compacted and o_proj / the MLP run on n rows instead of T.
+        // Row-wise results are unchanged (every GEMM / norm row is computed from that row's operands alone).
+        const bool prune = last && P.prune;
+        int n_tiles = P.n_tiles, n_rtiles = P.n_rt;
+        if (prune) { a.meta.tile_seq = P.lt_seq; a.meta.tile_q0 = P.lt_q0; n_tiles = P.n_lt; }
+        if (n_tiles) { if (e->HD == 128) attn_prefill_launch_hd128(a, n_tiles, st); else attn_prefill_launch(a, n_tiles, st); }
+        a.meta.tile_seq = P.rt_seq; a.meta.tile_q0 = P.rt_q0;
+        if (prune) { a.meta.tile_seq = P.lrt_seq; a.meta.tile_q0 = P.lrt_q0; n_rtiles = P.n_lrt; }
+        if (n_rtiles) attn_prefill_res_launch(a, n_rtiles, e->pf_res_cap, prune, st);
+        int n_dtiles = P.n_dt;
+        a.meta.tile_seq = P.dt_seq; a.meta.tile_q0 = P.dt_q0;
+        if (prune) { a.meta.tile_seq = P.ldt_seq; a.meta.tile_q0 = P.ldt_q0; n_dtiles = P.n_ldt; }
+        if (n_dtiles) attn_prefill_deep_launch(a, n_dtiles, e->pf_res_cap, e->pf_deep_cap, prune, st);
+        const int Mi = prune ? n : Ti;                       // rows from here on
+        const bf16_t* attn_in = e->attn_pf;
+        bf16_t* hres = e->h_pf;
+        if (prune) {   // qkv_pf is free once attention has run: T * NQKV >= 4 n * NQKV > n * (QD + H) elements
+            bf16_t* attn_c = e->qkv_pf;
+            bf16_t* h_c = e->qkv_pf + (size_t)n * QD;
+            const int qe = e->fp8 ? QD / 2 : QD;   // attention rows in bf16 units (fp8: QD bytes)
+            NTTS_LAUNCH((gather_rows_kernel), dim3(n), dim3(256), st, (const bf16_t*)e->attn_pf, (long)qe, P.last_row, attn_c, (long)qe, qe);
+            NTTS_LAUNCH((gather_rows_kernel), dim3(n), dim3(256), st, (const bf16_t*)e->h_pf, (long)H, P.last_row, h_c, (long)H, H);
+            attn_in = attn_c;
+            hres = h_c;
+        }
+        // the residual add rides in the o_proj / down_proj epilogue (EPI_RESID: h = bf16(h + bf16(acc)), in place -- the same two
+        // roundings the norm kernel applied), so the norm pass reads one row stream instead of two and writes one
+        // (131.8 -> 128.3 ms per batch, profiles/r02i_ab_prefill_resid_epilogue.jsonl)
+        NormArgs n1{};
+        calib_tap(e, attn_in, Mi, QD, 4 * i + 1, st);
+        {
+            GemmArgs ao = gemm_args(e, attn_in, QD, w.wo, QD, nullptr, hres, H, Mi, H, QD, w.so, w.xs[1]);
+            ao.resid_bf16 = hres; ao.ldrb = H;
+            gemm_large<EPI_RESID>(e, ao, st);
+            n1.o_bf16 = hres;
+        }
+        n1.norm_w = w.ln2; n1.normed_out = e->xn_pf;
+        n1.M = Mi; n1.H = H; n1.eps = c.rms_eps;
+        if (e->fp8) n1.out_fp8_inv = 1.0f / w.xs[2];
+        add_rmsnorm_launch(n1, st);
+        calib_tap(e, e->xn_pf, Mi, H, 4 * i + 2, st);
+        GemmArgs gu = gemm_args(e, e->xn_pf, H, w.wgu, H, nullptr, e->act_pf, F, Mi, 2 * F, H, w.sgu, w.xs[2]);
+        if (e->fp8) gu.out_fp8_inv = 1.0f / w.xs[3];
+        gemm_large<EPI_SILU_MUL>(e, gu, st);
+        calib_tap(e, e->act_pf, Mi, F, 4 * i + 3, st);
+        NormArgs n2{};
+        {
+            GemmArgs ad = gemm_args(e, e->act_pf, F, w.wd, F, nullptr, hres, H, Mi, H, F, w.sd, w.xs[3]);
+            ad.resid_bf16 = hres; ad.ldrb = H;
+            gemm_large<EPI_RESID>(e, ad, st);
+            n2.o_bf16 = hres;
+        }
+        n2.eps = c.rms_eps; n2.H = H;
+        if (!last) {
+            n2.norm_w = e->layers[i + 1].ln1; n2.normed_out = e->xn_pf; n2.M = Ti;
+            if (e->fp8) n2.out_fp8_inv = 1.0f / e->layers[i + 1].xs[0];
+        } else if (P.score_rows) {   // ntts_backbone_score: the final norm over the scored source positions only, gathered into rows 0 .. R - 1
+            n2.norm_w = e->final_norm; n2.normed_out = e->xn_pf; n2.M = P.R; n2.in_rows = P.score_rows;
+            if (e->fp8) n2.out_fp8_inv = 1.0f / e->xs_head;
+        } else {  // only each prompt's last position feeds the lm_head: gather it into its decode-slot row
+            n2.resid_out = e->h_dec; n2.norm_w = e->final_norm; n2.normed_out = e->xn_dec; n2.M = n;
+            n2.in_rows = prune ? nullptr : P.last_row; n2.out_rows = P.slot;
+            if (e->fp8) n2.out_fp8_inv = 1.0f / e->xs_head;
+        }
+        add_rmsnorm_launch(n2, st);
+    }
+}
+
 // Prompt pass.  With donor_slot / shared_len (ntts_backbone_prefill_shared): prompt i re-uses the KV pages that hold the
 // first pos0[i] = floor(shared_len[i] / 32) * 32 tokens of its donor's prompt -- only the remaining tokens are packed,
 // embedded and pushed through the layers; their queries attend to the shared pages exactly as they would to their own.
@@ -1580,7 +1725,7 @@ static int prefill_impl(ntts_backbone* e, int32_t n, const int32_t* ids, const i
     if (!e->finalized) return fail(e, NTTS_ESTATE, "weights not finalised");
     HIPCHK(e, hipSetDevice(e->device));
     const ntts_backbone_config& c = e->cfg;
-    const int B = c.max_batch, H = e->H, F = e->F, QD = c.num_heads * e->HD;
+    const int B = c.max_batch, H = e->H;
     long T = 0, Tfull = 0;
     std::vector<int> pos0(n, 0), id_off(n, 0);
     for (int i = 0; i < n; ++i) { id_off[i] = (int)Tfull; Tfull += lens[i] > 0 ? lens[i] : 0; }
@@ -1798,118 +1943,23 @@ static int prefill_impl(ntts_backbone* e, int32_t n, const int32_t* ids, const i
     }
 
     const int Ti = (int)T;
-    NormArgs n0{};
-    n0.gather_ids = md; n0.embed = e->embed; n0.resid_out = e->h_pf; n0.norm_w = e->layers[0].ln1; n0.normed_out = e->xn_pf;
-    n0.M = Ti; n0.H = H; n0.eps = c.rms_eps;
-    if (e->fp8) n0.out_fp8_inv = 1.0f / e->layers[0].xs[0];
-    add_rmsnorm_launch(n0, st);
-    // fp8 calibration (ntts_backbone_calibrate, bf16 engines): running max |x| of every GEMM's input rows, slot = 4 * layer + {0: QKV, 1: o_proj,
-    // 2: gate/up, 3: down_proj}, last slot = lm_head.  One small launch behind each producer, in calibration mode only.
-    auto tap = [&](const bf16_t* x, long rows, int cols, int slot) {   // x: DENSE rows (leading dimension == cols, as every workspace tapped below is)
-        if (!e->calib || rows <= 0) return;
-        const long nvec = rows * cols / 8;
-        float* dst = e->calib + slot;
-        NTTS_LAUNCH((amax_bf16_kernel), dim3((unsigned)std::min<long>((nvec + 255) / 256, 1024)), dim3(256), st, x, nvec, dst);
-    };
-    for (int i = 0; i < c.num_layers; ++i) {
-        const LayerW& w = e->layers[i];
-        const bool last = i + 1 == c.num_layers;
-        tap(e->xn_pf, Ti, H, 4 * i);
-        gemm_large<EPI_BF16>(e, gemm_args(e, e->xn_pf, H, w.wqkv, H, w.bqkv, e->qkv_pf, e->NQKV, Ti, e->NQKV, H, w.sqkv, w.xs[0]), st);
-        RopeWriteArgs r{};
-        r.qkv = e->qkv_pf; r.ld_qkv = e->NQKV; r.kpool = e->kv + (size_t)i * e->layer_stride; r.vpool = r.kpool + e->kv_half;
-        r.block_table = e->block_table; r.max_pages = e->max_pages; r.meta = meta; r.rope_cos = e->rope_cos; r.rope_sin = e->rope_sin;
-        r.nh = c.num_heads; r.nkv = c.num_kv_heads; r.T = Ti;
-        // the q heads are rotated by the attention kernel as it loads them (one read + one write of T x 896 values less per layer:
-        // prompt pass 28.16 -> 27.94 ms per chunk, profiles/r02k_sweep_pf_rope_q_fused.log); this kernel rotates k and scatters v
-        r.skip_q = 1;
-        if (e->generic) {   // head_dim 128 and / or qk-norm: q AND k normalised + rotated here (q in place), v scattered (attn_prefill.h)
-            RopeNormArgs g{};
-            g.qkv = e->qkv_pf; g.ld_qkv = e->NQKV; g.kpool = r.kpool; g.vpool = r.vpool; g.block_table = e->block_table; g.max_pages = e->max_pages;
-            g.meta = meta; g.rope_cos = e->rope_cos; g.rope_sin = e->rope_sin; g.q_norm = w.qn; g.k_norm = w.kn; g.eps = c.rms_eps;
-            g.nh = c.num_heads; g.nkv = c.num_kv_heads; g.rows = Ti; g.write_v = 1;
-            const long items = (long)Ti * (c.num_heads + 2 * c.num_kv_heads);
-            if (e->HD == 128) NTTS_LAUNCH((rope_norm_kv_write_kernel<128>), dim3((unsigned)((items + 3) / 4)), dim3(256), st, g);
-            else NTTS_LAUNCH((rope_norm_kv_write_kernel<64>), dim3((unsigned)((items + 3) / 4)), dim3(256), st, g);
-        } else
-        NTTS_LAUNCH((rope_kv_write_vec_kernel), dim3((Ti + kRopeTokPerBlock - 1) / kRopeTokPerBlock), dim3(256), st, r);
-        AttnPrefillArgs a{};
-        a.qkv = e->qkv_pf; a.ld_qkv = e->NQKV; a.out = e->attn_pf; a.ld_out = QD; a.kpool = r.kpool; a.vpool = r.vpool;
-        a.block_table = e->block_table; a.max_pages = e->max_pages; a.meta = meta; a.nh = c.num_heads; a.nkv = c.num_kv_heads;
-        if (e->fp8) a.out_fp8_inv = 1.0f / w.xs[1];     // attn_pf rows hold QD e4m3 BYTES (ld_out counts bytes then)
-        a.rope_cos = e->rope_cos; a.rope_sin = e->rope_sin;
-        if (e->generic) a.rope_cos = a.rope_sin = nullptr;   // (q is already normalised and rotated)
-        // Last layer: the KV pages are complete after the rope/KV-write above, and nothing but each prompt's LAST position
-        // is read afterwards (it alone feeds the lm_head).  Attention runs on the one query tile per prompt that holds
-        // it, then that row and its residual row are compacted and o_proj / the MLP run on n rows instead of T.
-        // Row-wise results are unchanged (every GEMM / norm row is computed from that row's operands alone).
-        const bool prune = last && T >= 4L * n && !e->calib;    // (calibration mode looks at EVERY position's GEMM inputs, the last layer's included)
-        int n_tiles = (int)tile_seq.size(), n_rtiles = (int)rtile_seq.size();
-        if (prune) { a.meta.tile_seq = md + o_ltseq; a.meta.tile_q0 = md + o_ltq0; n_tiles = (int)lt_seq.size(); }
-        if (n_tiles) { if (e->HD == 128) attn_prefill_launch_hd128(a, n_tiles, st); else attn_prefill_launch(a, n_tiles, st); }
-        a.meta.tile_seq = md + o_rtseq; a.meta.tile_q0 = md + o_rtq0;
-        if (prune) { a.meta.tile_seq = md + o_lrtseq; a.meta.tile_q0 = md + o_lrtq0; n_rtiles = (int)lrt_seq.size(); }
-        if (n_rtiles) attn_prefill_res_launch(a, n_rtiles, e->pf_res_cap, prune, st);
-        int n_dtiles = (int)dtile_seq.size();
-        a.meta.tile_seq = md + o_dtseq; a.meta.tile_q0 = md + o_dtq0;
-        if (prune) { a.meta.tile_seq = md + o_ldtseq; a.meta.tile_q0 = md + o_ldtq0; n_dtiles = (int)ldt_seq.size(); }
-        if (n_dtiles) attn_prefill_deep_launch(a, n_dtiles, e->pf_res_cap, e->pf_deep_cap, prune, st);
-        const int Mi = prune ? n : Ti;                       // rows from here on
-        const bf16_t* attn_in = e->attn_pf;
-        bf16_t* hres = e->h_pf;
-        if (prune) {   // qkv_pf is free once attention has run: T * NQKV >= 4 n * NQKV > n * (QD + H) elements
-            bf16_t* attn_c = e->qkv_pf;
-            bf16_t* h_c = e->qkv_pf + (size_t)n * QD;
-            const int qe = e->fp8 ? QD / 2 : QD;   // attention rows in bf16 units (fp8: QD bytes)
-            NTTS_LAUNCH((gather_rows_kernel), dim3(n), dim3(256), st, (const bf16_t*)e->attn_pf, (long)qe, (const int*)(md + o_last), attn_c, (long)qe, qe);
-            NTTS_LAUNCH((gather_rows_kernel), dim3(n), dim3(256), st, (const bf16_t*)e->h_pf, (long)H, (const int*)(md + o_last), h_c, (long)H, H);
-            attn_in = attn_c;
-            hres = h_c;
-        }
-        // the residual add rides in the o_proj / down_proj epilogue (EPI_RESID: h = bf16(h + bf16(acc)), in place -- the same two
-        // roundings the norm kernel applied), so the norm pass reads one row stream instead of two and writes one
-        // (131.8 -> 128.3 ms per batch, profiles/r02i_ab_prefill_resid_epilogue.jsonl)
-        NormArgs n1{};
-        tap(attn_in, Mi, QD, 4 * i + 1);
-        {
-            GemmArgs ao = gemm_args(e, attn_in, QD, w.wo, QD, nullptr, hres, H, Mi, H, QD, w.so, w.xs[1]);
-            ao.resid_bf16 = hres; ao.ldrb = H;
-            gemm_large<EPI_RESID>(e, ao, st);
-            n1.o_bf16 = hres;
-        }
-        n1.norm_w = w.ln2; n1.normed_out = e->xn_pf;
-        n1.M = Mi; n1.H = H; n1.eps = c.rms_eps;
-        if (e->fp8) n1.out_fp8_inv = 1.0f / w.xs[2];
-        add_rmsnorm_launch(n1, st);
-        tap(e->xn_pf, Mi, H, 4 * i + 2);
-        GemmArgs gu = gemm_args(e, e->xn_pf, H, w.wgu, H, nullptr, e->act_pf, F, Mi, 2 * F, H, w.sgu, w.xs[2]);
-        if (e->fp8) gu.out_fp8_inv = 1.0f / w.xs[3];
-        gemm_large<EPI_SILU_MUL>(e, gu, st);
-        tap(e->act_pf, Mi, F, 4 * i + 3);
-        NormArgs n2{};
-        {
-            GemmArgs ad = gemm_args(e, e->act_pf, F, w.wd, F, nullptr, hres, H, Mi, H, F, w.sd, w.xs[3]);
-            ad.resid_bf16 = hres; ad.ldrb = H;
-            gemm_large<EPI_RESID>(e, ad, st);
-            n2.o_bf16 = hres;
-        }
-        n2.eps = c.rms_eps; n2.H = H;
-        if (!last) {
-            n2.norm_w = e->layers[i + 1].ln1; n2.normed_out = e->xn_pf; n2.M = Ti;
-            if (e->fp8) n2.out_fp8_inv = 1.0f / e->layers[i + 1].xs[0];
-        } else {  // only each prompt's last position feeds the lm_head: gather it into its decode-slot row
-            n2.resid_out = e->h_dec; n2.norm_w = e->final_norm; n2.normed_out = e->xn_dec; n2.M = n;
-            n2.in_rows = prune ? nullptr : md + o_last; n2.out_rows = md + o_slot;
-            if (e->fp8) n2.out_fp8_inv = 1.0f / e->xs_head;
-        }
-        add_rmsnorm_launch(n2, st);
-    }
+    PromptPass pp{};
+    pp.md = md; pp.meta = meta; pp.Ti = Ti; pp.n = n;
+    pp.n_tiles = (int)tile_seq.size();
+    pp.rt_seq = md + o_rtseq; pp.rt_q0 = md + o_rtq0; pp.n_rt = (int)rtile_seq.size();
+    pp.dt_seq = md + o_dtseq; pp.dt_q0 = md + o_dtq0; pp.n_dt = (int)dtile_seq.size();
+    pp.lt_seq = md + o_ltseq; pp.lt_q0 = md + o_ltq0; pp.n_lt = (int)lt_seq.size();
+    pp.lrt_seq = md + o_lrtseq; pp.lrt_q0 = md + o_lrtq0; pp.n_lrt = (int)lrt_seq.size();
+    pp.ldt_seq = md + o_ldtseq; pp.ldt_q0 = md + o_ldtq0; pp.n_ldt = (int)ldt_seq.size();
+    pp.last_row = md + o_last; pp.slot = md + o_slot;
+    pp.prune = T >= 4L * n && !e->calib;    // (calibration mode looks at EVERY position's GEMM inputs, the last layer's included)
+    prompt_pass_layers(e, pp, st);
     if (e->calib) {        // the lm_head's input: the final norm of EVERY position (the decode steps feed the head one row per step and
         NormArgs nc{};     // sequence -- a record of the prompts' last positions only would be 64 rows for 64 calibration prompts); scratch output
         nc.o_bf16 = e->h_pf; nc.norm_w = e->final_norm;   // (no pruning in calibration mode: h_pf holds every row)
         nc.norm_w = e->final_norm; nc.normed_out = e->xn_pf; nc.M = Ti; nc.H = H; nc.eps = c.rms_eps;
         add_rmsnorm_launch(nc, st);
-        tap(e->xn_pf, Ti, H, 4 * c.num_layers);
+        calib_tap(e, e->xn_pf, Ti, H, 4 * c.num_layers, st);
     }
     lm_head_and_sample(e, SLOT_PREFILLED);
     HIPCHK(e, hipEventRecord(e->ev[1], st));
@@ -1936,6 +1986,180 @@ extern "C" int ntts_backbone_prefill_shared(ntts_backbone* e, int32_t n, const i
                                             const int32_t* shared_len) {
     if (!donor_slot || !shared_len) return fail(e, NTTS_EINVAL, "null argument");
     return prefill_impl(e, n, ids, lens, slots, samp, donor_slot, shared_len);
+}
+
+// ------------------------------------------------------------------------------------------------
+// teacher-forced scoring of given sequences (include/neutts_hip.h ntts_backbone_score)
+// ------------------------------------------------------------------------------------------------
+// (max, first index, sum) partials per row of a head of N columns on lm_head tile `tile` (gemm.h lm_head_launch_epi)
+static int score_n_part(int tile, int N) {
+    return tile == 0 ? (N + 63) / 64 : tile == 4 ? ((N + 287) / 288) * 3 : tile == 2 ? ((N + 255) / 256) * 4 : ((N + 127) / 128) * 2;
+}
+// Rows per lm_head launch when the caller passes chunk_rows = 0.  A chunk streams the whole head once (390 MB at NeuTTS-Air's vocabulary, ~80 us of
+// HBM time) against rows * V * H * 2 FLOP: at 2048 rows that is ~0.8 ms of matrix-core time, so the weight stream is ~10 % of a chunk and halves with
+// every doubling, while the three partial arrays grow by 12 bytes * n_part per row: 2048 rows * 2 268 partials (256 x 288 tile; 3 400 on the fp8 engine's 256 x 256) = 56 MB.  2048 rows are also the
+// 8 m-blocks of one group of the 256-row tiles' XCD-aware order (gemm.h gemm_tile_coords), so every chunk is whole groups.
+static constexpr int kScoreChunkRows = 2048, kScoreChunkMax = 8192;
+static constexpr long kScoreTapBytes = 64L << 20;
+
+extern "C" int ntts_backbone_score(ntts_backbone* e, int32_t n, const int32_t* ids, const int32_t* lens, const int32_t* slots,
+                                   const int32_t* score_from, int32_t chunk_rows, float* out_logprobs, int32_t* out_argmax,
+                                   float* out_argmax_logprobs, int64_t cap, int64_t* n_out) {
+    if (!e || n < 1 || !ids || !lens || !slots || !score_from || !out_logprobs || !out_argmax || !out_argmax_logprobs || !n_out || chunk_rows < 0 || cap < 0)
+        return fail(e, NTTS_EINVAL, "null/empty argument");
+    if (!e->finalized) return fail(e, NTTS_ESTATE, "weights not finalised");
+    if (e->lr_rows) return fail(e, NTTS_ESTATE, "score: the restricted lm_head is on (ntts_backbone_set_logits_range): scores are over the whole vocabulary");
+    if (e->calib) return fail(e, NTTS_ESTATE, "score: calibration mode is on (ntts_backbone_calibrate)");
+    const ntts_backbone_config& c = e->cfg;
+    const int B = c.max_batch, H = e->H, V = c.vocab_size;
+    long T = 0, R = 0;
+    std::vector<int> id_off(n, 0);
+    for (int i = 0; i < n; ++i) {
+        if (slots[i] < 0 || slots[i] >= B) return fail(e, NTTS_EINVAL, "sequence %d: slot %d out of range", i, slots[i]);
+        if (e->slots[slots[i]].state != SLOT_FREE) return fail(e, NTTS_EINVAL, "sequence %d: slot %d is busy", i, slots[i]);
+        for (int j = 0; j < i; ++j)
+            if (slots[j] == slots[i]) return fail(e, NTTS_EINVAL, "sequence %d: slot %d given twice", i, slots[i]);
+        if (lens[i] < 2) return fail(e, NTTS_EINVAL, "sequence %d: %d tokens (a scored token needs one before it)", i, lens[i]);
+        if (lens[i] > c.max_context) return fail(e, NTTS_EINVAL, "sequence %d: %d tokens exceed max_context %d", i, lens[i], c.max_context);
+        if (score_from[i] < 1 || score_from[i] >= lens[i])
+            return fail(e, NTTS_EINVAL, "sequence %d: score_from %d outside [1, %d)", i, score_from[i], lens[i]);
+        id_off[i] = (int)T;
+        T += lens[i];
+        R += lens[i] - score_from[i];
+        if (T > e->Tmax) return fail(e, NTTS_EINVAL, "sequence %d: %ld tokens so far exceed max_prefill_tokens %d", i, T, e->Tmax);
+    }
+    for (int i = 0; i < n; ++i)
+        for (int t = 0; t < lens[i]; ++t)
+            if (ids[id_off[i] + t] < 0 || ids[id_off[i] + t] >= V) return fail(e, NTTS_EINVAL, "sequence %d: token id %d out of range", i, ids[id_off[i] + t]);
+    *n_out = R;
+    if (cap < R) return fail(e, NTTS_EINVAL, "score: %ld values to return, room for %ld", R, (long)cap);
+    const bool tap = e->logits != nullptr;                  // ntts_backbone_set_debug(e, 1)
+    if (tap && R * (long)V * 4 > kScoreTapBytes)
+        return fail(e, NTTS_EINVAL, "score: the debug tap would keep %ld rows x %d logits (more than 64 MB); score fewer positions or switch it off", R, V);
+    {   // the pages must fit before any is taken
+        long need = 0;
+        for (int i = 0; i < n; ++i) need += (lens[i] + kPage - 1) / kPage;
+        if (need > (long)e->free_pages.size()) return fail(e, NTTS_ENOMEM, "score: %ld KV pages needed, %zu free", need, e->free_pages.size());
+    }
+    // one tile per engine, the 256-row one of its weight format, whatever the call holds: the partial groups -- and so the order of every sum -- depend
+    // neither on the chunking nor on which sequences share the call (a short call pads one m-block: the cost of a decode step's lm_head)
+    const int tile = e->fp8 ? 2 : 4;
+    const int np = score_n_part(tile, V);
+    int chunk = chunk_rows > 0 ? std::min<int>(chunk_rows, kScoreChunkMax) : kScoreChunkRows;
+    if (chunk > e->Tmax) chunk = e->Tmax;
+    HIPCHK(e, hipSetDevice(e->device));
+    // ---- scratch: first call, or a larger chunk than any before
+    if (!e->sc_rows) {
+        HIPCHK(e, hipMalloc((void**)&e->sc_rows, (size_t)2 * e->Tmax * sizeof(int)));
+        HIPCHK(e, hipMalloc((void**)&e->sc_out, (size_t)3 * e->Tmax * sizeof(float)));
+    }
+    if (chunk > e->sc_chunk_cap) {
+        HIPCHK(e, hipStreamSynchronize(e->stream));
+        for (void* b : {(void*)e->sc_part_val, (void*)e->sc_part_idx, (void*)e->sc_part_sum, (void*)e->sc_target_val})
+            if (b) (void)hipFree(b);
+        e->sc_part_val = e->sc_part_sum = e->sc_target_val = nullptr; e->sc_part_idx = nullptr; e->sc_chunk_cap = 0;
+        const size_t pb = (size_t)chunk * np * 4;
+        HIPCHK(e, hipMalloc((void**)&e->sc_part_val, pb));
+        HIPCHK(e, hipMalloc((void**)&e->sc_part_idx, pb));
+        HIPCHK(e, hipMalloc((void**)&e->sc_part_sum, pb));
+        HIPCHK(e, hipMalloc((void**)&e->sc_target_val, (size_t)chunk * 4));
+        e->sc_chunk_cap = chunk;
+    }
+    if (e->sc_logits) { HIPCHK(e, hipStreamSynchronize(e->stream)); (void)hipFree(e->sc_logits); e->sc_logits = nullptr; e->sc_logits_rows = 0; }
+    if (tap) {
+        HIPCHK(e, hipMalloc((void**)&e->sc_logits, (size_t)R * V * 4));
+        e->sc_logits_rows = R;
+    }
+    // ---- pages: taken here, given back on EVERY way out (the slots' host state never leaves FREE)
+    struct Pages {   // (an early return on a HIP error may leave kernels that write the pages queued: drained, best effort, before they change hands)
+        ntts_backbone* e; const int32_t* slots; int n; bool queued = false;
+        ~Pages() {
+            if (queued) (void)hipStreamSynchronize(e->stream);
+            for (int i = 0; i < n; ++i) drop_pages(e, e->slots[slots[i]]);
+        }
+    } pages{e, slots, n};
+    for (int i = 0; i < n; ++i)
+        if (alloc_pages(e, e->slots[slots[i]], lens[i]) != NTTS_OK) return fail(e, NTTS_ENOMEM, "KV page pool exhausted (%d pages)", e->num_pages);
+    // ---- meta block: [ids T][tok_seq T][tok_base n][seq_len n][pos0 n][slot n][tile lists][bt_rows n*max_pages]; the scored rows and their targets
+    //      go to sc_rows (2 T more ints would not fit the prompt pass's block)
+    const std::vector<int> pos0(n, 0);
+    const PrefillWorkLists wl = prefill_work_lists(n, lens, pos0.data(), e->pf_res_cap, e->pf_deep_cap);
+    std::vector<int> m;
+    m.reserve(2 * T + 16 * n);
+    m.insert(m.end(), ids, ids + T);
+    const size_t o_tok_seq = m.size(); m.insert(m.end(), wl.tok_seq.begin(), wl.tok_seq.end());
+    const size_t o_base = m.size();    m.insert(m.end(), wl.tok_base.begin(), wl.tok_base.end());
+    const size_t o_len = m.size();     m.insert(m.end(), lens, lens + n);
+    const size_t o_pos0 = m.size();    m.insert(m.end(), pos0.begin(), pos0.end());
+    const size_t o_slot = m.size();    m.insert(m.end(), slots, slots + n);
+    const size_t o_tseq = m.size();    m.insert(m.end(), wl.tile_seq.begin(), wl.tile_seq.end());
+    const size_t o_tq0 = m.size();     m.insert(m.end(), wl.tile_q0.begin(), wl.tile_q0.end());
+    const size_t o_rtseq = m.size();   m.insert(m.end(), wl.rtile_seq.begin(), wl.rtile_seq.end());
+    const size_t o_rtq0 = m.size();    m.insert(m.end(), wl.rtile_q0.begin(), wl.rtile_q0.end());
+    const size_t o_dtseq = m.size();   m.insert(m.end(), wl.dtile_seq.begin(), wl.dtile_seq.end());
+    const size_t o_dtq0 = m.size();    m.insert(m.end(), wl.dtile_q0.begin(), wl.dtile_q0.end());
+    const size_t o_bt = m.size();
+    for (int i = 0; i < n; ++i) {
+        const HostSlot& s = e->slots[slots[i]];
+        for (int k = 0; k < e->max_pages; ++k) m.push_back(k < (int)s.pages.size() ? s.pages[k] : 0);
+    }
+    if (m.size() > e->meta_cap) return fail(e, NTTS_EINVAL, "score meta block too large");
+    std::vector<int> rows;                                   // [R] source rows, then [R] targets
+    rows.reserve(2 * R);
+    for (int i = 0; i < n; ++i)
+        for (int j = score_from[i]; j < lens[i]; ++j) rows.push_back(id_off[i] + j - 1);
+    for (int i = 0; i < n; ++i)
+        for (int j = score_from[i]; j < lens[i]; ++j) rows.push_back(ids[id_off[i] + j]);
+    hipStream_t st = e->stream;
+    // (sc_rows is idle: the previous score call drained the stream before it returned; a blocking copy, so `rows` may go at any return)
+    HIPCHK(e, hipMemcpy(e->sc_rows, rows.data(), rows.size() * sizeof(int), hipMemcpyHostToDevice));
+    pages.queued = true;
+    HIPCHK(e, upload_meta(e, m.data(), m.size(), st));
+    const int* md = e->meta_dev;
+    PrefillMeta meta{md + o_base, md + o_len, md + o_pos0, md + o_slot, md + o_tok_seq, md + o_tseq, md + o_tq0};
+    NTTS_LAUNCH((score_block_table_kernel), dim3(n), dim3(64), st, md + o_slot, md + o_bt, e->block_table, e->max_pages);
+
+    // ---- the prompt pass over every position: no pruning of the last layer, no first token; the final norm on the scored source rows only
+    PromptPass pp{};
+    pp.md = md; pp.meta = meta; pp.Ti = (int)T; pp.n = n;
+    pp.n_tiles = (int)wl.tile_seq.size();
+    pp.rt_seq = md + o_rtseq; pp.rt_q0 = md + o_rtq0; pp.n_rt = (int)wl.rtile_seq.size();
+    pp.dt_seq = md + o_dtseq; pp.dt_q0 = md + o_dtq0; pp.n_dt = (int)wl.dtile_seq.size();
+    pp.score_rows = e->sc_rows; pp.R = (int)R;
+    prompt_pass_layers(e, pp, st);
+    // ---- lm_head + merge, chunk by chunk: partials of one chunk at a time, outputs of the whole call in sc_out
+    float* d_lp = e->sc_out;
+    int* d_am = (int*)(e->sc_out + e->Tmax);
+    float* d_alp = e->sc_out + 2 * (size_t)e->Tmax;
+    const size_t xrow = (size_t)H * (e->fp8 ? 1 : 2);        // bytes per lm_head input row
+    for (long r0 = 0; r0 < R; r0 += chunk) {
+        const int rows_c = (int)std::min<long>(chunk, R - r0);
+        GemmArgs a = gemm_args(e, (const bf16_t*)((const char*)e->xn_pf + (size_t)r0 * xrow), H, e->embed_tm, H, nullptr, nullptr, 0, rows_c, V, H, e->shead, e->xs_head);
+        a.tl = nullptr;
+        a.part_val = e->sc_part_val; a.part_idx = e->sc_part_idx; a.part_sum = e->sc_part_sum;
+        a.target = e->sc_rows + R + r0; a.target_val = e->sc_target_val;
+        if (tap) { a.logits = e->sc_logits + (size_t)r0 * V; a.ld_logits = V; }
+        lm_head_launch(a, tile, e->fp8, st);
+        ScoreMergeArgs sm{e->sc_part_val, e->sc_part_idx, e->sc_part_sum, np, e->sc_target_val, d_lp + r0, d_am + r0, d_alp + r0};
+        NTTS_LAUNCH((score_merge_kernel), dim3(rows_c), dim3(256), st, sm);
+    }
+    HIPCHK(e, hipGetLastError());
+    HIPCHK(e, hipMemcpyAsync(out_logprobs, d_lp, (size_t)R * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(e, hipMemcpyAsync(out_argmax, d_am, (size_t)R * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(e, hipMemcpyAsync(out_argmax_logprobs, d_alp, (size_t)R * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(e, hipStreamSynchronize(st));                     // blocking: the pages go back (Pages) only after the last kernel that reads them
+    pages.queued = false;
+    return NTTS_OK;
+}
+
+extern "C" int ntts_backbone_read_score_logits(ntts_backbone* e, int64_t row, float* out, int32_t n) {
+    if (!e || !out || n < 1) return NTTS_EINVAL;
+    if (!e->sc_logits) return fail(e, NTTS_ESTATE, "no score rows are kept: call ntts_backbone_set_debug(e, 1), then ntts_backbone_score");
+    if (row < 0 || row >= e->sc_logits_rows) return fail(e, NTTS_EINVAL, "score row %ld outside [0, %ld)", (long)row, e->sc_logits_rows);
+    HIPCHK(e, hipSetDevice(e->device));
+    if (n > e->cfg.vocab_size) n = e->cfg.vocab_size;
+    HIPCHK(e, hipMemcpy(out, e->sc_logits + (size_t)row * e->cfg.vocab_size, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+    return NTTS_OK;
 }
 
 extern "C" int ntts_backbone_kv_stats(ntts_backbone* e, int32_t* free_pages, int32_t* total_pages, int64_t* prompt_tokens_computed,

@@ -8,6 +8,7 @@
 #include "kernels/gemv.h"
 #include "kernels/norm.h"
 #include "kernels/sample.h"
+#include "kernels/score.h"
 
 #include <string.h>
 
@@ -424,6 +425,43 @@ extern "C" int ntts_k_mfma_probe(float* out_dev_768) {
     return hipDeviceSynchronize() == hipSuccess ? NTTS_OK : NTTS_EHIP;
 }
 
+// ---- operands of the lm_head probes, packed by the kernels the engine packs its head with: W [N][K] bf16 row-major -> tile-major bf16, or (fp8) e4m3
+//      bytes + per-row scales, X then quantised to e4m3 at the static scale xscale.  *X_out = the rows the launch reads.
+namespace {
+struct ProbeBuf { void* p = nullptr; ~ProbeBuf() { if (p) (void)hipFree(p); } };
+bool probe_alloc(ProbeBuf& b, size_t bytes) { return hipMalloc(&b.p, bytes) == hipSuccess && hipMemset(b.p, 0, bytes) == hipSuccess; }
+struct ProbeOperands { ProbeBuf wt, ws, xq, xf; };
+int pack_probe_operands(const void* X_dev, const void* W_dev, int M, int N, int K, int fp8, float xscale, ProbeOperands& o, const bf16_t** X_out) {
+    const long Np = ((long)N + 63) / 64 * 64;
+    const hipStream_t st = (hipStream_t)0;
+    if (!probe_alloc(o.wt, (size_t)Np * K * (fp8 ? 1 : 2))) return NTTS_ENOMEM;
+    // (plain pointers for the launches: the emulator's launch captures its arguments by value)
+    const void* src = W_dev;
+    const int* nomap = nullptr;
+    if (fp8) {
+        if (!probe_alloc(o.ws, (size_t)Np * 4) || !probe_alloc(o.xq, (size_t)M * K) || !probe_alloc(o.xf, (size_t)M * K * 4)) return NTTS_ENOMEM;
+        unsigned char* dst = (unsigned char*)o.wt.p;
+        float* sc = (float*)o.ws.p;
+        NTTS_LAUNCH((pack_weight_fp8_kernel), dim3((unsigned)N), dim3(256), st, src, 0, dst, sc, nomap, 0L, (long)K);
+        std::vector<bf16_t> xb((size_t)M * K);
+        std::vector<float> xw((size_t)M * K);
+        if (hipMemcpy(xb.data(), X_dev, xb.size() * 2, hipMemcpyDeviceToHost) != hipSuccess) return NTTS_EHIP;
+        for (size_t i = 0; i < xb.size(); ++i) { const unsigned int u = (unsigned int)xb[i] << 16; memcpy(&xw[i], &u, 4); }
+        if (hipMemcpy(o.xf.p, xw.data(), xw.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return NTTS_EHIP;
+        const float* xin = (const float*)o.xf.p;
+        unsigned char* xout = (unsigned char*)o.xq.p;
+        const long nx = (long)M * K;
+        NTTS_LAUNCH((fp8_quantize_kernel), dim3((unsigned)((nx + 511) / 512)), dim3(256), st, xin, xout, nx, 1.0f / xscale);
+        *X_out = (const bf16_t*)o.xq.p;
+    } else {
+        bf16_t* dst = (bf16_t*)o.wt.p;
+        NTTS_LAUNCH((pack_weight_kernel), dim3((unsigned)N), dim3(256), st, src, 0, dst, nomap, 0L, (long)K, 1);
+        *X_out = (const bf16_t*)X_dev;
+    }
+    return NTTS_OK;
+}
+}  // namespace
+
 // ---- the lm_head launch of the decode step (gemm.h lm_head_launch / gemv.h lm_head_gemv_launch) on caller-supplied operands: the penalty epilogue of
 //      every tile variant against tests/repetition_spec.py.  The head is packed here by the kernels the engine packs it with.
 //      part_sum / row_lse non-null (ntts_k_head_logprob_probe): the launch with the log-sum-exp epilogue, then sample.h's own merge of the partials.
@@ -444,37 +482,17 @@ static int head_probe(const void* X_dev, const void* W_dev, int32_t M, int32_t N
     const int width = variant == 8 ? 16 : variant == 4 ? 96 : 64;
     const int np = variant == 8 ? N / 16 : variant == 0 ? (N + 63) / 64 : variant == 4 ? ((N + 287) / 288) * 3 : variant == 2 ? ((N + 255) / 256) * 4 : ((N + 127) / 128) * 2;
     if (part_cap < np) return NTTS_EINVAL;
-    const long Np = ((long)N + 63) / 64 * 64, ldl = ((long)N + 7) / 8 * 8, pitch = seen_pitch_for(N), wsrc = ((long)N + 31) / 32;
-    const size_t esz = fp8 ? 1 : 2;
-    struct Buf { void* p = nullptr; ~Buf() { if (p) (void)hipFree(p); } };
-    Buf wt, ws, xq, xf, lg, lb, pv, pi, bm, pen, me, psum, rl;
-    auto dalloc = [](Buf& b, size_t bytes) { return hipMalloc(&b.p, bytes) == hipSuccess && hipMemset(b.p, 0, bytes) == hipSuccess; };
-    if (!dalloc(wt, (size_t)Np * K * esz) || !dalloc(lg, (size_t)M * N * 4) || !dalloc(lb, (size_t)M * ldl * 2) || !dalloc(pv, (size_t)M * np * 4) ||
+    const long ldl = ((long)N + 7) / 8 * 8, pitch = seen_pitch_for(N), wsrc = ((long)N + 31) / 32;
+    typedef ProbeBuf Buf;
+    ProbeOperands ops;
+    Buf lg, lb, pv, pi, bm, pen, me, psum, rl;
+    auto dalloc = [](Buf& b, size_t bytes) { return probe_alloc(b, bytes); };
+    if (!dalloc(lg, (size_t)M * N * 4) || !dalloc(lb, (size_t)M * ldl * 2) || !dalloc(pv, (size_t)M * np * 4) ||
         !dalloc(pi, (size_t)M * np * 4) || !dalloc(me, (size_t)M * 4)) return NTTS_ENOMEM;
     if (part_sum && (!dalloc(psum, (size_t)M * np * 4) || !dalloc(rl, (size_t)M * 2 * 4))) return NTTS_ENOMEM;
     const hipStream_t st = (hipStream_t)0;
-    {   // (plain pointers for the launches: the emulator's launch captures its arguments by value)
-        const void* src = W_dev;
-        const int* nomap = nullptr;
-        if (fp8) {
-            if (!dalloc(ws, (size_t)Np * 4) || !dalloc(xq, (size_t)M * K) || !dalloc(xf, (size_t)M * K * 4)) return NTTS_ENOMEM;
-            unsigned char* dst = (unsigned char*)wt.p;
-            float* sc = (float*)ws.p;
-            NTTS_LAUNCH((pack_weight_fp8_kernel), dim3((unsigned)N), dim3(256), st, src, 0, dst, sc, nomap, 0L, (long)K);
-            std::vector<bf16_t> xb((size_t)M * K);
-            std::vector<float> xw((size_t)M * K);
-            if (hipMemcpy(xb.data(), X_dev, xb.size() * 2, hipMemcpyDeviceToHost) != hipSuccess) return NTTS_EHIP;
-            for (size_t i = 0; i < xb.size(); ++i) { const unsigned int u = (unsigned int)xb[i] << 16; memcpy(&xw[i], &u, 4); }
-            if (hipMemcpy(xf.p, xw.data(), xw.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return NTTS_EHIP;
-            const float* xin = (const float*)xf.p;
-            unsigned char* xout = (unsigned char*)xq.p;
-            const long nx = (long)M * K;
-            NTTS_LAUNCH((fp8_quantize_kernel), dim3((unsigned)((nx + 511) / 512)), dim3(256), st, xin, xout, nx, 1.0f / xscale);
-        } else {
-            bf16_t* dst = (bf16_t*)wt.p;
-            NTTS_LAUNCH((pack_weight_kernel), dim3((unsigned)N), dim3(256), st, src, 0, dst, nomap, 0L, (long)K, 1);
-        }
-    }
+    const bf16_t* X = nullptr;
+    if (const int rc = pack_probe_operands(X_dev, W_dev, M, N, K, fp8, xscale, ops, &X)) return rc;
     if (mask_eos && hipMemcpy(me.p, mask_eos, (size_t)M * 4, hipMemcpyHostToDevice) != hipSuccess) return NTTS_EHIP;
     if (seen) {
         if (!dalloc(bm, (size_t)M * pitch * 4) || !dalloc(pen, (size_t)M * 4)) return NTTS_ENOMEM;
@@ -488,11 +506,10 @@ static int head_probe(const void* X_dev, const void* W_dev, int32_t M, int32_t N
         }
         if (hipMemcpy(pen.p, rep_pen, (size_t)M * 4, hipMemcpyHostToDevice) != hipSuccess) return NTTS_EHIP;
     }
-    const bf16_t* X = fp8 ? (const bf16_t*)xq.p : (const bf16_t*)X_dev;
     if (variant == 8) {
         GemvArgs a{};
-        a.X = X; a.ldx = K; a.W = (const bf16_t*)wt.p; a.ldw = K; a.w_tile_major = 1; a.slab_rows = M; a.M = M; a.N = N; a.K = K; a.n_valid = N;
-        a.wscale = fp8 ? (const float*)ws.p : nullptr; a.xscale = xscale;
+        a.X = X; a.ldx = K; a.W = (const bf16_t*)ops.wt.p; a.ldw = K; a.w_tile_major = 1; a.slab_rows = M; a.M = M; a.N = N; a.K = K; a.n_valid = N;
+        a.wscale = fp8 ? (const float*)ops.ws.p : nullptr; a.xscale = xscale;
         a.part_val = (float*)pv.p; a.part_idx = (int*)pi.p; a.mask_eos = (const int*)me.p;
         a.logits = (float*)lg.p; a.ld_logits = N; a.logits_bf16 = (bf16_t*)lb.p; a.ld_logits_bf16 = ldl;
         if (seen) { a.seen = (const unsigned int*)bm.p; a.seen_pitch = pitch; a.rep_pen = (const float*)pen.p; }
@@ -501,8 +518,8 @@ static int head_probe(const void* X_dev, const void* W_dev, int32_t M, int32_t N
     } else {
         GemmArgs a{};
         a.w_tile_major = 1;
-        a.X = X; a.ldx = K; a.W = (const bf16_t*)wt.p; a.ldw = K; a.M = M; a.N = N; a.K = K;
-        a.wscale = fp8 ? (const float*)ws.p : nullptr; a.xscale = xscale;
+        a.X = X; a.ldx = K; a.W = (const bf16_t*)ops.wt.p; a.ldw = K; a.M = M; a.N = N; a.K = K;
+        a.wscale = fp8 ? (const float*)ops.ws.p : nullptr; a.xscale = xscale;
         a.part_val = (float*)pv.p; a.part_idx = (int*)pi.p; a.mask_eos = (const int*)me.p;
         a.logits = (float*)lg.p; a.ld_logits = N; a.logits_bf16 = (bf16_t*)lb.p; a.ld_logits_bf16 = ldl;
         if (seen) { a.seen = (const unsigned int*)bm.p; a.seen_pitch = pitch; a.rep_pen = (const float*)pen.p; }
@@ -544,6 +561,58 @@ extern "C" int ntts_k_head_logprob_probe(const void* X_dev, const void* W_dev, i
     if (!part_sum || !row_lse) return NTTS_EINVAL;
     return head_probe(X_dev, W_dev, M, N, K, variant, fp8, xscale, seen, rep_pen, mask_eos, logits_out, logits_bf16_out, part_val, part_idx, part_cap,
                       n_part, part_width, part_sum, row_lse);
+}
+
+// ---- the scoring launch (backbone.cpp ntts_backbone_score: lm_head_launch with a target column per row, then score.h's merge) on caller-supplied
+//      operands, packed as head_probe packs them.  target_val and the merged outputs start as NaN / -1: a capture or a row that is missed shows.
+extern "C" int ntts_k_head_score_probe(const void* X_dev, const void* W_dev, int32_t M, int32_t N, int32_t K, int32_t variant, int32_t fp8, float xscale,
+                                       const int32_t* target, float* logits_out, float* part_val, int32_t* part_idx, float* part_sum, int32_t part_cap,
+                                       int32_t* n_part, int32_t* part_width, float* target_val, float* logprob, int32_t* argmax, float* argmax_logprob) {
+    if (!X_dev || !W_dev || !target || !logits_out || !part_val || !part_idx || !part_sum || !n_part || !part_width || !target_val || !logprob ||
+        !argmax || !argmax_logprob) return NTTS_EINVAL;
+    if (M < 1 || N < 16 || K < 64 || (K % 64) || (fp8 && (K % 128))) return NTTS_EINVAL;
+    if ((variant != 0 && variant != 1 && variant != 2 && variant != 4) || (variant == 4 && fp8)) return NTTS_EINVAL;
+    if (fp8 && !(xscale > 0.f)) return NTTS_EINVAL;
+    for (int m = 0; m < M; ++m)
+        if (target[m] < 0 || target[m] >= N) return NTTS_EINVAL;
+    const int width = variant == 4 ? 96 : 64;
+    const int np = variant == 0 ? (N + 63) / 64 : variant == 4 ? ((N + 287) / 288) * 3 : variant == 2 ? ((N + 255) / 256) * 4 : ((N + 127) / 128) * 2;
+    if (part_cap < np) return NTTS_EINVAL;
+    ProbeOperands ops;
+    ProbeBuf lg, pv, pi, psum, tg, outs;
+    if (!probe_alloc(lg, (size_t)M * N * 4) || !probe_alloc(pv, (size_t)M * np * 4) || !probe_alloc(pi, (size_t)M * np * 4) ||
+        !probe_alloc(psum, (size_t)M * np * 4) || !probe_alloc(tg, (size_t)M * 4) || !probe_alloc(outs, (size_t)M * 4 * 4)) return NTTS_ENOMEM;
+    const hipStream_t st = (hipStream_t)0;
+    const bf16_t* X = nullptr;
+    if (const int rc = pack_probe_operands(X_dev, W_dev, M, N, K, fp8, xscale, ops, &X)) return rc;
+    // outs: [target_val | logprob | argmax | argmax_logprob], M entries each; NaN bits (argmax: -1) ahead of the launch
+    std::vector<uint32_t> init((size_t)M * 4, 0x7fc00000u);
+    for (int m = 0; m < M; ++m) init[(size_t)2 * M + m] = 0xffffffffu;
+    if (hipMemcpy(tg.p, target, (size_t)M * 4, hipMemcpyHostToDevice) != hipSuccess) return NTTS_EHIP;
+    if (hipMemcpy(outs.p, init.data(), init.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return NTTS_EHIP;
+    float* o = (float*)outs.p;
+    GemmArgs a{};
+    a.w_tile_major = 1;
+    a.X = X; a.ldx = K; a.W = (const bf16_t*)ops.wt.p; a.ldw = K; a.M = M; a.N = N; a.K = K;
+    a.wscale = fp8 ? (const float*)ops.ws.p : nullptr; a.xscale = xscale;
+    a.part_val = (float*)pv.p; a.part_idx = (int*)pi.p; a.part_sum = (float*)psum.p;
+    a.logits = (float*)lg.p; a.ld_logits = N;
+    a.target = (const int*)tg.p; a.target_val = o;
+    lm_head_launch(a, variant, fp8 != 0, st);
+    ScoreMergeArgs sm{(const float*)pv.p, (const int*)pi.p, (const float*)psum.p, np, o, o + M, (int*)(o + 2 * (size_t)M), o + 3 * (size_t)M};
+    NTTS_LAUNCH((score_merge_kernel), dim3((unsigned)M), dim3(256), st, sm);
+    if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess) return NTTS_EHIP;
+    if (hipMemcpy(logits_out, lg.p, (size_t)M * N * 4, hipMemcpyDeviceToHost) != hipSuccess) return NTTS_EHIP;
+    if (hipMemcpy(part_val, pv.p, (size_t)M * np * 4, hipMemcpyDeviceToHost) != hipSuccess) return NTTS_EHIP;
+    if (hipMemcpy(part_idx, pi.p, (size_t)M * np * 4, hipMemcpyDeviceToHost) != hipSuccess) return NTTS_EHIP;
+    if (hipMemcpy(part_sum, psum.p, (size_t)M * np * 4, hipMemcpyDeviceToHost) != hipSuccess) return NTTS_EHIP;
+    if (hipMemcpy(target_val, o, (size_t)M * 4, hipMemcpyDeviceToHost) != hipSuccess) return NTTS_EHIP;
+    if (hipMemcpy(logprob, o + M, (size_t)M * 4, hipMemcpyDeviceToHost) != hipSuccess) return NTTS_EHIP;
+    if (hipMemcpy(argmax, o + 2 * (size_t)M, (size_t)M * 4, hipMemcpyDeviceToHost) != hipSuccess) return NTTS_EHIP;
+    if (hipMemcpy(argmax_logprob, o + 3 * (size_t)M, (size_t)M * 4, hipMemcpyDeviceToHost) != hipSuccess) return NTTS_EHIP;
+    *n_part = np;
+    *part_width = width;
+    return NTTS_OK;
 }
 
 // ---- attention probes: the decode launch of one form and one layer's prompt-pass attention (writer + the three tiers over the engine's own work

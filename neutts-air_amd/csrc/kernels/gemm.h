@@ -40,12 +40,15 @@ enum GemmEpi {
                          // EOS mask then overwrites its column as before (-inf either way: the two commute for any valid penalty).  A kernel
                          // of its own, launched only while a penalised request is live: the plain lm_head keeps its instructions and its registers
     EPI_ARGMAX_LSE = 9,      // EPI_ARGMAX / EPI_ARGMAX_PEN that also leave GemmArgs::part_sum = sum of exp(v - partial max) over the partial's in-range columns,
-    EPI_ARGMAX_PEN_LSE = 10  // v = the processed value the dump, the bf16 row and the max see: the log-sum-exp of the row, carried through the partials to the
+    EPI_ARGMAX_PEN_LSE = 10, // v = the processed value the dump, the bf16 row and the max see: the log-sum-exp of the row, carried through the partials to the
                              // sampling kernel (per-token log-probabilities).  Kernels of their own again, launched only while ntts_backbone_set_logprobs is on
+    EPI_ARGMAX_LSE_TGT = 11  // EPI_ARGMAX_LSE that also leaves GemmArgs::target_val[m] = the processed logit of column GemmArgs::target[m]: scoring of GIVEN
+                             // tokens (ntts_backbone_score; score.h merges the partials).  Kernels of their own once more, launched by a score call only
 };
-constexpr bool epi_is_argmax(int epi) { return epi == EPI_ARGMAX || epi == EPI_ARGMAX_PEN || epi == EPI_ARGMAX_LSE || epi == EPI_ARGMAX_PEN_LSE; }
+constexpr bool epi_is_argmax(int epi) { return epi == EPI_ARGMAX || epi == EPI_ARGMAX_PEN || epi == EPI_ARGMAX_LSE || epi == EPI_ARGMAX_PEN_LSE || epi == EPI_ARGMAX_LSE_TGT; }
 constexpr bool epi_has_pen(int epi) { return epi == EPI_ARGMAX_PEN || epi == EPI_ARGMAX_PEN_LSE; }
-constexpr bool epi_has_lse(int epi) { return epi == EPI_ARGMAX_LSE || epi == EPI_ARGMAX_PEN_LSE; }
+constexpr bool epi_has_lse(int epi) { return epi == EPI_ARGMAX_LSE || epi == EPI_ARGMAX_PEN_LSE || epi == EPI_ARGMAX_LSE_TGT; }
+constexpr bool epi_has_tgt(int epi) { return epi == EPI_ARGMAX_LSE_TGT; }
 
 struct GemmArgs {
     const bf16_t* X;
@@ -108,6 +111,9 @@ struct GemmArgs {
                               // 1 first ring slots requested, 2 first tile landed (past the first barrier), 3 k-loop done, 4 epilogue issued, 5 stores drained
     // EPI_ARGMAX_LSE / EPI_ARGMAX_PEN_LSE (last, so that no other field moves)
     float* part_sum;          // [M][part_stride], beside part_val: sum over the partial's columns n < N of exp(v - part_val); 0 when part_val is -inf
+    // EPI_ARGMAX_LSE_TGT (appended for the same reason)
+    const int* target;        // [M] a column in [0, N) per row
+    float* target_val;        // [M] the processed (bf16-valued) logit of that column, stored by the one lane that owns (row, target[row])
 };
 
 // position t of the grouped tile order (8 m-blocks x all n-blocks per group, m fastest) -> tile coordinates
@@ -398,6 +404,8 @@ NTTS_D void gemm_epilogue(const GemmArgs& p, f32x4 (&acc)[TM][4], int mrow0, int
                             if ((sbits >> (j * 4 + r)) & 1u) acc[a][j][r] = rep_penalised(rbf(acc[a][j][r]), pen);
                 }
             }
+            int tgt = -1;                                          // (no column: a row past M never stores)
+            if constexpr (epi_has_tgt(EPI)) { if (mok) tgt = p.target[m]; }
             alignas(16) bf16_t lo[16];
 #pragma unroll
             for (int j = 0; j < 4; ++j)
@@ -407,6 +415,7 @@ NTTS_D void gemm_epilogue(const GemmArgs& p, f32x4 (&acc)[TM][4], int mrow0, int
                     float v = rbf(acc[a][j][r]);                  // lm_head output is bf16, then .float()
                     if (meos && n == (p.eos_col1 > 0 ? p.eos_col1 - 1 : meos - 1)) v = -INFINITY;
                     lo[j * 4 + r] = f2bf(v);
+                    if constexpr (epi_has_tgt(EPI)) { if (n == tgt) p.target_val[m] = v; }   // one lane of one workgroup per row (target < N)
                     if (n < p.N) {
                         if (mok && p.logits) p.logits[(long)m * p.ld_logits + n] = v;
                         if (v > best) { best = v; bidx = n; }      // ascending n + strict '>' = first max wins
@@ -501,6 +510,8 @@ NTTS_D void gemm_epilogue_nat(const GemmArgs& p, f32x4 (&acc)[TM][TN], int mrow0
                             if ((sw[j >> 1] >> ((j & 1) * 16 + g * 4 + r)) & 1u) acc[a][j][r] = rep_penalised(rbf(acc[a][j][r]), pen);
                 }
             }
+            int tgt = -1;                                          // (no column: a row past M never stores)
+            if constexpr (epi_has_tgt(EPI)) { if (mok) tgt = p.target[m]; }
 #pragma unroll
             for (int j = 0; j < TN; ++j) {
                 alignas(8) bf16_t lo[4];
@@ -510,6 +521,7 @@ NTTS_D void gemm_epilogue_nat(const GemmArgs& p, f32x4 (&acc)[TM][TN], int mrow0
                     float v = rbf(acc[a][j][r]);                  // lm_head output is bf16, then .float()
                     if (meos && n == (p.eos_col1 > 0 ? p.eos_col1 - 1 : meos - 1)) v = -INFINITY;
                     lo[r] = f2bf(v);
+                    if constexpr (epi_has_tgt(EPI)) { if (n == tgt) p.target_val[m] = v; }   // one lane of one workgroup per row (target < N)
                     if (n < p.N) {
                         if (mok && p.logits) p.logits[(long)m * p.ld_logits + n] = v;
                         if (v > best) { best = v; bidx = n; }      // ascending n + strict '>' = first max wins
@@ -831,7 +843,7 @@ inline void gemm_launch(GemmArgs p, int ksplit, hipStream_t s) {
 // The decode lm_head (backbone.cpp k_lm_head; kapi.cpp ntts_k_head_penalty_probe runs the same launch on caller-supplied data).  head_tile: 0 = 64 x 64
 // skinny / 4-slot ring, 1 = 128 x 128, 2 = 256 x 256 (16 waves), 4 = natural-order 256 x 288 (12 waves, bf16 only); the 256-row tiles stream W with the
 // non-temporal policy (read once per step).  a.seen != null selects the kernels with the repetition penalty in their epilogue, a.part_sum != null
-// those that also reduce the row's log-sum-exp.
+// those that also reduce the row's log-sum-exp, a.target != null (with part_sum and target_val) the scoring kernels.
 template <int EPI>
 inline void lm_head_launch_epi(const GemmArgs& a, int head_tile, bool fp8, hipStream_t s) {
     switch (head_tile) {
@@ -850,7 +862,9 @@ inline void lm_head_launch_epi(const GemmArgs& a, int head_tile, bool fp8, hipSt
     }
 }
 inline void lm_head_launch(const GemmArgs& a, int head_tile, bool fp8, hipStream_t s) {
-    if (a.part_sum) {           // per-token log-probabilities on: the kernels whose epilogue also leaves the partial sums of exp
+    if (a.target) {             // scoring of given tokens (never set by the decode step): log-sum-exp partials + the target column's logit
+        lm_head_launch_epi<EPI_ARGMAX_LSE_TGT>(a, head_tile, fp8, s);
+    } else if (a.part_sum) {           // per-token log-probabilities on: the kernels whose epilogue also leaves the partial sums of exp
         if (a.seen) lm_head_launch_epi<EPI_ARGMAX_PEN_LSE>(a, head_tile, fp8, s);
         else lm_head_launch_epi<EPI_ARGMAX_LSE>(a, head_tile, fp8, s);
     } else if (a.seen) lm_head_launch_epi<EPI_ARGMAX_PEN>(a, head_tile, fp8, s);

@@ -144,6 +144,9 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "ntts_backbone_set_logprobs": (C.c_int, [p, i32]),
         "ntts_backbone_read_logprobs": (C.c_int, [p, i32, C.POINTER(f32), i32, C.POINTER(i32)]),
         "ntts_backbone_read_finished_logprobs": (C.c_int, [p, i32, C.POINTER(f32), i32, C.POINTER(i32)]),
+        "ntts_backbone_score": (C.c_int, [p, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), i32, C.POINTER(f32),
+                                          C.POINTER(i32), C.POINTER(f32), i64, C.POINTER(i64)]),
+        "ntts_backbone_read_score_logits": (C.c_int, [p, i64, C.POINTER(f32), i32]),
         "ntts_backbone_debug_force": (C.c_int, [p, i32, i32]),
         "ntts_backbone_last_timing": (C.c_int, [p, C.POINTER(f32), C.POINTER(f32)]),
         "ntts_backbone_step_bytes": (C.c_int, [p, C.POINTER(C.c_double)]),
@@ -185,6 +188,9 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "ntts_k_head_logprob_probe": (C.c_int, [p, p, i32, i32, i32, i32, i32, f32, C.POINTER(C.c_uint32), C.POINTER(f32), C.POINTER(i32),
                                                 C.POINTER(f32), C.POINTER(C.c_uint16), C.POINTER(f32), C.POINTER(i32), C.POINTER(f32), i32,
                                                 C.POINTER(i32), C.POINTER(i32), C.POINTER(f32)]),
+        "ntts_k_head_score_probe": (C.c_int, [p, p, i32, i32, i32, i32, i32, f32, C.POINTER(i32), C.POINTER(f32), C.POINTER(f32), C.POINTER(i32),
+                                              C.POINTER(f32), i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(f32), C.POINTER(f32), C.POINTER(i32),
+                                              C.POINTER(f32)]),
         "ntts_k_attn_decode_form": (C.c_int, [i32, i32, i32, i32, i32]),
         "ntts_k_attn_decode_probe": (C.c_int, [p, i64, p, f32, p, p, i32, p, i32, p, p, i32, i32, i32, i32, i32, i32, i32, i32, p]),
         "ntts_k_attn_prefill_probe": (C.c_int, [p, i64, p, f32, p, p, i32, p, i32, i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32),
@@ -313,6 +319,31 @@ def head_logprob_probe(lib, x_ptr: int, w_ptr: int, M: int, N: int, K: int, vari
     Returns head_penalty_probe's five values, then part_sum [M][n_part] (sum over the partial's columns of exp(v - its maximum); 0 where that is -inf)
     and per row M (the row maximum) and log S as the sampling kernel's own merge computes them: logsumexp(row) = M + log S."""
     return head_penalty_probe(lib, x_ptr, w_ptr, M, N, K, variant, seen, rep_pen, mask_eos, fp8, xscale, _lse=True)
+
+
+def head_score_probe(lib, x_ptr: int, w_ptr: int, M: int, N: int, K: int, variant: int, target, fp8: bool = False, xscale: float = 1.0):
+    """ntts_k_head_score_probe: the scoring launch (the lm_head tile `variant` with the target-capture epilogue, then the merge kernel) on DEVICE bf16
+    X [M][K] and W [N][K]; target: [M] columns in [0, N).  Returns a dict: logits fp32 [M][N], part_val / part_idx / part_sum [M][n_part], width
+    (columns per partial), target_val [M], and the merged logprob / argmax / argmax_logprob [M].  The last four start as NaN (argmax: -1) on the device."""
+    tg = np.ascontiguousarray(target, dtype=np.int32).reshape(M)
+    cap = N // 16 + 16
+    logits = np.zeros((M, N), dtype=np.float32)
+    pv, ps = np.zeros((M, cap), dtype=np.float32), np.zeros((M, cap), dtype=np.float32)
+    pi = np.zeros((M, cap), dtype=np.int32)
+    tv, lp, alp = (np.zeros(M, dtype=np.float32) for _ in range(3))
+    am = np.zeros(M, dtype=np.int32)
+    n_part, width = C.c_int32(), C.c_int32()
+    i32p, f32p = C.POINTER(C.c_int32), C.POINTER(C.c_float)
+    rc = lib.ntts_k_head_score_probe(C.c_void_p(x_ptr), C.c_void_p(w_ptr), M, N, K, variant, int(fp8), xscale, tg.ctypes.data_as(i32p),
+                                     logits.ctypes.data_as(f32p), pv.ctypes.data_as(f32p), pi.ctypes.data_as(i32p), ps.ctypes.data_as(f32p), cap,
+                                     C.byref(n_part), C.byref(width), tv.ctypes.data_as(f32p), lp.ctypes.data_as(f32p), am.ctypes.data_as(i32p),
+                                     alp.ctypes.data_as(f32p))
+    if rc != 0:
+        raise NeuTTSHipError(rc, "ntts_k_head_score_probe")
+    n = n_part.value
+    cut = lambda a: a.reshape(-1)[: M * n].reshape(M, n).copy()     # (the library wrote rows of n_part entries back to back)
+    return dict(logits=logits, part_val=cut(pv), part_idx=cut(pi), part_sum=cut(ps), width=width.value, target_val=tv, logprob=lp, argmax=am,
+                argmax_logprob=alp)
 
 
 class BackboneEngine:
@@ -535,6 +566,67 @@ class BackboneEngine:
         n = C.c_int32()
         self._chk(self.lib.ntts_backbone_read_finished_logprobs(self.h, slot, out.ctypes.data_as(C.POINTER(C.c_float)), len(out), C.byref(n)))
         return out[: n.value].copy()
+
+    def score_call(self, seqs, slots: Sequence[int], score_from: Sequence[int], chunk_rows: int = 0):
+        """One ntts_backbone_score call (include/neutts_hip.h has the definition): `seqs` on the FREE slots `slots`, sequence i scored from position
+        score_from[i].  Blocking; the slots and their KV pages are free again on return.  Returns the packed (logprobs, argmax ids, argmax logprobs)."""
+        lens = np.ascontiguousarray([len(q) for q in seqs], dtype=np.int32)
+        ids = np.ascontiguousarray(np.concatenate([np.asarray(q, dtype=np.int64) for q in seqs]) if len(seqs) else [], dtype=np.int32)
+        sl = np.ascontiguousarray(slots, dtype=np.int32)
+        sf = np.ascontiguousarray(score_from, dtype=np.int32)
+        if not (len(lens) == len(sl) == len(sf)):
+            raise ValueError("score_call: one slot and one score_from per sequence")
+        cap = int(max(0, int((lens.astype(np.int64) - sf).clip(min=0).sum())))
+        lp, alp = np.empty(cap, dtype=np.float32), np.empty(cap, dtype=np.float32)
+        am = np.empty(cap, dtype=np.int32)
+        n = C.c_int64()
+        i32p, f32p = C.POINTER(C.c_int32), C.POINTER(C.c_float)
+        self._chk(self.lib.ntts_backbone_score(self.h, len(lens), ids.ctypes.data_as(i32p), lens.ctypes.data_as(i32p), sl.ctypes.data_as(i32p),
+                                               sf.ctypes.data_as(i32p), int(chunk_rows), lp.ctypes.data_as(f32p), am.ctypes.data_as(i32p),
+                                               alp.ctypes.data_as(f32p), cap, C.byref(n)))
+        return lp[: n.value], am[: n.value], alp[: n.value]
+
+    def score(self, seqs, score_from=None, chunk_rows: int = 0):
+        """Teacher-forced scoring of given token sequences: for each, the model's log-probability of tokens score_from .. len - 1 given the ones before
+        (score_from: None = 1, an int for all, or one per sequence).  No logits processor enters; see include/neutts_hip.h.  The sequences are packed
+        into as many calls as max_prefill_tokens and the free decode slots require; running requests are not touched, and a sequence's values are
+        bit-identical for every chunk_rows and whichever sequences share its call (one lm_head tile per engine).  chunk_rows above 8192 or
+        max_prefill_tokens is taken as the smaller of the two.  Returns one
+        (logprobs float32, argmax_ids int32, argmax_logprobs float32) triple of numpy arrays per sequence, len - score_from entries each."""
+        seqs = [list(q) for q in seqs]
+        if score_from is None:
+            sf = [1] * len(seqs)
+        elif isinstance(score_from, (int, np.integer)):
+            sf = [int(score_from)] * len(seqs)
+        else:
+            sf = [int(v) for v in score_from]
+        if len(sf) != len(seqs):
+            raise ValueError("score: one score_from per sequence")
+        tmax = int(self.cfg.get("max_prefill_tokens", 0) or 16384)
+        out = [None] * len(seqs)
+        i = 0
+        while i < len(seqs):
+            if not self._free:
+                raise NeuTTSHipError(-4, "score: no free decode slot")
+            j, tok = i, 0
+            while j < len(seqs) and j - i < len(self._free) and (j == i or tok + len(seqs[j]) <= tmax):
+                tok += len(seqs[j])
+                j += 1
+            slots = self._free[-1: -(j - i) - 1: -1]          # borrowed for the call only: the library leaves them free
+            lp, am, alp = self.score_call(seqs[i:j], slots, sf[i:j], chunk_rows)
+            o = 0
+            for k in range(i, j):
+                m = len(seqs[k]) - sf[k]
+                out[k] = (lp[o:o + m].copy(), am[o:o + m].copy(), alp[o:o + m].copy())
+                o += m
+            i = j
+        return out
+
+    def read_score_logits(self, row: int) -> np.ndarray:
+        """Debug tap (set_debug(True) before the score call): the fp32 lm_head row behind output entry `row` of the most recent score_call."""
+        out = np.empty(self.vocab_size, dtype=np.float32)
+        self._chk(self.lib.ntts_backbone_read_score_logits(self.h, int(row), out.ctypes.data_as(C.POINTER(C.c_float)), len(out)))
+        return out
 
     def read_all_array(self):
         """Every slot's new ids in one call, as arrays: (ids [max_batch, max_context] int32 -- row s valid up to n[s]),

@@ -479,6 +479,69 @@ class NeuTTS:
         prompts = [self._apply_chat_template(rc, rt, t) for rc, rt, t in zip(ref_codes, ref_texts, texts)]
         return self._infer_stream_batch_hip(prompts, [[int(c) for c in _to_list(rc)] for rc in ref_codes], samp)
 
+    def score(self, text: str, codes, ref_codes, ref_text: str, include_eos: bool = True) -> Dict[str, object]:
+        """Teacher-forced score of an EXISTING utterance: the model's log-probability of every speech token of `codes` (and, with include_eos, of
+        `<|SPEECH_GENERATION_END|>` behind them) given the prompt `infer` would build for (text, ref_codes, ref_text) and the codes before it.
+        No sampling setting and no logits processor enters (include/neutts_hip.h: ntts_backbone_score).  Returns dict(logprobs = float32 array,
+        score = their mean as `sequence_score` computes it, top1_agreement = the fraction of positions where the model's argmax is the given
+        token).  For filtering or ranking utterances, re-scoring candidates of another run, and comparing two builds on the same sequences."""
+        return self.score_batch([text], [codes], ref_codes, ref_text, include_eos)[0]
+
+    def score_batch(self, texts: Sequence[str], codes, ref_codes, ref_texts, include_eos: bool = True) -> List[Dict[str, object]]:
+        """`score` for many utterances: one reference for all (ref_texts a string) or one per utterance, as `infer_batch` takes them.  The engine
+        packs the sequences into as few prompt passes as its max_prefill_tokens and free decode slots allow; an utterance's values do not depend on
+        what it is packed with.  RuntimeError on an instance with the restricted lm_head (speech_range_head=True): a score is over the whole vocabulary."""
+        if not isinstance(include_eos, (bool, np.bool_)):
+            raise ValueError(f"include_eos must be True or False (got {include_eos!r})")
+        if getattr(self.backbone, "logits_range", None):
+            raise RuntimeError("score needs the whole vocabulary: this instance runs the restricted lm_head (speech_range_head=True / set_logits_range); "
+                               "build it without, or call backbone.set_logits_range(None) first")
+        texts = list(texts)
+        def as_list(c):      # (not _to_list: it would turn 2.5 or True into a code)
+            if hasattr(c, "tolist"):
+                a = np.asarray(c.cpu() if hasattr(c, "cpu") else c).reshape(-1)
+                if a.dtype.kind not in "iu":
+                    raise ValueError(f"codes must be integers (got dtype {a.dtype})")
+                return a.tolist()
+            return list(c)
+        codes = [as_list(c) for c in codes]
+        if len(codes) != len(texts):
+            raise ValueError(f"codes: {len(codes)} sequences for {len(texts)} utterances")
+        if not isinstance(ref_texts, (list, tuple)):
+            ref_texts = [ref_texts] * len(texts)
+            ref_codes = [ref_codes] * len(texts)
+        if len(ref_texts) != len(texts) or len(ref_codes) != len(texts):
+            raise ValueError(f"references: {len(ref_codes)} codes and {len(ref_texts)} texts for {len(texts)} utterances")
+        who = lambda i: f"utterance {i}: " if len(texts) > 1 else ""
+        for i, c in enumerate(codes):
+            if len(c) == 0:
+                raise ValueError(f"{who(i)}no codes to score")
+            for v in c:
+                if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or not 0 <= v < 65536:
+                    raise ValueError(f"{who(i)}codes must be integers in [0, 65536) (got {v!r})")
+        if include_eos and self._eos_id is None:
+            raise ValueError("include_eos needs the id of <|SPEECH_GENERATION_END|> (tokenizer, or 'eos_token_id' with in-memory weights)")
+        seqs, froms = [], []
+        for i, (t, c, rc, rt) in enumerate(zip(texts, codes, ref_codes, ref_texts)):
+            prompt = self._apply_chat_template(rc, rt, t)
+            ids = list(prompt) + self._codes_to_ids(c) + ([int(self._eos_id)] if include_eos else [])
+            if max(ids) >= self.backbone.vocab_size or min(ids) < 0:
+                raise ValueError(f"{who(i)}a code has no token in the model's vocabulary of {self.backbone.vocab_size}")
+            if len(ids) > self.backbone.max_context:
+                raise ValueError(f"{who(i)}prompt + codes are {len(ids)} tokens, the engine's max_context is {self.backbone.max_context}")
+            seqs.append(ids)
+            froms.append(len(prompt))
+        out = []
+        for ids, f, (lp, am, _) in zip(seqs, froms, self.backbone.score(seqs, froms)):
+            out.append(dict(logprobs=lp, score=sequence_score(lp), top1_agreement=float(np.mean(am == np.asarray(ids[f:], dtype=np.int32)))))
+        return out
+
+    def _codes_to_ids(self, codes: Sequence[int]) -> List[int]:
+        """The inverse of `_ids_to_codes`: code N -> the id of `<|speech_N|>`."""
+        if self._speech_base is not None:
+            return [int(self._speech_base) + int(c) for c in codes]
+        return list(self.tokenizer.encode("".join(f"<|speech_{int(c)}|>" for c in codes), add_special_tokens=False))
+
     def encode_reference(self, ref_audio_path: str | Path):
         """ref:neutts/neutts.py:266-271: 16 kHz mono -> `codec.encode_code` -> 1-D int codes at 50 Hz.  On the encoder engine
         (kernels/enc.h) when encoder weights are loaded; one-off per speaker, off the synthesis hot path."""
