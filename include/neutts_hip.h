@@ -476,8 +476,49 @@ int ntts_host_free(void* p);
  * host creates the lanes of an engine gang with it); destroy drains it first.  No reference counterpart (one utterance, one stream). */
 int ntts_stream_create(int32_t device, void** stream);
 int ntts_stream_destroy(int32_t device, void* stream);
-/* GPU milliseconds (hipEvents) of the most recent decode call, H2D/D2H excluded. */
+/* GPU milliseconds (hipEvents) of the most recent decode call, H2D/D2H excluded (with an output format: the output stage included; after
+ * ntts_codec_convert: that stage alone, its last round). */
 int ntts_codec_last_timing(ntts_codec* c, float* ms);
+
+/* Output stage of the codec, on the device behind overlap-add.  NEW SYMBOLS ONLY: NTTS_ABI_VERSION stays 11; ntts_codec_decode and
+ * ntts_codec_decode_dev are unchanged.
+ *
+ * The reference has no such stage: NeuCodec.decode_code hands out 24 kHz float32 (ref:neutts/neutts.py:288-291) and every consumer of another
+ * format puts torchaudio.functional.resample(wav, 24000, rate) and an int16 cast behind infer() on the host.  Here the waveform is already
+ * resident, and the D2H copy shrinks with the format (2x for PCM16 at 24 kHz, 12x for mu-law at 8 kHz).
+ *
+ * Resampling: the polyphase FIR torchaudio.functional.resample builds by default (sinc_interp_hann, rolloff 0.99, lowpass_filter_width W).
+ * g = gcd(24000, rate), orig = 24000 / g, new = rate / g, base = min(orig, new) * 0.99, width = ceil(W * orig / base), taps = 2 width + orig;
+ * phase p in [0, new), tap j in [0, taps): t = clamp((-p / new + (j - width) / orig) * base, -W, W),
+ * h[p][j] = sinc(pi t) * cos(pi t / (2 W))^2 * base / orig; output sample m = q * new + p is sum_j h[p][j] * x[q * orig + j - width] with x zero
+ * outside its own utterance; n_out = ceil(n_in * new / orig); rate 24000 copies.  The table is built in double on the host and rounded once to
+ * fp32, the sum runs in fp32.  W = 6 is torchaudio's default and rolls off early (a tone at 0.8 of the output Nyquist frequency comes out ~6 % low):
+ * telephony callers will want 16 or more.  tests/wav_format_spec.py states all of this in numpy and is the authority.
+ * PCM16: clip(rint(x * 32768), -32768, 32767), ties to even, NaN -> 0.  mu-law: G.711 of that PCM16 sample, the 14-bit form
+ * (audioop.lin2ulaw(pcm16, 2)).  The three encodings are applied to ONE fp32 sample. */
+enum { NTTS_WAV_F32 = 0, NTTS_WAV_PCM16 = 1, NTTS_WAV_MULAW = 2 };
+typedef struct ntts_wav_format {
+    int32_t sample_rate;   /* 8000, 16000, 22050, 24000, 32000, 44100 or 48000; 0 = 24000 */
+    int32_t encoding;      /* NTTS_WAV_*: float32 / int16_t / uint8_t elements */
+    int32_t filter_width;  /* W in [1, 64]; 0 = 6 */
+} ntts_wav_format;         /* zeroed (or a NULL pointer) = 24000 / F32 / 6: the native output, nothing more is launched */
+/* Samples of an utterance of n_in 24 kHz samples in `fmt`.  Pure host arithmetic; message through ntts_codec_last_error(NULL). */
+int ntts_wav_out_len(const ntts_wav_format* fmt, int64_t n_in, int64_t* n_out);
+/* ntts_codec_decode / ntts_codec_decode_dev with the output stage: `out` holds elements of the format's type, row i at offset i * out_stride
+ * ELEMENTS (out_stride >= the longest utterance's samples in that format), out_lens[i] (HOST) = its samples.  The same pass, then one kernel;
+ * with the native format the very same calls as the plain entry points, bit for bit.
+ * ntts_codec_convert: the stage alone on waveforms of the caller's -- HOST float32 [n][in_stride] at 24 kHz, utterance i of n_samples[i]
+ * samples (what follows them in its row is never read as signal) -- H2D, kernel, D2H on the engine's stream; blocking.  For a host library
+ * that works on the 24 kHz float waveform between the codec and the output (a watermarker).
+ * Refused with NTTS_EINVAL and a message, nothing run: an unknown rate or encoding, filter_width outside [0, 64], out_stride below the largest
+ * out_lens; for convert also n_samples[i] < 0, n_samples[i] > in_stride, or more samples than the engine's max_frames * hop_length. */
+int ntts_codec_decode_fmt(ntts_codec* c, int32_t n, const int32_t* codes, const int32_t* lens, const ntts_wav_format* fmt,
+                          void* out, int64_t out_stride, int32_t* out_lens);
+int ntts_codec_decode_dev_fmt(ntts_codec* c, int32_t n, const int32_t* codes_dev, int32_t codes_stride, const int32_t* lens,
+                              void* out, int64_t out_stride, int32_t out_on_device, void* producer_stream,
+                              const ntts_wav_format* fmt, int32_t* out_lens);
+int ntts_codec_convert(ntts_codec* c, int32_t n, const float* wav, int64_t in_stride, const int32_t* n_samples,
+                       const ntts_wav_format* fmt, void* out, int64_t out_stride, int32_t* out_lens);
 
 /* ------------------------------------------------------------------------------------------ */
 /* Device-side streaming (ABI 6): the per-chunk post-process of infer_stream for `n` concurrent    */

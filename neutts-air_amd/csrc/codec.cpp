@@ -9,8 +9,11 @@
 #include <stdarg.h>
 #include <string.h>
 
+#include <algorithm>
 #include <map>
+#include <numeric>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/neutts_hip.h"
@@ -66,6 +69,12 @@ struct ntts_codec {
     float* tap = nullptr;
     std::vector<int> tap_off, tap_len;   // row offset / frames of every utterance of the most recent decode call
     bool attn_resident = true;   // utterances of up to 256 frames: attn_full_resident_kernel (NTTS_CODEC_ATTN_RESIDENT=0: the two-sweep paged kernel)
+    // output stage (ntts_wav_format): one coefficient table per (rate, filter width) used so far, kept until destroy; the formatted buffer
+    // is allocated with the first call that needs it, for the engine's whole workspace at that call's rate and element size
+    struct WavTable { float* coef; int orig, nw, width, taps; };
+    std::map<std::pair<int, int>, WavTable> wav_tables;
+    void* fbuf = nullptr;
+    size_t fbuf_cap = 0;         // bytes
 };
 
 static int cfail(ntts_codec* c, int code, const char* fmt, ...) {
@@ -100,6 +109,7 @@ extern "C" void ntts_codec_destroy(ntts_codec* c) {
     hipDeviceSynchronize();
     for (void* p : c->allocs) hipFree(p);
     if (c->tap) hipFree(c->tap);
+    if (c->fbuf) hipFree(c->fbuf);
     for (auto& e : c->ev)
         if (e) hipEventDestroy(e);
     if (c->ev_in) hipEventDestroy(c->ev_in);
@@ -425,14 +435,107 @@ static void resnet_block(ntts_codec* c, const ResW& w, const CodecRows& R, long 
     { GemmArgs ga_ = cg(c->xb, S * H, w.w2, 3L * S * H, w.cb2, c->h + H, H, rows - 2, H, c->h + H, H); CGEMM(EPI_F32, ga_, st); }
 }
 
+// ---- output stage (ntts_wav_format; kernels/codec.h wav_format_kernel).  The reference has none: its users' torchaudio.functional.resample and
+// int16 cast sit behind ref:neutts/neutts.py:288-291 on the host.
+struct WavFmt {
+    int rate = 24000, enc = NTTS_WAV_F32, W = 6, orig = 1, nw = 1;
+    size_t esz = 4;
+    bool plain() const { return rate == 24000 && enc == NTTS_WAV_F32; }     // the engine's native output: no kernel, no second buffer
+    int64_t out_len(int64_t n_in) const { return (n_in * nw + orig - 1) / orig; }
+};
+// a null format is the zeroed one: 24 000 Hz / float32 / width 6
+static int wav_fmt_check(ntts_codec* c, const ntts_wav_format* f, WavFmt* o) {
+    static const int rates[] = {8000, 16000, 22050, 24000, 32000, 44100, 48000};
+    WavFmt w;
+    if (f) {
+        if (f->sample_rate) w.rate = f->sample_rate;
+        w.enc = f->encoding;
+        if (f->filter_width < 0 || f->filter_width > 64) return cfail(c, NTTS_EINVAL, "wav format: filter_width %d outside [0, 64] (0 = 6)", f->filter_width);
+        if (f->filter_width) w.W = f->filter_width;
+    }
+    if (std::find(std::begin(rates), std::end(rates), w.rate) == std::end(rates))
+        return cfail(c, NTTS_EINVAL, "wav format: sample_rate %d is not one of 8000, 16000, 22050, 24000, 32000, 44100, 48000", w.rate);
+    if (w.enc != NTTS_WAV_F32 && w.enc != NTTS_WAV_PCM16 && w.enc != NTTS_WAV_MULAW)
+        return cfail(c, NTTS_EINVAL, "wav format: unknown encoding %d (0 = float32, 1 = PCM16, 2 = mu-law)", w.enc);
+    const int g = std::gcd(24000, w.rate);
+    w.orig = 24000 / g; w.nw = w.rate / g;
+    w.esz = w.enc == NTTS_WAV_F32 ? 4 : w.enc == NTTS_WAV_PCM16 ? 2 : 1;
+    *o = w;
+    return NTTS_OK;
+}
+
+extern "C" int ntts_wav_out_len(const ntts_wav_format* fmt, int64_t n_in, int64_t* n_out) {
+    WavFmt w;
+    if (!n_out || n_in < 0) return cfail(nullptr, NTTS_EINVAL, "ntts_wav_out_len: null / negative argument");
+    const int rc = wav_fmt_check(nullptr, fmt, &w);
+    if (rc != NTTS_OK) return rc;
+    *n_out = w.out_len(n_in);
+    return NTTS_OK;
+}
+
+// the [taps][nw] fp32 table of a (rate, width) pair: built in double, rounded once, uploaded on first use, kept until destroy
+static int wav_table(ntts_codec* c, const WavFmt& w, ntts_codec::WavTable* out) {
+    const auto key = std::make_pair(w.rate, w.W);
+    auto it = c->wav_tables.find(key);
+    if (it != c->wav_tables.end()) { *out = it->second; return NTTS_OK; }
+    const int orig = w.orig, nw = w.nw;
+    const double base = std::min(orig, nw) * 0.99;                    // rolloff 0.99 of the lower Nyquist frequency
+    const int width = (int)ceil((double)w.W * orig / base), taps = 2 * width + orig;
+    if (((kWavBlock - 1) / nw + 1) * orig + taps > kWavSpanMax) return cfail(c, NTTS_EINVAL, "wav format: filter of %d taps exceeds the kernel's staging span", taps);
+    std::vector<float> h((size_t)taps * nw);
+    for (int p = 0; p < nw; ++p)
+        for (int j = 0; j < taps; ++j) {
+            double t = (-(double)p / nw + (double)(j - width) / orig) * base;
+            t = std::min(std::max(t, -(double)w.W), (double)w.W);
+            const double win = cos(M_PI * t / (2.0 * w.W));
+            const double snc = t == 0.0 ? 1.0 : sin(M_PI * t) / (M_PI * t);
+            h[(size_t)j * nw + p] = (float)(snc * win * win * (base / orig));
+        }
+    ntts_codec::WavTable tb{nullptr, orig, nw, width, taps};
+    const int rc = dalloc(c, &tb.coef, h.size());
+    if (rc != NTTS_OK) return rc;
+    CHIP(c, hipMemcpy(tb.coef, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
+    c->wav_tables[key] = tb;
+    *out = tb;
+    return NTTS_OK;
+}
+
+// in [n][in_stride] (utterance b: lens_dev[b] * len_mul samples; the rest of a row is scratch) -> c->fbuf [n][out_len_max] in the format's element type
+static int wav_format_launch(ntts_codec* c, const WavFmt& w, const float* in, long in_stride, const int* lens_dev, int len_mul, int n,
+                             int64_t out_len_max, hipStream_t st) {
+    const size_t need = (size_t)n * out_len_max * w.esz;
+    if (c->fbuf_cap < need) {      // first use (or a wider format): room for the engine's whole waveform workspace in this format
+        const size_t whole = ((size_t)w.out_len((int64_t)c->wav_cap) + (size_t)c->max_rows) * w.esz;
+        CHIP(c, hipStreamSynchronize(st));
+        if (c->fbuf) { hipFree(c->fbuf); c->fbuf = nullptr; c->fbuf_cap = 0; }
+        CHIP(c, hipMalloc(&c->fbuf, std::max(need, whole)));
+        c->fbuf_cap = std::max(need, whole);
+    }
+    WavFormatArgs a{};
+    a.in = in; a.in_stride = in_stride; a.lens = lens_dev; a.len_mul = len_mul; a.out = c->fbuf; a.out_stride = out_len_max; a.enc = w.enc;
+    a.orig = 1; a.nw = 1;
+    if (w.rate != 24000) {
+        ntts_codec::WavTable tb;
+        const int rc = wav_table(c, w, &tb);
+        if (rc != NTTS_OK) return rc;
+        a.coef = tb.coef; a.orig = tb.orig; a.nw = tb.nw; a.width = tb.width; a.taps = tb.taps;
+    }
+    NTTS_LAUNCH((wav_format_kernel), dim3(n, (unsigned)((out_len_max + kWavBlock - 1) / kWavBlock)), dim3(256), st, a);
+    return NTTS_OK;
+}
+
 // codes: HOST packed codes (codes_dev == null), or DEVICE codes, utterance i at codes_dev + i * codes_stride (already in range:
 // they come from ntts_backbone_export_codes).  out_kind: 0 = host destination, blocking (the classic entry point);
 // 1 = host destination (pinned), asynchronous; 2 = device destination, asynchronous.  producer: a HIP stream whose work so far
-// must complete before the codes are read (the backbone's stream), or null.
+// must complete before the codes are read (the backbone's stream), or null.  wf: the output format (null = the native 24 kHz float32: the
+// waveform buffer is the copy's source and nothing more is launched); wav_stride counts elements of that format, out_lens (may be null)
+// receives every utterance's samples.
 static int codec_decode_impl(ntts_codec* c, int32_t n, const int32_t* codes, const int32_t* codes_dev, int32_t codes_stride,
-                             const int32_t* lens, float* wav_out, int64_t wav_stride, int out_kind, hipStream_t producer) {
+                             const int32_t* lens, void* wav_out, int64_t wav_stride, int out_kind, hipStream_t producer,
+                             const WavFmt* wf = nullptr, int32_t* out_lens = nullptr) {
     if (!c || n < 1 || (!codes && !codes_dev) || !lens || !wav_out) return cfail(c, NTTS_EINVAL, "null/empty argument");
     if (!c->finalized) return cfail(c, NTTS_ESTATE, "weights not finalised");
+    if (wf && wf->plain()) wf = nullptr;
     CHIP(c, hipSetDevice(c->device));
     const int H = c->H, hop = c->cfg.hop_length;
     int Tmax = 0;
@@ -448,7 +551,12 @@ static int codec_decode_impl(ntts_codec* c, int32_t n, const int32_t* codes, con
         for (long i = 0; i < total; ++i)
             if (codes[i] < 0 || codes[i] >= ncodes) return cfail(c, NTTS_EINVAL, "code %d out of range [0, %ld)", codes[i], ncodes);
     if (codes_dev && codes_stride < Tmax) return cfail(c, NTTS_EINVAL, "codes_stride %d < longest utterance %d", codes_stride, Tmax);
-    if (wav_stride < (int64_t)hop * Tmax) return cfail(c, NTTS_EINVAL, "wav_stride %ld < %d samples", (long)wav_stride, hop * Tmax);
+    // samples per row of the hand-over (the longest utterance's, in the output format) and bytes per sample
+    const int64_t row_len = wf ? wf->out_len((int64_t)hop * Tmax) : (int64_t)hop * Tmax;
+    const size_t esz = wf ? wf->esz : sizeof(float);
+    if (wav_stride < row_len) return cfail(c, NTTS_EINVAL, "wav_stride %ld < %ld samples", (long)wav_stride, (long)row_len);
+    if (out_lens)
+        for (int i = 0; i < n; ++i) out_lens[i] = (int32_t)(wf ? wf->out_len((int64_t)hop * lens[i]) : (int64_t)hop * lens[i]);
     const int Tp = Tmax + 2 * kPadRows;
     const long rows = total + 2L * kPadRows * n;          // packed: every utterance brings its own frames + pad rows (codec.h)
     if (rows > c->max_rows) return cfail(c, NTTS_EINVAL, "%ld rows exceed max_rows %ld: decode fewer utterances per call", rows, c->max_rows);
@@ -555,26 +663,31 @@ static int codec_decode_impl(ntts_codec* c, int32_t n, const int32_t* codes, con
     oa.frames = c->frames; oa.win2 = c->win2; oa.wav = c->wav; oa.wav_stride = (long)hop * Tmax; oa.R = R; oa.hop = hop; oa.n_fft = c->n_fft;
     oa.scale = c->fmt == kOpF16 ? 1.0f / kDftScale : 1.0f;
     NTTS_LAUNCH((ola_kernel), dim3(n, (unsigned)(((long)hop * Tmax + 255) / 256)), dim3(256), st, oa);
+    const void* src = c->wav;
+    if (wf) {                              // the output stage: the formatted buffer becomes the copy's source
+        const int rc = wav_format_launch(c, *wf, c->wav, (long)hop * Tmax, R.lens, hop, n, row_len, st);
+        if (rc != NTTS_OK) return rc;
+        src = c->fbuf;
+    }
     CHIP(c, hipEventRecord(c->ev[1], st));
     c->have_time = true;
     const hipMemcpyKind kind = out_kind == 2 ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    const size_t row_bytes = (size_t)row_len * esz;
     if (out_kind == 0) {
         CHIP(c, hipStreamSynchronize(st));
         CHIP(c, hipGetLastError());
         // one strided device-to-host copy for the whole batch (rows shorter than Tmax carry don't-care tails)
-        if (wav_stride == (int64_t)hop * Tmax)   // dense destination: one linear copy (DMA engine at PCIe speed into pinned memory)
-            CHIP(c, hipMemcpy(wav_out, c->wav, (size_t)n * hop * Tmax * sizeof(float), kind));
+        if (wav_stride == row_len)   // dense destination: one linear copy (DMA engine at PCIe speed into pinned memory)
+            CHIP(c, hipMemcpy(wav_out, src, (size_t)n * row_bytes, kind));
         else
-            CHIP(c, hipMemcpy2D(wav_out, (size_t)wav_stride * sizeof(float), c->wav, (size_t)hop * Tmax * sizeof(float),
-                                (size_t)hop * Tmax * sizeof(float), n, kind));
+            CHIP(c, hipMemcpy2D(wav_out, (size_t)wav_stride * esz, src, row_bytes, row_bytes, n, kind));
         return NTTS_OK;
     }
     // asynchronous hand-over, stream-ordered behind the pass (ntts_codec_sync waits for it)
-    if (wav_stride == (int64_t)hop * Tmax)
-        CHIP(c, hipMemcpyAsync(wav_out, c->wav, (size_t)n * hop * Tmax * sizeof(float), kind, st));
+    if (wav_stride == row_len)
+        CHIP(c, hipMemcpyAsync(wav_out, src, (size_t)n * row_bytes, kind, st));
     else
-        CHIP(c, hipMemcpy2DAsync(wav_out, (size_t)wav_stride * sizeof(float), c->wav, (size_t)hop * Tmax * sizeof(float),
-                                 (size_t)hop * Tmax * sizeof(float), n, kind, st));
+        CHIP(c, hipMemcpy2DAsync(wav_out, (size_t)wav_stride * esz, src, row_bytes, row_bytes, n, kind, st));
     if (c->ev_done && hipEventRecord(c->ev_done, st) == hipSuccess) c->have_done = true;
     else { (void)hipGetLastError(); c->have_done = false; }
     return NTTS_OK;
@@ -590,6 +703,81 @@ extern "C" int ntts_codec_decode_dev(ntts_codec* c, int32_t n, const int32_t* co
                                      float* wav_out, int64_t wav_stride, int32_t wav_on_device, void* producer_stream) {
     if (!codes_dev) return cfail(c, NTTS_EINVAL, "null/empty argument");
     return codec_decode_impl(c, n, nullptr, codes_dev, codes_stride, lens, wav_out, wav_stride, wav_on_device ? 2 : 1, (hipStream_t)producer_stream);
+}
+
+// The same two passes with the output stage behind overlap-add (ntts_wav_format); a zeroed or null format is the plain pass, bit for bit.
+extern "C" int ntts_codec_decode_fmt(ntts_codec* c, int32_t n, const int32_t* codes, const int32_t* lens, const ntts_wav_format* fmt,
+                                     void* out, int64_t out_stride, int32_t* out_lens) {
+    if (!c) return NTTS_EINVAL;
+    if (!codes || !out_lens) return cfail(c, NTTS_EINVAL, "null/empty argument");
+    WavFmt w;
+    const int rc = wav_fmt_check(c, fmt, &w);
+    if (rc != NTTS_OK) return rc;
+    return codec_decode_impl(c, n, codes, nullptr, 0, lens, out, out_stride, 0, nullptr, &w, out_lens);
+}
+
+extern "C" int ntts_codec_decode_dev_fmt(ntts_codec* c, int32_t n, const int32_t* codes_dev, int32_t codes_stride, const int32_t* lens,
+                                         void* out, int64_t out_stride, int32_t out_on_device, void* producer_stream,
+                                         const ntts_wav_format* fmt, int32_t* out_lens) {
+    if (!c) return NTTS_EINVAL;
+    if (!codes_dev || !out_lens) return cfail(c, NTTS_EINVAL, "null/empty argument");
+    WavFmt w;
+    const int rc = wav_fmt_check(c, fmt, &w);
+    if (rc != NTTS_OK) return rc;
+    return codec_decode_impl(c, n, nullptr, codes_dev, codes_stride, lens, out, out_stride, out_on_device ? 2 : 1, (hipStream_t)producer_stream, &w, out_lens);
+}
+
+// The output stage alone on the caller's 24 kHz float32 waveforms (a watermarker, a host library, sits between the codec and the output):
+// H2D into the engine's waveform workspace, the kernel, D2H, as many rows per round as the workspace holds.  Blocking.
+extern "C" int ntts_codec_convert(ntts_codec* c, int32_t n, const float* wav, int64_t in_stride, const int32_t* n_samples,
+                                  const ntts_wav_format* fmt, void* out, int64_t out_stride, int32_t* out_lens) {
+    if (!c) return NTTS_EINVAL;
+    if (n < 1 || !wav || !n_samples || !out || !out_lens || in_stride < 0) return cfail(c, NTTS_EINVAL, "null/empty argument");
+    WavFmt w;
+    int rc = wav_fmt_check(c, fmt, &w);
+    if (rc != NTTS_OK) return rc;
+    const int64_t cap = (int64_t)c->cfg.max_frames * c->cfg.hop_length;
+    int64_t Lmax = 0;
+    for (int i = 0; i < n; ++i) {
+        if (n_samples[i] < 0 || n_samples[i] > in_stride)
+            return cfail(c, NTTS_EINVAL, "utterance %d: n_samples %d outside [0, in_stride %ld]", i, n_samples[i], (long)in_stride);
+        if (n_samples[i] > cap) return cfail(c, NTTS_EINVAL, "utterance %d: %d samples exceed the engine's %ld (max_frames x hop)", i, n_samples[i], (long)cap);
+        Lmax = std::max<int64_t>(Lmax, n_samples[i]);
+    }
+    const int64_t row_len = w.out_len(Lmax);
+    if (out_stride < row_len) return cfail(c, NTTS_EINVAL, "out_stride %ld < %ld samples", (long)out_stride, (long)row_len);
+    for (int i = 0; i < n; ++i) out_lens[i] = (int32_t)w.out_len(n_samples[i]);
+    if (Lmax == 0) return NTTS_OK;
+    if (w.plain()) {                       // the native format: nothing to compute, nothing is launched
+        for (int i = 0; i < n; ++i) memcpy((float*)out + (size_t)i * out_stride, wav + (size_t)i * in_stride, (size_t)n_samples[i] * sizeof(float));
+        return NTTS_OK;
+    }
+    CHIP(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    const size_t row_bytes = (size_t)row_len * w.esz;
+    const int per_round = (int)std::min<int64_t>(std::min<int64_t>((int64_t)c->wav_cap / Lmax, c->max_rows), (int64_t)c->meta_cap);
+    for (int i0 = 0; i0 < n; i0 += per_round) {
+        const int nb = std::min(per_round, n - i0);
+        const int k = c->meta_next;            // the lengths go through the page-locked meta ring, as a decode pass's do
+        c->meta_next = (k + 1) % ntts_codec::kMetaStages;
+        if (c->meta_used[k]) CHIP(c, hipEventSynchronize(c->meta_ev[k]));
+        memcpy(c->meta_host[k], n_samples + i0, (size_t)nb * sizeof(int));
+        CHIP(c, hipMemcpyAsync(c->meta, c->meta_host[k], (size_t)nb * sizeof(int), hipMemcpyHostToDevice, st));
+        c->meta_used[k] = true;
+        CHIP(c, hipEventRecord(c->meta_ev[k], st));
+        CHIP(c, hipMemcpy2DAsync(c->wav, (size_t)Lmax * sizeof(float), wav + (size_t)i0 * in_stride, (size_t)in_stride * sizeof(float),
+                                 (size_t)Lmax * sizeof(float), nb, hipMemcpyHostToDevice, st));
+        CHIP(c, hipEventRecord(c->ev[0], st));
+        rc = wav_format_launch(c, w, c->wav, (long)Lmax, c->meta, 1, nb, row_len, st);
+        if (rc != NTTS_OK) return rc;
+        CHIP(c, hipEventRecord(c->ev[1], st));
+        c->have_time = true;
+        CHIP(c, hipMemcpy2DAsync((char*)out + (size_t)i0 * out_stride * w.esz, (size_t)out_stride * w.esz, c->fbuf, row_bytes, row_bytes, nb,
+                                 hipMemcpyDeviceToHost, st));
+        CHIP(c, hipStreamSynchronize(st));
+        CHIP(c, hipGetLastError());
+    }
+    return NTTS_OK;
 }
 
 extern "C" int ntts_codec_set_cu_mask(ntts_codec* c, const uint32_t* mask, int32_t n_words) {

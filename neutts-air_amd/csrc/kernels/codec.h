@@ -678,4 +678,82 @@ NTTS_KERNEL(256) void ola_kernel(OlaArgs p) {
     p.wav[(long)b * p.wav_stride + s] = acc * p.scale / env;
 }
 
+// ---- output stage behind overlap-add: resample 24 kHz -> 8 .. 48 kHz, encode as float32 / PCM16 / G.711 mu-law -------------------
+// The reference has no such stage: its users put torchaudio.functional.resample(wav, 24000, rate) and an int16 cast behind infer()
+// (ref:neutts/neutts.py:288-291 hands out 24 kHz float32).  The filter is that function's default construction (sinc_interp_hann, rolloff 0.99,
+// lowpass_filter_width W) as a polyphase FIR: output sample m = q * nw + p of an utterance is sum_j coef[j][p] * x[q * orig + j - width], x zero
+// outside [0, n_in) of its OWN utterance -- the tail of a shorter row of the input buffer is scratch and is masked by length, never read as signal.
+// tests/wav_format_spec.py is the contract (table, lengths, PCM16 rounding, the mu-law segments).
+constexpr int kWavF32 = 0, kWavPcm16 = 1, kWavMulaw = 2;
+constexpr int kWavBlock = 256;       // output samples per workgroup
+constexpr int kWavSpanMax = 1280;    // staged input samples per workgroup: (255 / nw + 1) * orig + taps; 1156 at 8 kHz with W = 64, the largest (checked on the host)
+struct WavFormatArgs {
+    const float* in;       // [B][in_stride] 24 kHz float32
+    long in_stride;
+    const int* lens;       // [B]; utterance b holds lens[b] * len_mul input samples (decode: frames x hop; convert: samples x 1)
+    int len_mul;
+    const float* coef;     // [taps][nw] fp32 (adjacent threads = adjacent phases: coalesced); null at 24 kHz: no filter, conversion only
+    void* out;             // [B][out_stride] float / int16_t / uint8_t
+    long out_stride;       // elements
+    int orig, nw, width, taps;
+    int enc;               // kWavF32 / kWavPcm16 / kWavMulaw
+};
+// clip(rint(x * 2^15), -32768, 32767), ties to even (v_rndne_f32), NaN -> 0
+NTTS_D int wav_pcm16(float x) {
+    float v = rintf(x * 32768.0f);
+    v = fminf(fmaxf(v, -32768.0f), 32767.0f);
+    return x != x ? 0 : (int)v;
+}
+// G.711 mu-law of a 16-bit sample, the 14-bit form (audioop.lin2ulaw(., 2)): bias 0x21, 8 segments of 16 steps
+NTTS_D unsigned int wav_mulaw(int s) {
+    const int v = s >> 2;
+    int mag = v < 0 ? -v : v;
+    mag = (mag > 8159 ? 8159 : mag) + 0x21;
+    const int seg = 31 - __builtin_clz((unsigned int)mag) - 5;
+    const unsigned int code = seg >= 8 ? 0x7Fu : (unsigned int)((seg << 4) | ((mag >> (seg + 1)) & 15));
+    return code ^ (v >= 0 ? 0xFFu : 0x7Fu);
+}
+// THE fp32 output sample m of the workgroup's utterance (all three encodings are applied to this one number): `span` = the staged input
+// samples from q0 * orig - width on, zero where the utterance has none
+NTTS_D float wav_sample(const WavFormatArgs& p, const float* span, long q0, long m) {
+    const long q = m / p.nw;
+    const int ph = (int)(m - q * p.nw);
+    const float* x = span + (q - q0) * p.orig;
+    const float* h = p.coef + ph;
+    float acc = 0.f;
+    for (int j = 0; j < p.taps; ++j) acc = __builtin_fmaf(h[(long)j * p.nw], x[j], acc);
+    return acc;
+}
+// grid (B, ceil(longest output / kWavBlock))
+NTTS_KERNEL(256) void wav_format_kernel(WavFormatArgs p) {
+    NTTS_SHARED float span[kWavSpanMax];
+    const int b = blockIdx.x;
+    const long n_in = (long)p.lens[b] * p.len_mul;
+    const long n_out = p.coef ? (n_in * p.nw + p.orig - 1) / p.orig : n_in;
+    const long m0 = (long)blockIdx.y * kWavBlock;
+    if (m0 >= n_out) return;                                  // (the whole workgroup: nobody is left at the barrier)
+    const float* x = p.in + (long)b * p.in_stride;
+    const long m = m0 + threadIdx.x;
+    float y = 0.f;
+    if (p.coef) {
+        const long m_last = (m0 + kWavBlock - 1 < n_out ? m0 + kWavBlock : n_out) - 1;
+        const long q0 = m0 / p.nw;
+        const long i0 = q0 * p.orig - p.width;
+        const int n_span = (int)((m_last / p.nw - q0) * p.orig) + p.taps;     // <= kWavSpanMax (host check)
+        for (int i = threadIdx.x; i < n_span; i += 256) {
+            const long idx = i0 + i;
+            span[i] = (idx >= 0 && idx < n_in) ? x[idx] : 0.f;
+        }
+        sync();
+        if (m < n_out) y = wav_sample(p, span, q0, m);
+    } else if (m < n_out) {
+        y = x[m];
+    }
+    if (m >= n_out) return;
+    const long o = (long)b * p.out_stride + m;
+    if (p.enc == kWavF32) ((float*)p.out)[o] = y;
+    else if (p.enc == kWavPcm16) ((int16_t*)p.out)[o] = (int16_t)wav_pcm16(y);
+    else ((uint8_t*)p.out)[o] = (uint8_t)wav_mulaw(wav_pcm16(y));
+}
+
 }  // namespace ntts

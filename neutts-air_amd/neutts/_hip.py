@@ -46,6 +46,10 @@ class CodecConfigC(C.Structure):
                 ("max_frames", C.c_int32), ("max_rows", C.c_int32), ("precision", C.c_int32)]
 
 
+class WavFormatC(C.Structure):
+    _fields_ = [("sample_rate", C.c_int32), ("encoding", C.c_int32), ("filter_width", C.c_int32)]
+
+
 class EncoderConfigC(C.Structure):
     _fields_ = [("sem_hidden", C.c_int32), ("sem_layers", C.c_int32), ("sem_heads", C.c_int32), ("sem_ffn", C.c_int32),
                 ("sem_conv_kernel", C.c_int32), ("sem_left", C.c_int32), ("sem_right", C.c_int32), ("sem_ln_eps", C.c_float),
@@ -159,6 +163,10 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "ntts_codec_finalize": (C.c_int, [p]),
         "ntts_codec_decode": (C.c_int, [p, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(f32), i64]),
         "ntts_codec_last_timing": (C.c_int, [p, C.POINTER(f32)]),
+        "ntts_wav_out_len": (C.c_int, [C.POINTER(WavFormatC), i64, C.POINTER(i64)]),
+        "ntts_codec_decode_fmt": (C.c_int, [p, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(WavFormatC), p, i64, C.POINTER(i32)]),
+        "ntts_codec_decode_dev_fmt": (C.c_int, [p, i32, p, i32, C.POINTER(i32), p, i64, i32, p, C.POINTER(WavFormatC), C.POINTER(i32)]),
+        "ntts_codec_convert": (C.c_int, [p, i32, C.POINTER(f32), i64, C.POINTER(i32), C.POINTER(WavFormatC), p, i64, C.POINTER(i32)]),
         "ntts_encoder_last_error": (C.c_char_p, [p]),
         "ntts_encoder_create": (C.c_int, [C.POINTER(EncoderConfigC), C.c_int, C.POINTER(p)]),
         "ntts_encoder_destroy": (None, [p]),
@@ -221,6 +229,34 @@ def _tensor_ptr(t):
             code = NTTS_DT_F32
         return tt.data_ptr(), code, tuple(tt.shape), int(tt.is_cuda), tt
     raise TypeError(f"unsupported tensor type {type(t)}")
+
+
+# ---- the codec's output stage (include/neutts_hip.h ntts_wav_format): resample 24 kHz -> WAV_RATES, encode as float32 / PCM16 / G.711 mu-law
+NATIVE_SAMPLE_RATE = 24000
+WAV_RATES = (8000, 16000, 22050, 24000, 32000, 44100, 48000)
+WAV_ENCODINGS = {"f32": (0, np.float32), "pcm16": (1, np.int16), "mulaw": (2, np.uint8)}
+WAV_MAX_FILTER_WIDTH = 64
+
+
+def wav_format(sample_rate=None, encoding="f32", filter_width=None, who: str = ""):
+    """Checked (WavFormatC, numpy dtype, is_native) of an output format; None = 24 000 Hz / "f32" / width 6.  ValueError names the bad value."""
+    rate = NATIVE_SAMPLE_RATE if sample_rate is None else sample_rate
+    if isinstance(rate, (bool, np.bool_)) or not isinstance(rate, (int, np.integer)) or int(rate) not in WAV_RATES:
+        raise ValueError(f"{who}sample_rate must be one of {WAV_RATES} (got {sample_rate!r})")
+    enc = "f32" if encoding is None else encoding
+    if not isinstance(enc, str) or enc not in WAV_ENCODINGS:
+        raise ValueError(f"{who}encoding must be one of {tuple(WAV_ENCODINGS)} (got {encoding!r})")
+    w = 6 if filter_width is None else filter_width
+    if isinstance(w, (bool, np.bool_)) or not isinstance(w, (int, np.integer)) or not 1 <= w <= WAV_MAX_FILTER_WIDTH:
+        raise ValueError(f"{who}filter_width must be an integer in [1, {WAV_MAX_FILTER_WIDTH}] (got {filter_width!r})")
+    code, dtype = WAV_ENCODINGS[enc]
+    return WavFormatC(int(rate), code, int(w)), dtype, (int(rate) == NATIVE_SAMPLE_RATE and enc == "f32")
+
+
+def wav_out_len(n_in: int, sample_rate=None) -> int:
+    """Samples at `sample_rate` of n_in samples at 24 kHz: ceil(n_in * rate / 24000) (ntts_wav_out_len's arithmetic)."""
+    rate = int(wav_format(sample_rate)[0].sample_rate)
+    return -(-int(n_in) * rate // NATIVE_SAMPLE_RATE)
 
 
 @dataclass
@@ -1289,47 +1325,65 @@ class CodecEngine:
             del keep
         self._chk(self.lib.ntts_codec_finalize(self.h))
 
-    def _pinned(self, n_floats: int) -> np.ndarray:
-        """Engine-owned page-locked staging buffer (grown on demand), viewed as a float32 numpy array."""
-        if getattr(self, "_pin_cap", 0) < n_floats:
+    def _pinned(self, n: int, dtype=np.float32) -> np.ndarray:
+        """Engine-owned page-locked staging buffer (sized in bytes, grown on demand), viewed as a numpy array of `n` elements of `dtype`."""
+        nbytes = max(1, n * np.dtype(dtype).itemsize)
+        if getattr(self, "_pin_cap", 0) < nbytes:
             if getattr(self, "_pin_ptr", None):
                 self.lib.ntts_host_free(self._pin_ptr)
+                self._pin_ptr, self._pin_cap = None, 0
             ptr = C.c_void_p()
-            if self.lib.ntts_host_alloc(n_floats * 4, C.byref(ptr)) != 0:
+            if self.lib.ntts_host_alloc(nbytes, C.byref(ptr)) != 0:
                 raise MemoryError("pinned host allocation failed")
-            self._pin_ptr, self._pin_cap = ptr, n_floats
-        return np.ctypeslib.as_array((C.c_float * n_floats).from_address(self._pin_ptr.value))
+            self._pin_ptr, self._pin_cap = ptr, nbytes
+        return np.frombuffer((C.c_char * nbytes).from_address(self._pin_ptr.value), dtype=dtype, count=n)
 
-    def decode(self, codes: Sequence[Sequence[int]], reuse_output: bool = False) -> List[np.ndarray]:
-        """codes: one int sequence per utterance -> list of float32 waveforms (hop_length * len each).
+    def _decode_call(self, n: int, flat: np.ndarray, lens: np.ndarray, tmax: int, fmt, reuse_output: bool):
+        """One ntts_codec_decode / ntts_codec_decode_fmt call -> ([n, stride] array of the format's dtype, samples per utterance)."""
+        fc, dtype, native = fmt
+        i32p = C.POINTER(C.c_int32)
+        stride = wav_out_len(self.hop_length * tmax, fc.sample_rate)
+        wav = (self._pinned(n * stride, dtype) if reuse_output else np.empty(n * stride, dtype=dtype)).reshape(n, stride)
+        if native:        # the plain entry point: the calls and the bits of an engine without the output stage
+            self._chk(self.lib.ntts_codec_decode(self.h, n, flat.ctypes.data_as(i32p), lens.ctypes.data_as(i32p),
+                                                 wav.ctypes.data_as(C.POINTER(C.c_float)), stride))
+            return wav, self.hop_length * lens.astype(np.int64)
+        out_lens = np.zeros(n, dtype=np.int32)
+        self._chk(self.lib.ntts_codec_decode_fmt(self.h, n, flat.ctypes.data_as(i32p), lens.ctypes.data_as(i32p), C.byref(fc),
+                                                 C.c_void_p(wav.ctypes.data), stride, out_lens.ctypes.data_as(i32p)))
+        return wav, out_lens
+
+    def decode(self, codes: Sequence[Sequence[int]], reuse_output: bool = False, sample_rate=None, encoding="f32",
+               filter_width=None) -> List[np.ndarray]:
+        """codes: one int sequence per utterance -> list of waveforms: float32 at 24 kHz, hop_length * len samples each, by default;
+        sample_rate (one of WAV_RATES) / encoding ("f32", "pcm16" -> int16, "mulaw" -> uint8) / filter_width (the resampler's
+        lowpass_filter_width, 1..64, default 6) put the device output stage behind the pass: ceil(hop_length * len * rate / 24000) samples.
         reuse_output=True returns views into an engine-owned pinned buffer (fast D2H, no copy): they are only valid
         until the next decode() call on this engine."""
+        fmt = wav_format(sample_rate, encoding, filter_width)
         out: List[Optional[np.ndarray]] = [None] * len(codes)
         order = sorted(range(len(codes)), key=lambda i: -len(codes[i]))   # batch similar lengths together
         i = 0
-        i32p = C.POINTER(C.c_int32)
         while i < len(order):
             tmax = len(codes[order[i]])
             nb = max(1, min(len(order) - i, self.max_rows // (tmax + 6)))
             grp = order[i:i + nb]
             lens = np.array([len(codes[j]) for j in grp], dtype=np.int32)
             flat = np.ascontiguousarray(np.concatenate([np.asarray(codes[j], dtype=np.int32) for j in grp]))
-            stride = int(self.hop_length * tmax)
-            if reuse_output and i == 0 and nb == len(order):      # single call covers the batch: pinned fast path
-                wav = self._pinned(len(grp) * stride).reshape(len(grp), stride)
-            else:
-                wav = np.empty((len(grp), stride), dtype=np.float32)
-            self._chk(self.lib.ntts_codec_decode(self.h, len(grp), flat.ctypes.data_as(i32p), lens.ctypes.data_as(i32p),
-                                                 wav.ctypes.data_as(C.POINTER(C.c_float)), stride))
+            # (pinned fast path when a single call covers the batch)
+            wav, out_lens = self._decode_call(len(grp), flat, lens, tmax, fmt, reuse_output and i == 0 and nb == len(order))
             for r, j in enumerate(grp):
-                out[j] = wav[r, : self.hop_length * len(codes[j])]     # view into this call's buffer: no second copy
+                out[j] = wav[r, : int(out_lens[r])]     # view into this call's buffer: no second copy
             i += nb
         return out  # type: ignore[return-value]
 
-    def decode_array(self, codes: np.ndarray, lens: Optional[np.ndarray] = None, reuse_output: bool = False) -> np.ndarray:
+    def decode_array(self, codes: np.ndarray, lens: Optional[np.ndarray] = None, reuse_output: bool = False, sample_rate=None,
+                     encoding="f32", filter_width=None) -> np.ndarray:
         """Batch fast path: codes [n, T] int (row i valid up to lens[i]; all T when lens is None) -> waveforms
         [n, hop_length * T] float32 in ONE engine call (n * (T + 6) must fit max_rows).  reuse_output=True returns a
-        view of the engine's pinned staging buffer, valid until the next decode on this engine."""
+        view of the engine's pinned staging buffer, valid until the next decode on this engine.  With an output format (as `decode`):
+        [n, wav_out_len(hop_length * T, sample_rate)] of the encoding's dtype, row i valid up to wav_out_len(hop_length * lens[i], sample_rate)."""
+        fmt = wav_format(sample_rate, encoding, filter_width)
         codes = np.asarray(codes)
         n, T = codes.shape
         if lens is None:
@@ -1338,12 +1392,40 @@ class CodecEngine:
         else:
             lens = np.ascontiguousarray(lens, dtype=np.int32)
             flat = np.ascontiguousarray(np.concatenate([codes[i, : lens[i]] for i in range(n)]), dtype=np.int32)
-        stride = int(self.hop_length * int(lens.max()))
-        wav = (self._pinned(n * stride) if reuse_output else np.empty(n * stride, dtype=np.float32)).reshape(n, stride)
+        return self._decode_call(n, flat, lens, int(lens.max()), fmt, reuse_output)[0]
+
+    def convert_array(self, wav: np.ndarray, n_samples, sample_rate=None, encoding="f32", filter_width=None, out_stride: Optional[int] = None):
+        """The output stage alone (ntts_codec_convert): wav [n, in_stride] float32 at 24 kHz, row i valid up to n_samples[i] (what follows is
+        never read as signal) -> ([n, out_stride] array of the encoding's dtype, samples per row)."""
+        fc, dtype, _ = wav_format(sample_rate, encoding, filter_width)
+        wav = np.ascontiguousarray(wav, dtype=np.float32)
+        n, in_stride = wav.shape
+        n_samples = np.ascontiguousarray(n_samples, dtype=np.int32)
+        if len(n_samples) != n:
+            raise ValueError(f"n_samples: {len(n_samples)} values for {n} waveforms")
+        if out_stride is None:
+            out_stride = wav_out_len(max(0, int(n_samples.max())) if n else 0, fc.sample_rate)
+        out_stride = int(out_stride)
+        buf = np.zeros(max(1, n * max(0, out_stride)), dtype=dtype)       # (never a null pointer, even for n rows of no samples)
+        out_lens = np.zeros(n, dtype=np.int32)
         i32p = C.POINTER(C.c_int32)
-        self._chk(self.lib.ntts_codec_decode(self.h, n, flat.ctypes.data_as(i32p), lens.ctypes.data_as(i32p),
-                                             wav.ctypes.data_as(C.POINTER(C.c_float)), stride))
-        return wav
+        self._chk(self.lib.ntts_codec_convert(self.h, n, wav.ctypes.data_as(C.POINTER(C.c_float)), in_stride, n_samples.ctypes.data_as(i32p),
+                                              C.byref(fc), C.c_void_p(buf.ctypes.data), out_stride, out_lens.ctypes.data_as(i32p)))
+        out = buf[: n * out_stride].reshape(n, out_stride)
+        return out, out_lens
+
+    def convert(self, wavs: Sequence[np.ndarray], sample_rate=None, encoding="f32", filter_width=None) -> List[np.ndarray]:
+        """24 kHz float waveforms (one 1-D array each; e.g. what a watermarker handed back) -> the same in another output format, as `decode`
+        with these arguments would have produced from them."""
+        wavs = [np.asarray(w, dtype=np.float32).reshape(-1) for w in wavs]
+        if not wavs:
+            return []
+        n_samples = np.array([len(w) for w in wavs], dtype=np.int32)
+        buf = np.zeros((len(wavs), max(1, int(n_samples.max()))), dtype=np.float32)
+        for r, w in enumerate(wavs):
+            buf[r, : len(w)] = w
+        out, out_lens = self.convert_array(buf, n_samples, sample_rate, encoding, filter_width)
+        return [out[r, : int(out_lens[r])] for r in range(len(wavs))]
 
     def set_debug(self, keep_stages: bool):
         self._chk(self.lib.ntts_codec_set_debug(self.h, int(keep_stages)))
@@ -1364,22 +1446,31 @@ class CodecEngine:
         self._chk(self.lib.ntts_codec_set_cu_mask(self.h, arr, len(words)))
 
     def decode_device(self, codes_dev_ptr: int, codes_stride: int, lens: np.ndarray, producer_stream: int = 0,
-                      wav_dev_ptr: Optional[int] = None, wav_stride: Optional[int] = None, reuse_output: bool = True):
+                      wav_dev_ptr: Optional[int] = None, wav_stride: Optional[int] = None, reuse_output: bool = True,
+                      sample_rate=None, encoding="f32", filter_width=None):
         """Codes already on the device (BackboneEngine.export_codes) -> waveforms, asynchronously: returns the [n, stride]
-        float32 destination (a view of the engine's pinned host buffer, or None when `wav_dev_ptr` names a device buffer);
-        call sync() before reading it."""
+        destination (a view of the engine's pinned host buffer, or None when `wav_dev_ptr` names a device buffer);
+        call sync() before reading it.  float32 at 24 kHz by default; with an output format (as `decode`) elements of the encoding's dtype,
+        stride = wav_out_len(hop_length * max(lens), sample_rate) unless given, row i valid up to wav_out_len(hop_length * lens[i], sample_rate)."""
+        fc, dtype, native = wav_format(sample_rate, encoding, filter_width)
         lens = np.ascontiguousarray(lens, dtype=np.int32)
         n = len(lens)
-        stride = int(wav_stride or self.hop_length * int(lens.max()))
+        stride = int(wav_stride or wav_out_len(self.hop_length * int(lens.max()), fc.sample_rate))
         wav = None
         if wav_dev_ptr is None:
-            wav = self._pinned(n * stride).reshape(n, stride)
+            wav = self._pinned(n * stride, dtype).reshape(n, stride)
             dst, on_dev = wav.ctypes.data, 0
         else:
             dst, on_dev = wav_dev_ptr, 1
-        self._chk(self.lib.ntts_codec_decode_dev(self.h, n, C.c_void_p(codes_dev_ptr), codes_stride,
-                                                 lens.ctypes.data_as(C.POINTER(C.c_int32)), C.c_void_p(dst), stride, on_dev,
-                                                 C.c_void_p(producer_stream or None)))
+        i32p = C.POINTER(C.c_int32)
+        if native:
+            self._chk(self.lib.ntts_codec_decode_dev(self.h, n, C.c_void_p(codes_dev_ptr), codes_stride, lens.ctypes.data_as(i32p),
+                                                     C.c_void_p(dst), stride, on_dev, C.c_void_p(producer_stream or None)))
+        else:
+            out_lens = np.zeros(n, dtype=np.int32)
+            self._chk(self.lib.ntts_codec_decode_dev_fmt(self.h, n, C.c_void_p(codes_dev_ptr), codes_stride, lens.ctypes.data_as(i32p),
+                                                         C.c_void_p(dst), stride, on_dev, C.c_void_p(producer_stream or None), C.byref(fc),
+                                                         out_lens.ctypes.data_as(i32p)))
         return wav
 
     def sync(self):

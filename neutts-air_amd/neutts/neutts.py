@@ -185,6 +185,12 @@ def _check_best_of(best_of, do_sample: bool, who: str = "") -> None:
         raise ValueError(f"{who}best_of = {best_of} needs do_sample=True: greedy candidates are identical")
 
 
+def _check_output(sample_rate, encoding, filter_width, who: str = "") -> None:
+    """The output formats the codec's device output stage produces (_hip.wav_format: include/neutts_hip.h ntts_wav_format); ValueError naming the
+    offending value before anything reaches the engine."""
+    _hip.wav_format(sample_rate, encoding, filter_width, who)
+
+
 def sequence_score(logprobs) -> float:
     """A candidate's score: the arithmetic mean of its per-token log-probabilities (-inf for an empty one)."""
     lp = np.asarray(logprobs, dtype=np.float64)
@@ -215,9 +221,21 @@ class NeuTTS:
         best_of: int = 1,
         speech_range_head: bool = False,
         codec_precision: str = "fp16",
+        output_sample_rate: int = 24_000,
+        output_encoding: str = "f32",
+        output_filter_width: int = 6,
     ):
         # Consts (ref:neutts/neutts.py:84-91)
-        self.sample_rate = 24_000
+        self.sample_rate = 24_000            # the NATIVE rate (the codec's; what a watermarker sees), whatever the output format
+        # Output format of infer / infer_batch / decode_codes (the reference hands out 24 kHz float32, ref:neutts/neutts.py:288-291, and its users
+        # resample and cast on the host): one of _hip.WAV_RATES, "f32" / "pcm16" (int16) / "mulaw" (uint8, G.711), the resampler's
+        # lowpass_filter_width (torchaudio's default 6 rolls off early: telephony callers want 16 or more).  Applied on the device behind the codec
+        # pass (include/neutts_hip.h ntts_wav_format); sample_rate= / encoding= per call override the first two.  The streaming entry points
+        # take the default format only: chunked resampling needs per-stream filter history across chunk edges.
+        _check_output(output_sample_rate, output_encoding, output_filter_width, "output_")
+        self.output_sample_rate = int(output_sample_rate)
+        self.output_encoding = output_encoding
+        self.output_filter_width = int(output_filter_width)
         self.max_context = 2048
         self.hop_length = 480
         self.streaming_overlap_frames = 1
@@ -424,20 +442,30 @@ class NeuTTS:
         """Generate speech for `text` in the voice of the encoded reference (ref:neutts/neutts.py:216-243).  temperature / top_k / top_p /
         min_p override the instance's sampling attributes for this call (None = the attribute), and so do the two further keywords every entry
         point takes behind them: repetition_penalty= and repetition_ignore_prompt= (anything else is a TypeError).
-        best_of=N: N sampled candidates, the one with the highest mean log-probability is synthesised; return_scores=True: (wav, score)."""
+        best_of=N: N sampled candidates, the one with the highest mean log-probability is synthesised; return_scores=True: (wav, score).
+        sample_rate= / encoding= (two more keywords of the catch-all) override output_sample_rate / output_encoding for this call."""
+        out = self._resolve_output(repetition.pop("sample_rate", None), repetition.pop("encoding", None))
         best_of, want = self._pop_scoring(1, repetition, "return_scores")
         samp = self._resolve_sampling(1, temperature, top_k, top_p, min_p, repetition)
         prompt_ids = self._apply_chat_template(ref_codes, ref_text, text)
         ids, lps = self._generate_scored([prompt_ids], samp, best_of, want)
-        wav = self._decode_ids(ids[0])
-        if self.watermarker is not None:
-            wav = self.watermarker.apply_watermark(wav, sample_rate=24_000)
+        if out is None:
+            wav = self._decode_ids(ids[0])
+            if self.watermarker is not None:
+                wav = self.watermarker.apply_watermark(wav, sample_rate=24_000)
+        else:
+            speech_ids = self._ids_to_codes(ids[0])
+            if len(speech_ids) == 0:
+                raise ValueError("No valid speech tokens found in the output.")
+            wav = self._decode_formatted([speech_ids], out)[0]
         return (wav, sequence_score(lps[0])) if want else wav
 
     def infer_batch(self, texts: Sequence[str], ref_codes, ref_texts, *, temperature=None, top_k=None, top_p=None, min_p=None, **repetition) -> List[np.ndarray]:
         """Many utterances at once: continuous batching over the engine's decode slots (over every engine's, with engines > 1),
         one codec pass.  The sampling overrides take one value for the call or one per utterance, and so does best_of= (candidates per
-        utterance; only the winners go through the codec); return_scores=True: (wavs, scores), score = mean log-probability of the ids."""
+        utterance; only the winners go through the codec); return_scores=True: (wavs, scores), score = mean log-probability of the ids.
+        sample_rate= / encoding= (two more keywords of the catch-all) override output_sample_rate / output_encoding for this call (one format per call)."""
+        out = self._resolve_output(repetition.pop("sample_rate", None), repetition.pop("encoding", None))
         best_of, want = self._pop_scoring(len(texts), repetition, "return_scores")
         samp = self._resolve_sampling(len(texts), temperature, top_k, top_p, min_p, repetition)
         if not isinstance(ref_texts, (list, tuple)):
@@ -448,14 +476,18 @@ class NeuTTS:
         codes = [self._ids_to_codes(x) for x in ids]
         if any(len(c) == 0 for c in codes):
             raise ValueError("No valid speech tokens found in the output.")
-        wavs = self.codec.engine.decode(codes)
-        if self.watermarker is not None:
-            wavs = [self.watermarker.apply_watermark(w, sample_rate=24_000) for w in wavs]
+        if out is None:
+            wavs = self.codec.engine.decode(codes)
+            if self.watermarker is not None:
+                wavs = [self.watermarker.apply_watermark(w, sample_rate=24_000) for w in wavs]
+        else:
+            wavs = self._decode_formatted(codes, out)
         return (wavs, [sequence_score(lp) for lp in lps]) if want else wavs
 
     def infer_stream(self, text: str, ref_codes, ref_text: str, *, temperature=None, top_k=None, top_p=None, min_p=None, **repetition) -> Generator[np.ndarray, None, None]:
         """Streaming synthesis with the reference's window / cross-fade semantics (ref:neutts/neutts.py:373-465).  Sampling overrides as `infer`
-        (checked here, before the generator is handed out)."""
+        (checked here, before the generator is handed out).  Chunks are 24 kHz float32: any other output format is a ValueError."""
+        self._refuse_stream_output(repetition.pop("sample_rate", None), repetition.pop("encoding", None), "infer_stream")
         samp = self._resolve_sampling(1, temperature, top_k, top_p, min_p, repetition)
         prompt_ids = self._apply_chat_template(ref_codes, ref_text, text)
         ref = [int(c) for c in _to_list(ref_codes)]
@@ -468,7 +500,9 @@ class NeuTTS:
         yields `(utterance index, chunk)` pairs; the chunks of one utterance, in order, are exactly what `infer_stream`
         yields for it.  One decode burst serves every running utterance, and all windows that became decodable in a burst
         go through the codec in ONE batched call, enqueued behind the next burst (the two engines' streams overlap).
-        At most `max_batch` utterances (the engine's decode slots) per call.  Sampling overrides as `infer_batch`."""
+        At most `max_batch` utterances (the engine's decode slots) per call.  Sampling overrides as `infer_batch`.  Chunks are 24 kHz float32:
+        any other output format is a ValueError."""
+        self._refuse_stream_output(repetition.pop("sample_rate", None), repetition.pop("encoding", None), "infer_stream_batch")
         samp = self._resolve_sampling(len(texts), temperature, top_k, top_p, min_p, repetition)
         if not isinstance(ref_texts, (list, tuple)):
             ref_texts = [ref_texts] * len(texts)
@@ -697,8 +731,40 @@ class NeuTTS:
             return x[(x >= 0) & (x < 65536)].astype(np.int32)
         return np.asarray(self._ids_to_codes(np.asarray(ids).tolist()), dtype=np.int32)
 
-    def decode_codes(self, codes: Sequence[Sequence[int]]) -> List[np.ndarray]:
-        return self.codec.engine.decode(codes)
+    def decode_codes(self, codes: Sequence[Sequence[int]], sample_rate=None, encoding=None) -> List[np.ndarray]:
+        """Codec codes -> waveforms in the instance's output format (sample_rate= / encoding= override it for this call); no watermark, as before."""
+        out = self._resolve_output(sample_rate, encoding)
+        if out is None:
+            return self.codec.engine.decode(codes)
+        return self.codec.engine.decode(codes, sample_rate=out[0], encoding=out[1], filter_width=out[2])
+
+    def _resolve_output(self, sample_rate=None, encoding=None):
+        """Per-call output format: None = the instance attribute.  -> None for the native format (24 kHz float32: the calls of an instance without
+        the output stage), else the checked (sample_rate, encoding, filter_width).  ValueError on a bad value, before the engine is touched."""
+        rate = self.output_sample_rate if sample_rate is None else sample_rate
+        enc = self.output_encoding if encoding is None else encoding
+        _check_output(rate, enc, self.output_filter_width, "" if sample_rate is not None or encoding is not None else "output_")
+        return None if (int(rate) == self.sample_rate and enc == "f32") else (int(rate), enc, int(self.output_filter_width))
+
+    def _refuse_stream_output(self, sample_rate, encoding, who: str) -> None:
+        out = self._resolve_output(sample_rate, encoding)
+        if out is not None:
+            if out[0] != self.sample_rate:
+                what = f"sample_rate={out[0]!r}" if sample_rate is not None else f"output_sample_rate={out[0]!r}"
+            else:
+                what = f"encoding={out[1]!r}" if encoding is not None else f"output_encoding={out[1]!r}"
+            raise ValueError(f"{who} yields 24 kHz float32 chunks only (got {what}): resampling a stream needs filter history across chunk "
+                             "edges; use infer / infer_batch for another output format, or convert the finished stream")
+
+    def _decode_formatted(self, codes: Sequence[Sequence[int]], out) -> List[np.ndarray]:
+        """One codec pass with the device output stage behind it.  A watermarker is a host library that works on the 24 kHz float waveform: with
+        one present the order is decode (native), watermark on the host, then the output stage alone (CodecEngine.convert)."""
+        rate, enc, width = out
+        eng = self.codec.engine
+        if self.watermarker is None:
+            return eng.decode(codes, sample_rate=rate, encoding=enc, filter_width=width)
+        wavs = [self.watermarker.apply_watermark(w, sample_rate=24_000) for w in eng.decode(codes)]
+        return eng.convert(wavs, sample_rate=rate, encoding=enc, filter_width=width)
 
     def _decode_ids(self, ids: Sequence[int]) -> np.ndarray:
         speech_ids = self._ids_to_codes(ids)
