@@ -520,6 +520,35 @@ int ntts_codec_decode_dev_fmt(ntts_codec* c, int32_t n, const int32_t* codes_dev
 int ntts_codec_convert(ntts_codec* c, int32_t n, const float* wav, int64_t in_stride, const int32_t* n_samples,
                        const ntts_wav_format* fmt, void* out, int64_t out_stride, int32_t* out_lens);
 
+/* The output stage on a signal that arrives in CHUNKS (a stream).  NEW SYMBOLS ONLY: NTTS_ABI_VERSION stays 11.
+ *
+ * After N input samples in all a stream has emitted M(N) output samples: M = N at 24 kHz; otherwise M = ((N - width) / orig) * new once
+ * N >= width (0 before) -- every output sample whose `taps` inputs x[q * orig - width, q * orig + width + orig) have all arrived -- and
+ * M = ceil(N * new / orig) with the stream's LAST chunk, the missing inputs zero as in the one-shot stage.  Chunk k delivers the outputs
+ * [M(N_{k-1}), M(N_k)).  Sample m is the dot product of the one-shot stage: the same table, the same operands, the same order.  THE CONCATENATED
+ * CHUNKS OF A STREAM ARE BIT-IDENTICAL TO ntts_codec_convert OF THE CONCATENATED SIGNAL, in all three encodings, for every chunking.
+ * Between chunks a stream keeps the inputs its next outputs still need: at most taps - 1 samples (390 floats at 8 kHz with W = 64).  The output
+ * lags the input by at most width + orig input samples (231: under 10 ms); only a stream's first chunk is shorter for it, and a chunk may be
+ * empty.  tests/wav_stream_spec.py (stream_out_count, resample_chunks; the numbers are tests/wav_format_spec.py's) is the authority.
+ *
+ * ntts_wav_stream: that stage alone for `n_streams` independent streams on a codec engine -- the streaming twin of ntts_codec_convert, for a
+ * host library between the codec and the output (a watermarker).  A chunk holds at most max_chunk_samples samples.
+ * ntts_wav_stream_push: n entries; entry i appends n_samples[i] samples (HOST float32, row i of wav [n][in_stride]; what follows them in the
+ * row is never read as signal) to stream stream[i] and receives out_lens[i] elements of the format in row i of out [n][out_stride ELEMENTS].
+ * n_samples[i] = 0 is legal; with last[i] it is the pure flush.  After last[i] the stream is empty and may start a new signal.  H2D, one
+ * kernel, D2H on the codec engine's stream; blocking.
+ * Refused with NTTS_EINVAL and a message (ntts_wav_stream_last_error), nothing run and no stream moved: a bad format (as ntts_codec_convert),
+ * a stream index out of range or named twice in one call, n_samples[i] negative, above in_stride or above max_chunk_samples, out_stride below
+ * the largest out_lens.
+ * ntts_wav_stream_count: M(n_in_total) of a format; pure host arithmetic (message through ntts_wav_stream_last_error(NULL)). */
+typedef struct ntts_wav_stream ntts_wav_stream;
+int ntts_wav_stream_create(ntts_codec* c, const ntts_wav_format* fmt, int32_t n_streams, int32_t max_chunk_samples, ntts_wav_stream** out);
+void ntts_wav_stream_destroy(ntts_wav_stream* ws);
+const char* ntts_wav_stream_last_error(const ntts_wav_stream* ws);
+int ntts_wav_stream_push(ntts_wav_stream* ws, int32_t n, const int32_t* stream, const float* wav, int64_t in_stride, const int32_t* n_samples,
+                         const int32_t* last, void* out, int64_t out_stride, int32_t* out_lens);
+int ntts_wav_stream_count(const ntts_wav_format* fmt, int64_t n_in_total, int32_t last, int64_t* n_out_total);
+
 /* ------------------------------------------------------------------------------------------ */
 /* Device-side streaming (ABI 6): the per-chunk post-process of infer_stream for `n` concurrent    */
 /* utterances -- token cache, window assembly, the 27-frame slice and the triangular cross-fade    */
@@ -560,6 +589,17 @@ int ntts_streams_pump_end(ntts_streams* s, int32_t cap, int32_t* n_chunks, int32
                           const float** chunks, int64_t* row_stride, int32_t* n_running, int32_t* more);
 /* Streams that have emitted their last chunk.  (After a failed pump the set's bookkeeping is ahead of what was emitted: destroy it.) */
 int ntts_streams_done(ntts_streams* s, int32_t* n_done);
+/* Chunks in another output format (ntts_wav_format; NEW SYMBOLS ONLY).  ntts_streams_set_format: legal until the first pump_begin
+ * (NTTS_ESTATE after); a bad format is NTTS_EINVAL.  A non-native format puts the chunked output stage (above: one history row per stream)
+ * behind the cross-fade on the codec's stream; the page-locked buffer and the D2H copy are sized in the format's element type.
+ * ntts_streams_pump_end_fmt is pump_end for such a set: chunk k holds chunk_samples[k] ELEMENTS of the format (possibly none: the output lags
+ * the input by up to width + orig samples) at (char*)(*chunks) + k * (*row_stride) * element size.  The chunks of a stream, concatenated, are
+ * ntts_codec_convert of its concatenated 24 kHz chunks, bit for bit.  With the native format (zeroed, NULL, or never set) it runs the launches
+ * and copies of ntts_streams_pump_end and returns the same bits.  Plain ntts_streams_pump_end on a set with a non-native format is
+ * NTTS_ESTATE: its float** would lie. */
+int ntts_streams_set_format(ntts_streams* s, const ntts_wav_format* fmt);
+int ntts_streams_pump_end_fmt(ntts_streams* s, int32_t cap, int32_t* n_chunks, int32_t* chunk_stream, int32_t* chunk_samples, int32_t* chunk_last,
+                              const void** chunks, int64_t* row_stride, int32_t* n_running, int32_t* more);
 
 /* ------------------------------------------------------------------------------------------ */
 /* NeuCodec ENCODER engine: reference enrolment.  Replaces                                       */

@@ -19,6 +19,7 @@
 #include "../../include/neutts_hip.h"
 #include "kernels/codec.h"
 #include "kernels/gemm.h"
+#include "wav_stream.h"
 
 using namespace ntts;
 
@@ -777,6 +778,256 @@ extern "C" int ntts_codec_convert(ntts_codec* c, int32_t n, const float* wav, in
         CHIP(c, hipStreamSynchronize(st));
         CHIP(c, hipGetLastError());
     }
+    return NTTS_OK;
+}
+
+// ---- the chunked output stage (wav_stream.h; kernels/codec.h wav_stream_kernel): per-stream counts and history, shared by ntts_wav_stream_* below
+// and ntts_streams_pump_end_fmt (stream.cpp)
+struct ntts::WavStreamCore {
+    ntts_codec* c = nullptr;
+    WavFmt w;
+    ntts_codec::WavTable tb{nullptr, 1, 1, 0, 0};     // coef stays null at 24 kHz
+    int n = 0, max_chunk = 0, max_jobs = 0;
+    long out_stride = 0, hist_stride = 0;
+    std::vector<int64_t> N, M;                        // per stream: input samples received / output samples emitted
+    std::vector<int> n_hist, parity;
+    float* hist = nullptr;                            // device [2][n][hist_stride]
+    void* out = nullptr;                              // device [max_jobs][out_stride] elements
+    WavStreamJob* jobs_dev = nullptr;
+    WavStreamJob* jobs_host = nullptr;                // page-locked
+};
+
+// width and taps of a checked format (wav_table's arithmetic); 0 / 0 at 24 kHz
+static void wav_geometry(const WavFmt& w, int* width, int* taps) {
+    if (w.rate == 24000) { *width = 0; *taps = 0; return; }
+    const double base = std::min(w.orig, w.nw) * 0.99;
+    *width = (int)ceil((double)w.W * w.orig / base);
+    *taps = 2 * *width + w.orig;
+}
+static int64_t wav_count(const WavFmt& w, int width, int64_t N, bool last) {
+    if (w.rate == 24000) return N;
+    if (last) return w.out_len(N);
+    return N >= width ? ((N - width) / w.orig) * w.nw : 0;
+}
+
+int ntts::wav_stream_count_of(ntts_codec* c, const ntts_wav_format* fmt, int64_t n_in_total, bool last, int64_t* n_out_total) {
+    WavFmt w;
+    if (!n_out_total || n_in_total < 0) return cfail(c, NTTS_EINVAL, "ntts_wav_stream_count: null / negative argument");
+    const int rc = wav_fmt_check(c, fmt, &w);
+    if (rc != NTTS_OK) return rc;
+    int width, taps;
+    wav_geometry(w, &width, &taps);
+    *n_out_total = wav_count(w, width, n_in_total, last);
+    return NTTS_OK;
+}
+
+void ntts::wav_core_destroy(WavStreamCore* k) {
+    if (!k) return;
+    hipSetDevice(k->c->device);
+    hipStreamSynchronize(k->c->stream);
+    for (void* b : {(void*)k->hist, k->out, (void*)k->jobs_dev})
+        if (b) hipFree(b);
+    if (k->jobs_host) hipHostFree(k->jobs_host);
+    delete k;
+}
+
+int ntts::wav_core_create(ntts_codec* c, const ntts_wav_format* fmt, int n_streams, int max_chunk_samples, int max_jobs, WavStreamCore** out) {
+    if (!c || !out) return NTTS_EINVAL;
+    WavFmt w;
+    int rc = wav_fmt_check(c, fmt, &w);
+    if (rc != NTTS_OK) return rc;
+    if (n_streams < 1) return cfail(c, NTTS_EINVAL, "wav stream: n_streams %d < 1", n_streams);
+    if (max_chunk_samples < 1) return cfail(c, NTTS_EINVAL, "wav stream: max_chunk_samples %d < 1", max_chunk_samples);
+    if (max_jobs < 1) return cfail(c, NTTS_EINVAL, "wav stream: max_jobs %d < 1", max_jobs);
+    WavStreamCore* k = new WavStreamCore();
+    k->c = c; k->w = w; k->n = n_streams; k->max_chunk = max_chunk_samples; k->max_jobs = max_jobs;
+    k->N.assign(n_streams, 0); k->M.assign(n_streams, 0); k->n_hist.assign(n_streams, 0); k->parity.assign(n_streams, 0);
+    k->out_stride = max_chunk_samples;
+#define KHIP(call)                                                                                        \
+    do {                                                                                                  \
+        hipError_t _s = (call);                                                                           \
+        if (_s != hipSuccess) {                                                                           \
+            rc = cfail(c, _s == 2 ? NTTS_ENOMEM : NTTS_EHIP, "%s failed: %s", #call, hipGetErrorString(_s)); \
+            wav_core_destroy(k);                                                                          \
+            return rc;                                                                                    \
+        }                                                                                                 \
+    } while (0)
+    KHIP(hipSetDevice(c->device));
+    if (w.rate != 24000) {
+        rc = wav_table(c, w, &k->tb);
+        if (rc != NTTS_OK) { wav_core_destroy(k); return rc; }
+        // a chunk emits at most the outputs of its own samples plus those the history was holding back
+        k->out_stride = (long)w.out_len((int64_t)max_chunk_samples + k->tb.taps) + w.nw;
+        k->hist_stride = k->tb.taps;
+        KHIP(hipMalloc((void**)&k->hist, 2 * (size_t)n_streams * k->hist_stride * sizeof(float)));
+        KHIP(hipMemset(k->hist, 0, 2 * (size_t)n_streams * k->hist_stride * sizeof(float)));
+    }
+    if (!w.plain()) {
+        KHIP(hipMalloc(&k->out, (size_t)max_jobs * k->out_stride * w.esz));
+        KHIP(hipMemset(k->out, 0, (size_t)max_jobs * k->out_stride * w.esz));
+        KHIP(hipMalloc((void**)&k->jobs_dev, (size_t)max_jobs * sizeof(WavStreamJob)));
+        KHIP(hipHostMalloc((void**)&k->jobs_host, (size_t)max_jobs * sizeof(WavStreamJob), hipHostMallocDefault));
+    }
+#undef KHIP
+    *out = k;
+    return NTTS_OK;
+}
+
+bool ntts::wav_core_plain(const WavStreamCore* k) { return k->w.plain(); }
+size_t ntts::wav_core_esz(const WavStreamCore* k) { return k->w.esz; }
+long ntts::wav_core_out_stride(const WavStreamCore* k) { return k->out_stride; }
+void* ntts::wav_core_out(const WavStreamCore* k) { return k->out; }
+
+int64_t ntts::wav_core_peek(const WavStreamCore* k, int u, int n_new, bool last) {
+    return wav_count(k->w, k->tb.width, k->N[u] + n_new, last) - k->M[u];
+}
+
+int64_t ntts::wav_core_plan(WavStreamCore* k, int job, int u, int n_new, bool last, int phase) {
+    const int64_t N1 = k->N[u] + n_new, M1 = wav_count(k->w, k->tb.width, N1, last);
+    if (k->jobs_host) {
+        WavStreamJob& j = k->jobs_host[job];
+        j.n_before = (long)k->N[u]; j.m0 = (long)k->M[u]; j.m1 = (long)M1; j.u = u; j.n_new = n_new; j.n_hist = k->n_hist[u];
+        j.parity = k->parity[u]; j.last = last ? 1 : 0; j.phase = phase;
+    }
+    const int64_t n_out = M1 - k->M[u];
+    if (last) {                          // the stream is empty again and may start a new signal
+        k->N[u] = 0; k->M[u] = 0; k->n_hist[u] = 0;
+    } else {
+        k->N[u] = N1; k->M[u] = M1;
+        if (k->tb.coef) {
+            const int64_t first = (M1 / k->w.nw) * k->w.orig - k->tb.width;
+            k->n_hist[u] = (int)(N1 - (first > 0 ? first : 0));         // <= taps - 1
+        }
+    }
+    if (k->tb.coef) k->parity[u] ^= 1;
+    return n_out;
+}
+
+int ntts::wav_core_run(WavStreamCore* k, int n_jobs, const float* in_dev, long in_stride, hipStream_t st) {
+    ntts_codec* c = k->c;
+    if (n_jobs < 1 || k->w.plain()) return NTTS_OK;
+    if (n_jobs > k->max_jobs) return cfail(c, NTTS_EINVAL, "wav stream: %d jobs exceed the %d it was created for", n_jobs, k->max_jobs);
+    for (int j = 0; j < n_jobs; ++j)          // (the rows are sized for the longest chunk: checked, not assumed, before anything is written)
+        if (k->jobs_host[j].m1 - k->jobs_host[j].m0 > k->out_stride || k->jobs_host[j].n_new > in_stride || k->jobs_host[j].n_hist > k->hist_stride)
+            return cfail(c, NTTS_EINVAL, "wav stream: job %d (%d samples in, %ld out) exceeds its rows", j, k->jobs_host[j].n_new,
+                         k->jobs_host[j].m1 - k->jobs_host[j].m0);
+    CHIP(c, hipMemcpyAsync(k->jobs_dev, k->jobs_host, (size_t)n_jobs * sizeof(WavStreamJob), hipMemcpyHostToDevice, st));
+    WavStreamArgs a{};
+    a.f.coef = k->tb.coef; a.f.orig = k->tb.orig; a.f.nw = k->tb.nw; a.f.width = k->tb.width; a.f.taps = k->tb.taps; a.f.enc = k->w.enc;
+    a.f.out = k->out; a.f.out_stride = k->out_stride;
+    a.jobs = k->jobs_dev; a.in = in_dev; a.in_stride = in_stride; a.hist = k->hist; a.hist_stride = k->hist_stride; a.n_streams = k->n;
+    // a stream's two jobs of one round depend on each other through its history row: two launches, phase 0 first (as the cross-fade's)
+    for (int phase = 0; phase < 2; ++phase) {
+        int lo = -1, hi = -1;
+        int64_t longest = 0;
+        for (int j = 0; j < n_jobs; ++j)
+            if (k->jobs_host[j].phase == phase) {
+                if (lo < 0) lo = j;
+                hi = j;
+                longest = std::max<int64_t>(longest, k->jobs_host[j].m1 - k->jobs_host[j].m0);
+            }
+        if (lo < 0) continue;
+        const unsigned gy = (unsigned)std::max<int64_t>(1, (longest + kWavBlock - 1) / kWavBlock);    // (a job without output still leaves its history)
+        NTTS_LAUNCH((wav_stream_kernel), dim3(hi - lo + 1, gy), dim3(256), st, a, lo, phase);
+    }
+    return NTTS_OK;
+}
+
+// ---- ntts_wav_stream_*: the chunked stage alone on host chunks, the streaming twin of ntts_codec_convert
+struct ntts_wav_stream {
+    ntts_codec* c = nullptr;
+    WavStreamCore* k = nullptr;
+    int n = 0, max_chunk = 0;
+    float* in_dev = nullptr;             // [n][max_chunk]
+    std::vector<int> seen;               // per stream: the call that named it last (repeats within one call)
+    int call = 0;
+    std::string err;
+};
+static std::string g_wav_stream_err;
+static int wfail(ntts_wav_stream* ws, int code, const char* fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    if (ws) ws->err = buf; else g_wav_stream_err = buf;
+    return code;
+}
+extern "C" const char* ntts_wav_stream_last_error(const ntts_wav_stream* ws) { return ws ? ws->err.c_str() : g_wav_stream_err.c_str(); }
+
+extern "C" void ntts_wav_stream_destroy(ntts_wav_stream* ws) {
+    if (!ws) return;
+    if (ws->k) wav_core_destroy(ws->k);
+    if (ws->in_dev) hipFree(ws->in_dev);
+    delete ws;
+}
+
+extern "C" int ntts_wav_stream_create(ntts_codec* c, const ntts_wav_format* fmt, int32_t n_streams, int32_t max_chunk_samples, ntts_wav_stream** out) {
+    if (!c || !out) return wfail(nullptr, NTTS_EINVAL, "null argument");
+    ntts_wav_stream* ws = new ntts_wav_stream();
+    ws->c = c; ws->n = n_streams; ws->max_chunk = max_chunk_samples;
+    int rc = wav_core_create(c, fmt, n_streams, max_chunk_samples, n_streams, &ws->k);
+    if (rc != NTTS_OK) { rc = wfail(nullptr, rc, "%s", c->err.c_str()); ntts_wav_stream_destroy(ws); return rc; }
+    if (!wav_core_plain(ws->k) && hipMalloc((void**)&ws->in_dev, (size_t)n_streams * max_chunk_samples * sizeof(float)) != hipSuccess) {
+        (void)hipGetLastError();
+        ntts_wav_stream_destroy(ws);
+        return wfail(nullptr, NTTS_ENOMEM, "wav stream: no device memory for %d x %d samples", n_streams, max_chunk_samples);
+    }
+    ws->seen.assign(n_streams, 0);
+    *out = ws;
+    return NTTS_OK;
+}
+
+extern "C" int ntts_wav_stream_count(const ntts_wav_format* fmt, int64_t n_in_total, int32_t last, int64_t* n_out_total) {
+    const int rc = wav_stream_count_of(nullptr, fmt, n_in_total, last != 0, n_out_total);
+    if (rc != NTTS_OK) wfail(nullptr, rc, "%s", g_codec_create_err.c_str());
+    return rc;
+}
+
+extern "C" int ntts_wav_stream_push(ntts_wav_stream* ws, int32_t n, const int32_t* stream, const float* wav, int64_t in_stride, const int32_t* n_samples,
+                                    const int32_t* last, void* out, int64_t out_stride, int32_t* out_lens) {
+    if (!ws) return NTTS_EINVAL;
+    if (n < 1 || !stream || !wav || !n_samples || !last || !out || !out_lens || in_stride < 0) return wfail(ws, NTTS_EINVAL, "null/empty argument");
+    // ---- every refusal first: nothing is run and no stream's state moves
+    ++ws->call;
+    int64_t Lmax = 0, Omax = 0;
+    for (int i = 0; i < n; ++i) {
+        const int u = stream[i];
+        if (u < 0 || u >= ws->n) return wfail(ws, NTTS_EINVAL, "entry %d: stream %d outside [0, %d)", i, u, ws->n);
+        if (ws->seen[u] == ws->call) return wfail(ws, NTTS_EINVAL, "entry %d: stream %d is named twice in one call", i, u);
+        ws->seen[u] = ws->call;
+        if (n_samples[i] < 0 || n_samples[i] > in_stride)
+            return wfail(ws, NTTS_EINVAL, "entry %d: n_samples %d outside [0, in_stride %ld]", i, n_samples[i], (long)in_stride);
+        if (n_samples[i] > ws->max_chunk) return wfail(ws, NTTS_EINVAL, "entry %d: n_samples %d above max_chunk_samples %d", i, n_samples[i], ws->max_chunk);
+        Lmax = std::max<int64_t>(Lmax, n_samples[i]);
+        Omax = std::max<int64_t>(Omax, wav_core_peek(ws->k, u, n_samples[i], last[i] != 0));
+    }
+    if (out_stride < Omax) return wfail(ws, NTTS_EINVAL, "out_stride %ld < %ld samples", (long)out_stride, (long)Omax);
+    for (int i = 0; i < n; ++i) out_lens[i] = (int32_t)wav_core_plan(ws->k, i, stream[i], n_samples[i], last[i] != 0, 0);
+    if (wav_core_plain(ws->k)) {           // the native format: nothing to compute, nothing is launched
+        for (int i = 0; i < n; ++i) memcpy((float*)out + (size_t)i * out_stride, wav + (size_t)i * in_stride, (size_t)n_samples[i] * sizeof(float));
+        return NTTS_OK;
+    }
+    ntts_codec* c = ws->c;
+    const size_t esz = wav_core_esz(ws->k);
+#define WHIP(call)                                                                                           \
+    do {                                                                                                     \
+        hipError_t _s = (call);                                                                              \
+        if (_s != hipSuccess) return wfail(ws, NTTS_EHIP, "%s failed: %s", #call, hipGetErrorString(_s));     \
+    } while (0)
+    WHIP(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    if (Lmax > 0)
+        WHIP(hipMemcpy2DAsync(ws->in_dev, (size_t)ws->max_chunk * sizeof(float), wav, (size_t)in_stride * sizeof(float), (size_t)Lmax * sizeof(float), n,
+                              hipMemcpyHostToDevice, st));
+    const int rc = wav_core_run(ws->k, n, ws->in_dev, ws->max_chunk, st);      // (also with no output at all: the histories move on)
+    if (rc != NTTS_OK) return wfail(ws, rc, "%s", c->err.c_str());
+    if (Omax > 0)
+        WHIP(hipMemcpy2DAsync(out, (size_t)out_stride * esz, wav_core_out(ws->k), (size_t)wav_core_out_stride(ws->k) * esz, (size_t)Omax * esz, n,
+                              hipMemcpyDeviceToHost, st));
+    WHIP(hipStreamSynchronize(st));
+    WHIP(hipGetLastError());
+#undef WHIP
     return NTTS_OK;
 }
 

@@ -756,4 +756,78 @@ NTTS_KERNEL(256) void wav_format_kernel(WavFormatArgs p) {
     else ((uint8_t*)p.out)[o] = (uint8_t)wav_mulaw(wav_pcm16(y));
 }
 
+// ---- the same stage on a signal that arrives in chunks (ntts_wav_stream_*, ntts_streams_pump_end_fmt) ------------------------------------------------
+// A stream has received N 24 kHz samples and emitted M output samples so far.  Output m = q * nw + p needs the inputs [q * orig - width,
+// q * orig - width + taps): it is emitted as soon as they have all arrived (M = ((N - width) / orig) * nw), the last chunk emits the rest up to
+// ceil(N * nw / orig) with the missing inputs zero.  Sample m is wav_sample's dot product over the operands wav_format_kernel stages for it, so the
+// concatenated chunks are the one-shot stage's output bit for bit.  What the next outputs still need of the inputs so far -- the last
+// N - max(0, (M / nw) * orig - width) of them, at most taps - 1 -- is the stream's history row.  The workgroups of a job read the row while it is
+// replaced: two rows per stream, the job reads `parity` and writes the other (as StreamBlendArgs.prev).
+struct WavStreamJob {
+    long n_before;         // input samples of the stream before this chunk
+    long m0, m1;           // output samples before / after it: the job writes m1 - m0 elements
+    int u;                 // the stream: its history rows
+    int n_new;             // samples of this chunk
+    int n_hist;            // samples in the history row: the inputs [n_before - n_hist, n_before)
+    int parity;            // which of the two rows holds them
+    int last;              // the stream's final chunk: inputs behind it are zero, no history is left
+    int phase;             // the launch this job belongs to (two jobs of one stream in a round: the later one in the later launch)
+};
+struct WavStreamArgs {
+    WavFormatArgs f;       // coef (null at 24 kHz: no filter, no history), orig, nw, width, taps, enc; out = [jobs][out_stride] elements
+    const WavStreamJob* jobs;
+    const float* in;       // [jobs][in_stride]: every job's new samples
+    long in_stride;
+    float* hist;           // [2][n_streams][hist_stride]
+    long hist_stride;
+    int n_streams;
+};
+// input sample `idx` of the job's stream: zero outside [0, N), the chunk from n_before on, the history row below it
+NTTS_D float wav_stream_input(const WavStreamJob& j, const float* pv, const float* nx, long idx) {
+    if (idx < 0 || idx >= j.n_before + j.n_new) return 0.f;
+    if (idx >= j.n_before) return nx[idx - j.n_before];
+    const long h = idx - (j.n_before - j.n_hist);
+    return h >= 0 ? pv[h] : 0.f;         // (never below the row: the history holds what an output not yet emitted can need)
+}
+// grid (jobs of the launch, max(1, ceil(longest output / kWavBlock))); jobs job0 .. job0 + gridDim.x - 1, those of `phase`
+NTTS_KERNEL(256) void wav_stream_kernel(WavStreamArgs p, int job0, int phase) {
+    NTTS_SHARED float span[kWavSpanMax];
+    const int jb = job0 + blockIdx.x;
+    const WavStreamJob j = p.jobs[jb];
+    if (j.phase != phase) return;                             // (block-uniform)
+    const float* nx = p.in + (long)jb * p.in_stride;
+    const float* pv = p.hist + ((long)j.parity * p.n_streams + j.u) * p.hist_stride;
+    float* nv = p.hist + ((long)(j.parity ^ 1) * p.n_streams + j.u) * p.hist_stride;
+    const long N = j.n_before + j.n_new;
+    const long mb = j.m0 + (long)blockIdx.y * kWavBlock;       // first output sample of this workgroup
+    if (mb < j.m1) {                                          // (block-uniform: everybody reaches the barrier or nobody)
+        const long m = mb + threadIdx.x;
+        float y = 0.f;
+        if (p.f.coef) {
+            const long m_last = (mb + kWavBlock < j.m1 ? mb + kWavBlock : j.m1) - 1;
+            const long q0 = mb / p.f.nw;
+            const long i0 = q0 * p.f.orig - p.f.width;
+            const int n_span = (int)((m_last / p.f.nw - q0) * p.f.orig) + p.f.taps;   // <= kWavSpanMax (host check, as wav_format_kernel)
+            for (int i = threadIdx.x; i < n_span; i += 256) span[i] = wav_stream_input(j, pv, nx, i0 + i);   // a span across history and chunk: by index
+            sync();
+            if (m < j.m1) y = wav_sample(p.f, span, q0, m);
+        } else if (m < j.m1) {
+            y = nx[m - j.n_before];                            // 24 kHz: output m is input m
+        }
+        if (m < j.m1) {
+            const long o = (long)jb * p.f.out_stride + (m - j.m0);
+            if (p.f.enc == kWavF32) ((float*)p.f.out)[o] = y;
+            else if (p.f.enc == kWavPcm16) ((int16_t*)p.f.out)[o] = (int16_t)wav_pcm16(y);
+            else ((uint8_t*)p.f.out)[o] = (uint8_t)wav_mulaw(wav_pcm16(y));
+        }
+    }
+    if (!p.f.coef || j.last) return;
+    // the history the next chunk finds (in the other row): the inputs from the first one output m1 reads
+    const long first = (j.m1 / p.f.nw) * p.f.orig - p.f.width;
+    const long h0 = first > 0 ? first : 0;
+    long keep = N - h0;                                        // <= taps - 1 (m1 counts every output whose inputs have arrived)
+    if (keep > p.hist_stride) keep = p.hist_stride;            // (never past the row, whatever the job says)
+    for (int x = blockIdx.y * 256 + threadIdx.x; x < keep; x += gridDim.y * 256) nv[x] = wav_stream_input(j, pv, nx, h0 + x);
+}
+
 }  // namespace ntts

@@ -17,6 +17,7 @@
 
 #include "../../include/neutts_hip.h"
 #include "kernels/stream.h"
+#include "wav_stream.h"
 
 using namespace ntts;
 
@@ -48,6 +49,9 @@ struct ntts_streams {
     bool snap_open = false, have_snap = false;
     // host view of every stream
     std::vector<int> n_dec, prev_len, frames, done;
+    // output format of the chunks (ntts_streams_set_format): the chunked output stage behind the cross-fade; null = 24 kHz float32
+    WavStreamCore* fmt = nullptr;
+    bool pumped = false;                            // a pump has begun: the format is fixed
     std::string err;
 };
 
@@ -74,6 +78,7 @@ extern "C" void ntts_streams_destroy(ntts_streams* s) {
     hipSetDevice(s->device);
     if (s->cst) hipStreamSynchronize(s->cst);
     if (s->est) hipStreamSynchronize(s->est);
+    if (s->fmt) wav_core_destroy(s->fmt);
     for (void* b : {(void*)s->ibuf, (void*)s->win, (void*)s->wav_win, (void*)s->prev, (void*)s->out_dev, (void*)s->jobs_dev, (void*)s->parity_dev})
         if (b) hipFree(b);
     for (void* b : {(void*)s->snap_host, (void*)s->out_host, (void*)s->jobs_host, (void*)s->parity_host})
@@ -180,6 +185,7 @@ extern "C" int ntts_streams_pump_begin(ntts_streams* s) {
     SHIP(s, hipMemcpyAsync(s->snap_host, s->clen, 2 * (size_t)s->n * sizeof(int), hipMemcpyDeviceToHost, s->est));   // clen | fin are adjacent
     SHIP(s, hipEventRecord(s->ev_snap, s->est));
     s->snap_open = true;
+    s->pumped = true;
     return NTTS_OK;
 }
 
@@ -198,8 +204,76 @@ extern "C" int ntts_streams_pump_wait(ntts_streams* s, int32_t* n_running) {
     return NTTS_OK;
 }
 
-extern "C" int ntts_streams_pump_end(ntts_streams* s, int32_t cap, int32_t* n_chunks, int32_t* chunk_stream, int32_t* chunk_samples,
-                                     int32_t* chunk_last, const float** chunks, int64_t* row_stride, int32_t* n_running, int32_t* more) {
+// The output format of the set's chunks: legal until the first pump_begin.  A non-native format puts the chunked output stage (kernels/codec.h
+// wav_stream_kernel, one history row per stream) behind the cross-fade; the native one (zeroed or null) takes it away again.
+extern "C" int ntts_streams_set_format(ntts_streams* s, const ntts_wav_format* fmt) {
+    if (!s) return NTTS_EINVAL;
+    if (s->pumped) return sfail(s, NTTS_ESTATE, "the format of a stream set is fixed once a pump has begun");
+    SHIP(s, hipSetDevice(s->device));
+    WavStreamCore* k = nullptr;
+    const int rc = wav_core_create(s->c, fmt, s->n, (int)s->out_stride, 2 * s->n, &k);
+    if (rc != NTTS_OK) return sfail(s, rc, "%s", ntts_codec_last_error(s->c));
+    if (s->fmt) wav_core_destroy(s->fmt);
+    s->fmt = nullptr;
+    if (wav_core_plain(k)) { wav_core_destroy(k); return NTTS_OK; }
+    // the page-locked buffer holds 2 n rows of the format's elements (48 kHz float32 is the largest: twice the native row)
+    const size_t need = 2 * (size_t)s->n * wav_core_out_stride(k) * wav_core_esz(k), have = 2 * (size_t)s->n * s->out_stride * sizeof(float);
+    if (need > have) {
+        float* nb = nullptr;
+        if (hipHostMalloc((void**)&nb, need, hipHostMallocDefault) != hipSuccess) {
+            (void)hipGetLastError();
+            wav_core_destroy(k);
+            return sfail(s, NTTS_ENOMEM, "no page-locked memory for %zu bytes of chunks", need);
+        }
+        hipHostFree(s->out_host);
+        s->out_host = nb;
+    }
+    s->fmt = k;
+    return NTTS_OK;
+}
+
+// the round's J windows on the codec's stream: window codes -> codec pass(es) -> cross-fade into out_dev [J][out_stride]
+static int pump_windows(ntts_streams* s, int J, int stride) {
+    SHIP(s, hipMemcpyAsync(s->jobs_dev, s->jobs_host, (size_t)J * sizeof(StreamJob), hipMemcpyHostToDevice, s->cst));
+    SHIP(s, hipMemcpyAsync(s->parity_dev, s->parity_host, (size_t)J * sizeof(int), hipMemcpyHostToDevice, s->cst));
+    StreamGatherArgs ga{};
+    ga.jobs = s->jobs_dev; ga.cache = s->cache; ga.cache_stride = s->cache_stride; ga.win = s->win; ga.win_stride = s->W;
+    NTTS_LAUNCH((stream_gather_kernel), dim3(J), dim3(128), s->cst, ga);
+    std::vector<int> lens(J);
+    for (int k = 0; k < J; ++k) lens[k] = s->jobs_host[k].t1 - s->jobs_host[k].t0;
+    for (int k0 = 0; k0 < J;) {                             // as many windows per codec pass as its workspace holds
+        long rows = 0;
+        int k1 = k0, tmax = 0;
+        while (k1 < J) {
+            const int tm = lens[k1] > tmax ? lens[k1] : tmax;
+            if (rows + lens[k1] + 6 > s->max_rows || (long)(k1 - k0 + 1) * tm > s->max_rows) break;
+            rows += lens[k1] + 6; tmax = tm; ++k1;
+        }
+        if (k1 == k0) return sfail(s, NTTS_EINVAL, "the codec engine's max_rows %ld cannot hold one window", s->max_rows);
+        const int rc = ntts_codec_decode_dev(s->c, k1 - k0, s->win + (size_t)k0 * s->W, s->W, lens.data() + k0, s->wav_win + (size_t)k0 * s->wav_stride,
+                                             s->wav_stride, 1, nullptr);
+        if (rc != NTTS_OK) return sfail(s, rc, "codec pass: %s", ntts_codec_last_error(s->c));
+        k0 = k1;
+    }
+    StreamBlendArgs ba{};
+    ba.jobs = s->jobs_dev; ba.wav = s->wav_win; ba.wav_stride = s->wav_stride; ba.prev = s->prev; ba.prev_stride = s->prev_stride;
+    ba.parity = s->parity_dev; ba.n_streams = s->n; ba.stride = stride; ba.out = s->out_dev; ba.out_stride = s->out_stride;
+    // a stream's regular and final window of one round depend on each other through `prev`: the final windows are listed behind all
+    // regular ones of their stream (add() order), so two launches -- regular jobs, then final jobs -- keep the order without atomics
+    for (int phase = 0; phase < 2; ++phase) {
+        int a = -1, b = -1;
+        for (int k = 0; k < J; ++k)
+            if (((s->jobs_host[k].flags >> 1) & 1) == phase) { if (a < 0) a = k; b = k; }
+        if (a < 0) continue;
+        // (jobs of the two kinds interleave in the list: launch over the whole range and let the other kind return at once)
+        StreamBlendArgs pa = ba;
+        NTTS_LAUNCH((stream_blend_phase_kernel), dim3(b - a + 1, 8), dim3(256), s->cst, pa, a, phase);
+    }
+    return NTTS_OK;
+}
+
+static int pump_end_impl(ntts_streams* s, int32_t cap, int32_t* n_chunks, int32_t* chunk_stream, int32_t* chunk_samples,
+                         int32_t* chunk_last, const void** chunks, int64_t* row_stride, int32_t* n_running, int32_t* more) {
     if (!s || !n_chunks || !chunk_stream || !chunk_samples || !chunk_last || !chunks || !row_stride || cap < 2 * s->n) return sfail(s, NTTS_EINVAL, "bad argument (cap >= 2 n)");
     if (!s->snap_open && !s->have_snap) return sfail(s, NTTS_ESTATE, "no pump is open (ntts_streams_pump_begin first)");
     SHIP(s, hipSetDevice(s->device));
@@ -215,7 +289,7 @@ extern "C" int ntts_streams_pump_end(ntts_streams* s, int32_t cap, int32_t* n_ch
     // ---- which windows exist now (ref:neutts/neutts.py:401-415 / :443-459): per stream at most one regular window per round, and its
     //      final window once it has finished and no regular window is left
     int J = 0, pending = 0, running = 0;
-    std::vector<int> last_of(n, 0);
+    std::vector<int> flush;                                 // formatted streams that end without a final window: their held-back outputs
     auto add = [&](int u, int t0, int t1, int s0, int n1, bool last) {
         StreamJob& j = s->jobs_host[J];
         const bool hp = s->frames[u] > 0;
@@ -247,17 +321,28 @@ extern "C" int ntts_streams_pump_end(ntts_streams* s, int32_t cap, int32_t* n_ch
                 if (s0 < 0) return sfail(s, NTTS_EINVAL, "stream %d: final window starts before its first frame", u);
                 add(u, t0, clen[u], s0, (clen[u] - t0) * hop - s0, true);
                 s->n_dec[u] = clen[u];
+            } else if (s->fmt && s->frames[u] > 0) {
+                flush.push_back(u);                         // (the tokens ended on a window's edge: lookforward 0 only)
             }
             s->done[u] = 1;
         }
     }
-    *n_chunks = J;
+    // the output stage's jobs: one per blended chunk, then the flushes (no new samples: chunks of their own, behind the round's others)
+    const int Jw = J + (int)flush.size();
+    *n_chunks = Jw;
     *chunks = s->out_host;
-    *row_stride = s->out_stride;
+    *row_stride = s->fmt ? wav_core_out_stride(s->fmt) : s->out_stride;
+    // with an output format every blended chunk is one job of the chunked output stage: its samples in that format are what the caller gets
+    for (int k = 0; k < J && s->fmt; ++k)
+        chunk_samples[k] = (int32_t)wav_core_plan(s->fmt, k, s->jobs_host[k].u, s->jobs_host[k].out_len, chunk_last[k] != 0, chunk_last[k] ? 1 : 0);
+    for (int k = J; k < Jw; ++k) {
+        chunk_stream[k] = flush[k - J]; chunk_last[k] = 1;
+        chunk_samples[k] = (int32_t)wav_core_plan(s->fmt, k, flush[k - J], 0, true, 1);
+    }
     if (n_running) *n_running = running;
     if (more) *more = pending > 0 ? 1 : 0;
     if (pending == 0) s->have_snap = false;
-    if (J == 0) return NTTS_OK;
+    if (Jw == 0) return NTTS_OK;
     // ---- device: window codes -> codec pass(es) -> cross-fade -> the new samples to page-locked memory; all on the codec's stream, behind
     //      the append (ev_snap was recorded after it on the backbone's stream), beside whatever the backbone runs next
     {   // (ntts_codec_set_cu_mask re-creates the codec's stream: ask for it every time)
@@ -266,45 +351,33 @@ extern "C" int ntts_streams_pump_end(ntts_streams* s, int32_t cap, int32_t* n_ch
         s->cst = (hipStream_t)st;
     }
     SHIP(s, hipStreamWaitEvent(s->cst, s->ev_snap, 0));
-    SHIP(s, hipMemcpyAsync(s->jobs_dev, s->jobs_host, (size_t)J * sizeof(StreamJob), hipMemcpyHostToDevice, s->cst));
-    SHIP(s, hipMemcpyAsync(s->parity_dev, s->parity_host, (size_t)J * sizeof(int), hipMemcpyHostToDevice, s->cst));
-    StreamGatherArgs ga{};
-    ga.jobs = s->jobs_dev; ga.cache = s->cache; ga.cache_stride = s->cache_stride; ga.win = s->win; ga.win_stride = s->W;
-    NTTS_LAUNCH((stream_gather_kernel), dim3(J), dim3(128), s->cst, ga);
-    std::vector<int> lens(J);
-    for (int k = 0; k < J; ++k) lens[k] = s->jobs_host[k].t1 - s->jobs_host[k].t0;
-    for (int k0 = 0; k0 < J;) {                             // as many windows per codec pass as its workspace holds
-        long rows = 0;
-        int k1 = k0, tmax = 0;
-        while (k1 < J) {
-            const int tm = lens[k1] > tmax ? lens[k1] : tmax;
-            if (rows + lens[k1] + 6 > s->max_rows || (long)(k1 - k0 + 1) * tm > s->max_rows) break;
-            rows += lens[k1] + 6; tmax = tm; ++k1;
-        }
-        if (k1 == k0) return sfail(s, NTTS_EINVAL, "the codec engine's max_rows %ld cannot hold one window", s->max_rows);
-        const int rc = ntts_codec_decode_dev(s->c, k1 - k0, s->win + (size_t)k0 * s->W, s->W, lens.data() + k0, s->wav_win + (size_t)k0 * s->wav_stride,
-                                             s->wav_stride, 1, nullptr);
-        if (rc != NTTS_OK) return sfail(s, rc, "codec pass: %s", ntts_codec_last_error(s->c));
-        k0 = k1;
+    if (J > 0) {
+        const int rc = pump_windows(s, J, stride);
+        if (rc != NTTS_OK) return rc;
     }
-    StreamBlendArgs ba{};
-    ba.jobs = s->jobs_dev; ba.wav = s->wav_win; ba.wav_stride = s->wav_stride; ba.prev = s->prev; ba.prev_stride = s->prev_stride;
-    ba.parity = s->parity_dev; ba.n_streams = n; ba.stride = stride; ba.out = s->out_dev; ba.out_stride = s->out_stride;
-    // a stream's regular and final window of one round depend on each other through `prev`: the final windows are listed behind all
-    // regular ones of their stream (add() order), so two launches -- regular jobs, then final jobs -- keep the order without atomics
-    for (int phase = 0; phase < 2; ++phase) {
-        int a = -1, b = -1;
-        for (int k = 0; k < J; ++k)
-            if (((s->jobs_host[k].flags >> 1) & 1) == phase) { if (a < 0) a = k; b = k; }
-        if (a < 0) continue;
-        // (jobs of the two kinds interleave in the list: launch over the whole range and let the other kind return at once)
-        StreamBlendArgs pa = ba;
-        NTTS_LAUNCH((stream_blend_phase_kernel), dim3(b - a + 1, 8), dim3(256), s->cst, pa, a, phase);
+    if (s->fmt) {      // behind the cross-fade, on the samples where they are; the copy is sized in the format's elements
+        const int rc = wav_core_run(s->fmt, Jw, s->out_dev, s->out_stride, s->cst);
+        if (rc != NTTS_OK) return sfail(s, rc, "output stage: %s", ntts_codec_last_error(s->c));
+        SHIP(s, hipMemcpyAsync(s->out_host, wav_core_out(s->fmt), (size_t)Jw * wav_core_out_stride(s->fmt) * wav_core_esz(s->fmt), hipMemcpyDeviceToHost, s->cst));
+    } else {
+        SHIP(s, hipMemcpyAsync(s->out_host, s->out_dev, (size_t)J * s->out_stride * sizeof(float), hipMemcpyDeviceToHost, s->cst));
     }
-    SHIP(s, hipMemcpyAsync(s->out_host, s->out_dev, (size_t)J * s->out_stride * sizeof(float), hipMemcpyDeviceToHost, s->cst));
     SHIP(s, hipStreamSynchronize(s->cst));
     SHIP(s, hipGetLastError());
     return NTTS_OK;
+}
+
+extern "C" int ntts_streams_pump_end(ntts_streams* s, int32_t cap, int32_t* n_chunks, int32_t* chunk_stream, int32_t* chunk_samples,
+                                     int32_t* chunk_last, const float** chunks, int64_t* row_stride, int32_t* n_running, int32_t* more) {
+    if (s && s->fmt) return sfail(s, NTTS_ESTATE, "the set has an output format (ntts_streams_set_format): its chunks are not float32, use ntts_streams_pump_end_fmt");
+    return pump_end_impl(s, cap, n_chunks, chunk_stream, chunk_samples, chunk_last, (const void**)chunks, row_stride, n_running, more);
+}
+
+// pump_end for a set with an output format: chunk k holds chunk_samples[k] ELEMENTS of the format at (*chunks) + k * (*row_stride) elements.
+// With the native format: the launches, the copy and the bits of ntts_streams_pump_end.
+extern "C" int ntts_streams_pump_end_fmt(ntts_streams* s, int32_t cap, int32_t* n_chunks, int32_t* chunk_stream, int32_t* chunk_samples,
+                                         int32_t* chunk_last, const void** chunks, int64_t* row_stride, int32_t* n_running, int32_t* more) {
+    return pump_end_impl(s, cap, n_chunks, chunk_stream, chunk_samples, chunk_last, chunks, row_stride, n_running, more);
 }
 
 extern "C" int ntts_streams_done(ntts_streams* s, int32_t* n_done) {

@@ -167,6 +167,14 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "ntts_codec_decode_fmt": (C.c_int, [p, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(WavFormatC), p, i64, C.POINTER(i32)]),
         "ntts_codec_decode_dev_fmt": (C.c_int, [p, i32, p, i32, C.POINTER(i32), p, i64, i32, p, C.POINTER(WavFormatC), C.POINTER(i32)]),
         "ntts_codec_convert": (C.c_int, [p, i32, C.POINTER(f32), i64, C.POINTER(i32), C.POINTER(WavFormatC), p, i64, C.POINTER(i32)]),
+        "ntts_wav_stream_create": (C.c_int, [p, C.POINTER(WavFormatC), i32, i32, C.POINTER(p)]),
+        "ntts_wav_stream_destroy": (None, [p]),
+        "ntts_wav_stream_last_error": (C.c_char_p, [p]),
+        "ntts_wav_stream_push": (C.c_int, [p, i32, C.POINTER(i32), C.POINTER(f32), i64, C.POINTER(i32), C.POINTER(i32), p, i64, C.POINTER(i32)]),
+        "ntts_wav_stream_count": (C.c_int, [C.POINTER(WavFormatC), i64, i32, C.POINTER(i64)]),
+        "ntts_streams_set_format": (C.c_int, [p, C.POINTER(WavFormatC)]),
+        "ntts_streams_pump_end_fmt": (C.c_int, [p, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(p),
+                                                C.POINTER(i64), C.POINTER(i32), C.POINTER(i32)]),
         "ntts_encoder_last_error": (C.c_char_p, [p]),
         "ntts_encoder_create": (C.c_int, [C.POINTER(EncoderConfigC), C.c_int, C.POINTER(p)]),
         "ntts_encoder_destroy": (None, [p]),
@@ -1427,6 +1435,10 @@ class CodecEngine:
         out, out_lens = self.convert_array(buf, n_samples, sample_rate, encoding, filter_width)
         return [out[r, : int(out_lens[r])] for r in range(len(wavs))]
 
+    def stream_converter(self, n: int = 1, sample_rate=None, encoding="f32", filter_width=None, max_chunk_samples: int = 16384) -> "WavStream":
+        """The output stage for `n` signals that arrive in chunks (ntts_wav_stream_*): the streaming twin of `convert`."""
+        return WavStream(self, n, sample_rate, encoding, filter_width, max_chunk_samples)
+
     def set_debug(self, keep_stages: bool):
         self._chk(self.lib.ntts_codec_set_debug(self.h, int(keep_stages)))
 
@@ -1486,6 +1498,85 @@ class CodecEngine:
         return ms.value
 
 
+class WavStream:
+    """The codec's output stage on `n` independent 24 kHz float32 signals that arrive in chunks (ntts_wav_stream_*): every stream keeps the
+    few input samples its next outputs still need, and its chunks, concatenated, are CodecEngine.convert of the concatenated signal bit for
+    bit.  A chunk's output lags its input by up to width + orig samples; `last` flushes a stream, which is then empty and may start again."""
+
+    def __init__(self, codec: "CodecEngine", n: int = 1, sample_rate=None, encoding="f32", filter_width=None, max_chunk_samples: int = 16384):
+        self.lib = codec.lib
+        self.fmt, self.dtype, self.native = wav_format(sample_rate, encoding, filter_width)
+        self.n, self.max_chunk_samples = int(n), int(max_chunk_samples)
+        h = C.c_void_p()
+        rc = self.lib.ntts_wav_stream_create(codec.h, C.byref(self.fmt), self.n, self.max_chunk_samples, C.byref(h))
+        if rc != 0:
+            raise NeuTTSHipError(rc, (self.lib.ntts_wav_stream_last_error(None) or b"").decode())
+        self.h = h
+        self._keep = codec                                               # the converter borrows the engine
+        self._total = [0] * self.n                                       # input samples of every stream's current signal
+
+    def _chk(self, rc: int):
+        if rc != 0:
+            raise NeuTTSHipError(rc, (self.lib.ntts_wav_stream_last_error(self.h) or b"").decode())
+
+    def out_count(self, n_in_total: int, last: bool = False) -> int:
+        """Output samples a stream has emitted in all after n_in_total input samples (ntts_wav_stream_count)."""
+        m = C.c_int64()
+        rc = self.lib.ntts_wav_stream_count(C.byref(self.fmt), int(n_in_total), int(bool(last)), C.byref(m))
+        if rc != 0:
+            raise NeuTTSHipError(rc, (self.lib.ntts_wav_stream_last_error(None) or b"").decode())
+        return m.value
+
+    def push_array(self, streams, wav: np.ndarray, n_samples, last, out_stride: Optional[int] = None):
+        """One ntts_wav_stream_push: wav [k, in_stride] float32, row i = n_samples[i] new samples of stream streams[i] (its final chunk if
+        last[i]) -> ([k, out_stride] array of the encoding's dtype, elements per row)."""
+        wav = np.ascontiguousarray(wav, dtype=np.float32)
+        k, in_stride = wav.shape
+        st = np.ascontiguousarray(streams, dtype=np.int32)
+        ns = np.ascontiguousarray(n_samples, dtype=np.int32)
+        la = np.ascontiguousarray(np.asarray(last).astype(np.int32))
+        if not (len(st) == len(ns) == len(la) == k):
+            raise ValueError(f"streams / n_samples / last: {len(st)} / {len(ns)} / {len(la)} values for {k} rows")
+        if out_stride is None:          # what the longest chunk of this call can emit, the stream's held-back outputs included
+            out_stride = max([1] + [self.out_count(self._total[int(u)] + int(v), bool(f)) - self.out_count(self._total[int(u)])
+                                    for u, v, f in zip(st, ns, la) if 0 <= int(u) < self.n and int(v) >= 0])
+        out_stride = int(out_stride)
+        buf = np.zeros(max(1, k * max(0, out_stride)), dtype=self.dtype)
+        out_lens = np.zeros(k, dtype=np.int32)
+        i32p = C.POINTER(C.c_int32)
+        self._chk(self.lib.ntts_wav_stream_push(self.h, k, st.ctypes.data_as(i32p), wav.ctypes.data_as(C.POINTER(C.c_float)), in_stride,
+                                                ns.ctypes.data_as(i32p), la.ctypes.data_as(i32p), C.c_void_p(buf.ctypes.data), out_stride,
+                                                out_lens.ctypes.data_as(i32p)))
+        for u, v, f in zip(st, ns, la):
+            self._total[int(u)] = 0 if f else self._total[int(u)] + int(v)
+        return buf[: k * out_stride].reshape(k, out_stride), out_lens
+
+    def push(self, chunks: Sequence[np.ndarray], streams: Optional[Sequence[int]] = None, last=False) -> List[np.ndarray]:
+        """chunks: one 1-D float32 array per entry, for streams `streams` (default 0, 1, ...); last: one flag or one per entry -> the chunks in
+        the output format."""
+        chunks = [np.asarray(c, dtype=np.float32).reshape(-1) for c in chunks]
+        if not chunks:
+            return []
+        streams = list(range(len(chunks))) if streams is None else list(streams)
+        last = [bool(last)] * len(chunks) if isinstance(last, (bool, np.bool_, int)) else [bool(f) for f in last]
+        buf = np.zeros((len(chunks), max(1, max(len(c) for c in chunks))), dtype=np.float32)
+        for r, c in enumerate(chunks):
+            buf[r, : len(c)] = c
+        out, out_lens = self.push_array(streams, buf, [len(c) for c in chunks], last)
+        return [out[r, : int(out_lens[r])] for r in range(len(chunks))]
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.ntts_wav_stream_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class StreamSet:
     """Device-side streaming state of `n` concurrent infer_stream utterances (ntts_streams_*, ABI 6): token caches, window assembly,
     the 27-frame slice and the cross-fade with the previous chunk (ref:neutts/neutts.py:385-388, :401-465) run on the device; per burst
@@ -1493,7 +1584,8 @@ class StreamSet:
 
     def __init__(self, backbone: "BackboneEngine", codec: "CodecEngine", slots: Sequence[int], ref_codes: Sequence[Sequence[int]],
                  max_new_tokens: int, chunk: int, lookforward: int, lookback: int, overlap: int, hop_length: int, speech_base: int,
-                 n_codes: int, modulo: bool = False):
+                 n_codes: int, modulo: bool = False, fmt=None):
+        """fmt: None (24 kHz float32 chunks) or (sample_rate, encoding, filter_width): the chunked output stage behind the cross-fade."""
         self.lib = backbone.lib
         self.n = len(slots)
         prm = StreamParamsC(chunk, lookforward, lookback, overlap, hop_length, speech_base, n_codes, int(bool(modulo)))
@@ -1510,6 +1602,16 @@ class StreamSet:
         self._keep = (backbone, codec)                                   # the set borrows both engines
         cap = 2 * self.n
         self._cs, self._cn, self._cl = (np.zeros(cap, dtype=np.int32) for _ in range(3))
+        self._fmt = None
+        if fmt is not None:
+            fc, dtype, native = wav_format(*fmt)
+            if not native:                                               # (the native format spelled out: the calls of a set without one)
+                self.set_format(fc)
+                self._fmt = (fc, dtype)
+
+    def set_format(self, fc: "WavFormatC"):
+        """ntts_streams_set_format as it is: legal until the first pump_begin."""
+        self._chk(self.lib.ntts_streams_set_format(self.h, C.byref(fc) if fc is not None else None))
 
     def _chk(self, rc: int):
         if rc != 0:
@@ -1526,9 +1628,21 @@ class StreamSet:
         return run.value
 
     def pump_end(self):
-        """-> (chunks, n_running, more): chunks = [(stream, samples (view of pinned memory, valid until the next pump_end), last)]."""
+        """-> (chunks, n_running, more): chunks = [(stream, samples (view of pinned memory, valid until the next pump_end), last)]; with an
+        output format the samples are of its dtype (and a chunk may be empty)."""
         i32p = C.POINTER(C.c_int32)
         n, run, more = C.c_int32(), C.c_int32(), C.c_int32()
+        if self._fmt is not None:
+            dtype = np.dtype(self._fmt[1])
+            vptr, stride = C.c_void_p(), C.c_int64()
+            self._chk(self.lib.ntts_streams_pump_end_fmt(self.h, len(self._cs), C.byref(n), self._cs.ctypes.data_as(i32p), self._cn.ctypes.data_as(i32p),
+                                                         self._cl.ctypes.data_as(i32p), C.byref(vptr), C.byref(stride), C.byref(run), C.byref(more)))
+            out = []
+            if n.value:
+                nbytes = n.value * stride.value * dtype.itemsize
+                buf = np.frombuffer((C.c_char * nbytes).from_address(vptr.value), dtype=dtype).reshape(n.value, stride.value)
+                out = [(int(self._cs[k]), buf[k, : int(self._cn[k])], bool(self._cl[k])) for k in range(n.value)]
+            return out, run.value, bool(more.value)
         ptr, stride = C.POINTER(C.c_float)(), C.c_int64()
         self._chk(self.lib.ntts_streams_pump_end(self.h, len(self._cs), C.byref(n), self._cs.ctypes.data_as(i32p), self._cn.ctypes.data_as(i32p),
                                                  self._cl.ctypes.data_as(i32p), C.byref(ptr), C.byref(stride), C.byref(run), C.byref(more)))

@@ -191,6 +191,9 @@ def _check_output(sample_rate, encoding, filter_width, who: str = "") -> None:
     _hip.wav_format(sample_rate, encoding, filter_width, who)
 
 
+_INSTANCE_FORMAT = object()      # "the instance's stream_* attributes" as a default argument (None is the native format)
+
+
 def sequence_score(logprobs) -> float:
     """A candidate's score: the arithmetic mean of its per-token log-probabilities (-inf for an empty one)."""
     lp = np.asarray(logprobs, dtype=np.float64)
@@ -224,18 +227,29 @@ class NeuTTS:
         output_sample_rate: int = 24_000,
         output_encoding: str = "f32",
         output_filter_width: int = 6,
+        stream_sample_rate: int = 24_000,
+        stream_encoding: str = "f32",
+        stream_filter_width: Optional[int] = None,
     ):
         # Consts (ref:neutts/neutts.py:84-91)
         self.sample_rate = 24_000            # the NATIVE rate (the codec's; what a watermarker sees), whatever the output format
         # Output format of infer / infer_batch / decode_codes (the reference hands out 24 kHz float32, ref:neutts/neutts.py:288-291, and its users
         # resample and cast on the host): one of _hip.WAV_RATES, "f32" / "pcm16" (int16) / "mulaw" (uint8, G.711), the resampler's
         # lowpass_filter_width (torchaudio's default 6 rolls off early: telephony callers want 16 or more).  Applied on the device behind the codec
-        # pass (include/neutts_hip.h ntts_wav_format); sample_rate= / encoding= per call override the first two.  The streaming entry points
-        # take the default format only: chunked resampling needs per-stream filter history across chunk edges.
+        # pass (include/neutts_hip.h ntts_wav_format); sample_rate= / encoding= per call override the first two.
         _check_output(output_sample_rate, output_encoding, output_filter_width, "output_")
         self.output_sample_rate = int(output_sample_rate)
         self.output_encoding = output_encoding
         self.output_filter_width = int(output_filter_width)
+        # Format of the chunks of infer_stream / infer_stream_batch: a property of the transport, apart from the one above (a server hands mu-law
+        # to its phone legs and keeps float files from infer).  The same stage with one history row of at most taps - 1 samples per stream
+        # (ntts_streams_set_format / ntts_wav_stream_*): a stream's chunks, concatenated, are the one-shot stage's output of its concatenated
+        # 24 kHz chunks bit for bit; they lag the native ones by up to width + orig input samples (under 10 ms).  stream_filter_width None =
+        # output_filter_width.  stream_sample_rate= / stream_encoding= / stream_filter_width= per call override them.
+        _check_output(stream_sample_rate, stream_encoding, output_filter_width if stream_filter_width is None else stream_filter_width, "stream_")
+        self.stream_sample_rate = int(stream_sample_rate)
+        self.stream_encoding = stream_encoding
+        self.stream_filter_width = None if stream_filter_width is None else int(stream_filter_width)
         self.max_context = 2048
         self.hop_length = 480
         self.streaming_overlap_frames = 1
@@ -486,23 +500,29 @@ class NeuTTS:
 
     def infer_stream(self, text: str, ref_codes, ref_text: str, *, temperature=None, top_k=None, top_p=None, min_p=None, **repetition) -> Generator[np.ndarray, None, None]:
         """Streaming synthesis with the reference's window / cross-fade semantics (ref:neutts/neutts.py:373-465).  Sampling overrides as `infer`
-        (checked here, before the generator is handed out).  Chunks are 24 kHz float32: any other output format is a ValueError."""
+        (checked here, before the generator is handed out).  Chunks are 24 kHz float32 unless stream_sample_rate= / stream_encoding= /
+        stream_filter_width= (or the instance's stream_* attributes) say otherwise; sample_rate= / encoding= / a non-native output_* attribute
+        stay a ValueError here."""
         self._refuse_stream_output(repetition.pop("sample_rate", None), repetition.pop("encoding", None), "infer_stream")
+        fmt = self._resolve_stream_output(repetition.pop("stream_sample_rate", None), repetition.pop("stream_encoding", None),
+                                          repetition.pop("stream_filter_width", None))
         samp = self._resolve_sampling(1, temperature, top_k, top_p, min_p, repetition)
         prompt_ids = self._apply_chat_template(ref_codes, ref_text, text)
         ref = [int(c) for c in _to_list(ref_codes)]
         if self._stream_on_device([ref]):       # token cache, windows, codec pass and cross-fade on the device (csrc/stream.cpp): a set of one stream
-            return (chunk for _, chunk in self._infer_stream_batch_hip([prompt_ids], [ref], samp))
-        return self._infer_stream_hip(prompt_ids, ref, samp)        # host loop: a watermarker (a host library) sits between the codec and the slice
+            return (chunk for _, chunk in self._infer_stream_batch_hip([prompt_ids], [ref], samp, fmt))
+        return self._infer_stream_hip(prompt_ids, ref, samp, fmt)   # host loop: a watermarker (a host library) sits between the codec and the slice
 
     def infer_stream_batch(self, texts: Sequence[str], ref_codes, ref_texts, *, temperature=None, top_k=None, top_p=None, min_p=None, **repetition) -> Generator[tuple, None, None]:
         """Many utterances streamed at once (BASELINE config 5's shape: a decode batch with the codec on its own stream):
         yields `(utterance index, chunk)` pairs; the chunks of one utterance, in order, are exactly what `infer_stream`
         yields for it.  One decode burst serves every running utterance, and all windows that became decodable in a burst
         go through the codec in ONE batched call, enqueued behind the next burst (the two engines' streams overlap).
-        At most `max_batch` utterances (the engine's decode slots) per call.  Sampling overrides as `infer_batch`.  Chunks are 24 kHz float32:
-        any other output format is a ValueError."""
+        At most `max_batch` utterances (the engine's decode slots) per call.  Sampling overrides as `infer_batch`.  Chunk format as
+        `infer_stream`: stream_sample_rate= / stream_encoding= / stream_filter_width=, one format per call."""
         self._refuse_stream_output(repetition.pop("sample_rate", None), repetition.pop("encoding", None), "infer_stream_batch")
+        fmt = self._resolve_stream_output(repetition.pop("stream_sample_rate", None), repetition.pop("stream_encoding", None),
+                                          repetition.pop("stream_filter_width", None))
         samp = self._resolve_sampling(len(texts), temperature, top_k, top_p, min_p, repetition)
         if not isinstance(ref_texts, (list, tuple)):
             ref_texts = [ref_texts] * len(texts)
@@ -511,7 +531,7 @@ class NeuTTS:
         if len(texts) > cap:
             raise ValueError(f"{len(texts)} utterances exceed the engine's {cap} decode slots")
         prompts = [self._apply_chat_template(rc, rt, t) for rc, rt, t in zip(ref_codes, ref_texts, texts)]
-        return self._infer_stream_batch_hip(prompts, [[int(c) for c in _to_list(rc)] for rc in ref_codes], samp)
+        return self._infer_stream_batch_hip(prompts, [[int(c) for c in _to_list(rc)] for rc in ref_codes], samp, fmt)
 
     def score(self, text: str, codes, ref_codes, ref_text: str, include_eos: bool = True) -> Dict[str, object]:
         """Teacher-forced score of an EXISTING utterance: the model's log-probability of every speech token of `codes` (and, with include_eos, of
@@ -754,7 +774,39 @@ class NeuTTS:
             else:
                 what = f"encoding={out[1]!r}" if encoding is not None else f"output_encoding={out[1]!r}"
             raise ValueError(f"{who} yields 24 kHz float32 chunks only (got {what}): resampling a stream needs filter history across chunk "
-                             "edges; use infer / infer_batch for another output format, or convert the finished stream")
+                             "edges; use infer / infer_batch for another output format, or convert the finished stream.  The chunks' own "
+                             "format is set by stream_sample_rate= / stream_encoding= / stream_filter_width=, which keep that history on the device")
+
+    def _resolve_stream_output(self, sample_rate=None, encoding=None, filter_width=None):
+        """Per-call chunk format of the stream entry points: None = the instance's stream_* attribute (stream_filter_width None = output_filter_width).
+        -> None for 24 kHz float32 (the calls of an instance without the stage), else the checked (sample_rate, encoding, filter_width)."""
+        rate = self.stream_sample_rate if sample_rate is None else sample_rate
+        enc = self.stream_encoding if encoding is None else encoding
+        width = filter_width if filter_width is not None else (self.stream_filter_width if self.stream_filter_width is not None else self.output_filter_width)
+        _check_output(rate, enc, width, "stream_")
+        return None if (int(rate) == self.sample_rate and enc == "f32") else (int(rate), enc, int(width))
+
+    @staticmethod
+    def _format_chunks(conv, blended):
+        """[(utterance, 24 kHz float32 chunk, last)] in order -> [(utterance, formatted chunk)]: one WavStream push per run of distinct utterances
+        (a regular and a final window of one utterance in the same round are two chunks of its signal, in that order)."""
+        out = []
+        k0 = 0
+        while k0 < len(blended):
+            k1, seen = k0, set()
+            while k1 < len(blended) and blended[k1][0] not in seen:
+                seen.add(blended[k1][0])
+                k1 += 1
+            run = blended[k0:k1]
+            outs = conv.push([b[1] for b in run], [b[0] for b in run], [b[2] for b in run])
+            out += [(b[0], np.array(o)) for b, o in zip(run, outs)]
+            k0 = k1
+        return out
+
+    def _stream_converter(self, n: int, fmt):
+        """The chunked output stage for the host loops' blended chunks (a WavStream of n rows); the longest chunk is a final window's frame."""
+        longest = (self.streaming_frames_per_chunk + self.streaming_lookforward + 2 * self.streaming_overlap_frames) * self.hop_length
+        return self.codec.engine.stream_converter(n, fmt[0], fmt[1], fmt[2], max_chunk_samples=longest)
 
     def _decode_formatted(self, codes: Sequence[Sequence[int]], out) -> List[np.ndarray]:
         """One codec pass with the device output stage behind it.  A watermarker is a host library that works on the 24 kHz float waveform: with
@@ -812,11 +864,17 @@ class NeuTTS:
         return ids[:j] + [speech_gen_start] + list(codes)
 
     # ------------------------------------------------------------------------------------------ streaming
-    def _infer_stream_hip(self, prompt_ids: List[int], ref_codes: List[int], samp: Optional[Sequence[tuple]] = None) -> Generator[np.ndarray, None, None]:
+    def _infer_stream_hip(self, prompt_ids: List[int], ref_codes: List[int], samp: Optional[Sequence[tuple]] = None,
+                          fmt=_INSTANCE_FORMAT) -> Generator[np.ndarray, None, None]:
         """Window / cross-fade semantics of ref:neutts/neutts.py:401-465 (Appendix C of SURVEY.md), token by token.
         The backbone and the codec are separate engines on separate HIP streams: the next `chunk` decode steps are
         enqueued (asynchronously) BEFORE the codec pass of the chunk that just became decodable, so the codec runs
-        beside the backbone instead of between its bursts; the host only blocks in `read()`."""
+        beside the backbone instead of between its bursts; the host only blocks in `read()`.  With a chunk format (`fmt`) every blended chunk
+        goes through the chunked output stage (a WavStream of one row) behind the cross-fade; a watermarker still sees 24 kHz float32 windows."""
+        if fmt is _INSTANCE_FORMAT:
+            fmt = self._resolve_stream_output()
+        conv = self._stream_converter(1, fmt) if fmt is not None else None
+        emit = (lambda x, last=False: x) if conv is None else (lambda x, last=False: conv.push([x], last=last)[0])
         eng = self.backbone
         self._seed += 1
         slot = eng.acquire_slot()         # from the engine's pool: a stream that is still open never shares its slot
@@ -854,7 +912,7 @@ class NeuTTS:
                         if self.watermarker is not None:
                             recon = self.watermarker.apply_watermark(recon, sample_rate=24_000)
                         n_decoded_tokens += chunk
-                        yield blend.push(np.array(recon[s0:s1]))
+                        yield emit(blend.push(np.array(recon[s0:s1])))
                 if not finished and not self.streaming_overlap_compute:
                     eng.decode(chunk)                     # serial variant (A/B aid): backbone waits for the codec
             remaining = len(token_cache) - n_decoded_tokens
@@ -864,10 +922,14 @@ class NeuTTS:
                 recon = self.codec.engine.decode([token_cache[t0:]])[0]
                 if self.watermarker is not None:
                     recon = self.watermarker.apply_watermark(recon, sample_rate=24_000)
-                yield blend.push(np.array(recon[s0:]), last=True)
+                yield emit(blend.push(np.array(recon[s0:]), last=True), last=True)
+            elif conv is not None and blend.prev is not None:        # the tokens ended on a window's edge (lookforward 0 only): what the stage holds back
+                yield emit(np.zeros(0, dtype=np.float32), last=True)
         finally:
             eng.sync()
             eng.release(slot)
+            if conv is not None:
+                conv.close()
 
 
     # ---- device-side streaming (csrc/stream.cpp, ABI 6)
@@ -882,7 +944,7 @@ class NeuTTS:
             return False                   # (ntts_streams_create refuses these; the host loop slices like the reference does)
         return min(len(rc) for rc in ref_codes) >= self.streaming_overlap_frames
 
-    def _stream_batch_device(self, slots, ref_codes):
+    def _stream_batch_device(self, slots, ref_codes, fmt=None):
         """The loop of _infer_stream_batch_hip with the token caches, the window assembly, the 27-frame slice and the cross-fade on the
         device (ntts_streams_*): per burst the host waits for a snapshot of 2 n integers, enqueues the next burst, and receives each
         stream's new samples.  Same windows, same arithmetic (kernels/stream.h restates numpy's operations one by one): the chunks are
@@ -891,7 +953,7 @@ class NeuTTS:
         chunk, look_f = self.streaming_frames_per_chunk, self.streaming_lookforward
         mod = int(getattr(self, "_stream_modulo", 0))
         ss = _hip.StreamSet(eng, self.codec.engine, slots, ref_codes, int(eng.cfg["max_context"]), chunk, look_f, self.streaming_lookback,
-                            self.streaming_overlap_frames, self.hop_length, 0 if mod else int(self._speech_base), mod or 65536, bool(mod))
+                            self.streaming_overlap_frames, self.hop_length, 0 if mod else int(self._speech_base), mod or 65536, bool(mod), fmt=fmt)
         try:
             # the first window is complete once chunk + lookforward tokens exist (ref :401-404) and the prompt pass produced one of them
             steps = chunk + look_f - 1
@@ -933,7 +995,7 @@ class NeuTTS:
             self._gang_codec0_lent = True
         return self._gang_codecs
 
-    def _infer_stream_batch_gang(self, prompts: List[List[int]], ref_codes: List[List[int]], samp: Optional[Sequence[tuple]] = None):
+    def _infer_stream_batch_gang(self, prompts: List[List[int]], ref_codes: List[List[int]], samp: Optional[Sequence[tuple]] = None, fmt=None):
         """infer_stream_batch over an ENGINE GANG (BASELINE configs[4]'s literal shape: ref:neutts/neutts.py:373-465
         for many utterances at once).  The utterances are dealt out in admission groups over the gang's engines; every group is a
         device-side stream set (ntts_streams_*) on its engine, the engine's codec engine on the same lane.  Per turn of an engine:
@@ -1011,7 +1073,7 @@ class NeuTTS:
                             i0 = i1
                         item[0] = _hip.StreamSet(eng, codecs[k], slots, [ref_codes[i] for i in idx], int(eng.cfg["max_context"]), chunk, look_f,
                                                  self.streaming_lookback, self.streaming_overlap_frames, self.hop_length,
-                                                 0 if mod else int(self._speech_base), mod or 65536, bool(mod))
+                                                 0 if mod else int(self._speech_base), mod or 65536, bool(mod), fmt=fmt)
                         admitted = True
                         running += len(idx)
                     if running:
@@ -1043,13 +1105,17 @@ class NeuTTS:
                             except _hip.NeuTTSHipError:
                                 pass
 
-    def _infer_stream_batch_hip(self, prompts: List[List[int]], ref_codes: List[List[int]], samp: Optional[Sequence[tuple]] = None):
+    def _infer_stream_batch_hip(self, prompts: List[List[int]], ref_codes: List[List[int]], samp: Optional[Sequence[tuple]] = None,
+                                fmt=_INSTANCE_FORMAT):
+        # fmt: the chunks' format -- None = 24 kHz float32, (sample_rate, encoding, filter_width), or (the default) the instance's stream_* attributes
+        if fmt is _INSTANCE_FORMAT:
+            fmt = self._resolve_stream_output()
         # (stream_on_gang: off unless the caller sets it -- it pays for one of the two models measured.  512 streams of the fp8 Nano-sized model
         #  over four 128-slot engines, one admission group per engine: 150.2 k codec-tokens/s and first audio 152 / 168 / 186 ms against 144.2 k /
         #  182 ms on ONE 512-slot engine; NeuTTS-Air bf16: 256 streams over 4 x 64 slots 80.3 k against 100.5 k on one engine, 512 streams over
         #  4 x 128 111.9 k against 114.9 k -- four chains stream Air's larger weights four times; profiles/r05o_sweep_stream_gang*.txt)
         if (self.gang is not None and len(prompts) > 1 and getattr(self, "stream_on_gang", False) and self._stream_on_device(ref_codes)):
-            yield from self._infer_stream_batch_gang(prompts, ref_codes, samp)
+            yield from self._infer_stream_batch_gang(prompts, ref_codes, samp, fmt)
             return
         eng = self.backbone
         n = len(prompts)
@@ -1077,7 +1143,7 @@ class NeuTTS:
                                       self.streaming_lookback, self.streaming_overlap_frames)
         if self._stream_on_device(ref_codes):
             try:
-                yield from self._stream_batch_device(slots, ref_codes)
+                yield from self._stream_batch_device(slots, ref_codes, fmt)
             finally:
                 eng.sync()
                 for s in slots:
@@ -1096,7 +1162,10 @@ class NeuTTS:
         blend = [_StreamBlender(stride) for _ in range(n)]
         done = [False] * n                                # final chunk emitted
         need = chunk + look_f                             # undecoded tokens that make a window decodable (ref :401-404)
+        conv = None
         try:
+            if fmt is not None:                           # the chunked output stage behind the cross-fade: one row per utterance
+                conv = self._stream_converter(n, fmt)
             while not all(done):
                 ids_all, n_new_all, fin_all = eng.read_all_array()    # blocks until the bursts enqueued so far are done
                 ids, n_new, fin = ids_all[slots], n_new_all[slots], fin_all[slots]     # row i = utterance i
@@ -1104,6 +1173,7 @@ class NeuTTS:
                 if running and self.streaming_overlap_compute:
                     eng.decode(chunk)                     # async: runs beside the codec pass below
                 jobs = []                                 # (utterance, window codes, s0, s1 or None, last)
+                flush = []                                # formatted utterances that end without a final window
                 for i in range(n):
                     if done[i]:
                         continue
@@ -1127,6 +1197,8 @@ class NeuTTS:
                             t0 = max(int(clen[i]) - (look_b + ovl + remaining), 0)
                             s0 = (int(clen[i]) - t0 - remaining - ovl) * hop
                             jobs.append((i, cache[i, t0:clen[i]], s0, None, True))
+                        elif conv is not None and (blend[i].prev is not None or any(j[0] == i for j in jobs)):
+                            flush.append(i)               # (the tokens ended on a window's edge: lookforward 0 only)
                         done[i] = True
                 if jobs:
                     wavs = self.codec.engine.decode([j[1] for j in jobs], reuse_output=True)     # one batched codec pass; views of the
@@ -1136,14 +1208,21 @@ class NeuTTS:
                             recon = self.watermarker.apply_watermark(recon, sample_rate=24_000)   # codec engine may overwrite that buffer
                         pieces.append((i, np.array(recon[s0:s1]), last))
                     del wavs
-                    for i, piece, last in pieces:
-                        yield i, blend[i].push(piece, last=last)
+                    if conv is None:
+                        for i, piece, last in pieces:
+                            yield i, blend[i].push(piece, last=last)
+                    else:                                  # blended on the host, then the chunked output stage
+                        yield from self._format_chunks(conv, [(i, blend[i].push(piece, last=last), last) for i, piece, last in pieces])
+                if flush:                                 # what the stage holds back of them: chunks of their own, behind the round's others
+                    yield from self._format_chunks(conv, [(i, np.zeros(0, dtype=np.float32), True) for i in flush])
                 if running and not self.streaming_overlap_compute:
                     eng.decode(chunk)
         finally:
             eng.sync()
             for s in slots:
                 eng.release(s)
+            if conv is not None:
+                conv.close()
 
 
 def _engine_config_from_hf(hc) -> Dict[str, object]:
