@@ -586,6 +586,13 @@ extern "C" int ntts_backbone_create(const ntts_backbone_config* c, int device, n
     CR_HIP(hipMalloc((void**)&e->attn_pf, T * c->num_heads * e->HD * 2));
     CR_HIP(hipMalloc((void**)&e->o_pf, T * H * 2));
     CR_HIP(hipMalloc((void**)&e->act_pf, T * F * 2));
+    // the prompt pass's meta block (prefill_impl has the layout), term by term:
+    //   2 T                             [ids][tok_seq]
+    //   B (19 + max_pages)              per prompt tok_base, seq_len, pos0, slot, last_row, the 8 sampler fields, mark_off (n + 1 entries) and 2 seed words
+    //                                   (16 n + 1), and [bt_rows]
+    //   (T / 64 + 3 B) 2                seq + q0 of the two-sweep tiles of every layer (at most T / 64 + n) and of the pruned last layer's three lists (n items)
+    //   6 B + 3 B max_pages             seq + q0 of the resident and deep work items: one per 256 positions of a tier, at most max_pages / 8 + 2 per prompt
+    //   64                              spare
     e->meta_cap = 2 * T + (size_t)B * (19 + e->max_pages) + (T / 64 + 3 * B) * 2 + 6 * (size_t)B + 3 * (size_t)B * e->max_pages + 64;
     CR_HIP(hipMalloc((void**)&e->meta_dev, e->meta_cap * sizeof(int)));
     for (int i = 0; i < ntts_backbone::kMetaStages; ++i) {
@@ -1596,24 +1603,17 @@ static void calib_tap(ntts_backbone* e, const bf16_t* x, long rows, int cols, in
 // (h_dec / xn_dec), a score call (score_rows != null) normalises the R scored source positions into rows 0 .. R - 1 of xn_pf.
 struct PromptPass {
     const int* md;                 // the meta block (its first Ti entries are the packed token ids)
-    PrefillMeta meta;              // with the two-sweep tile list of every layer
-    int Ti, n, n_tiles;
-    const int *rt_seq, *rt_q0, *dt_seq, *dt_q0;      // resident / deep work lists of every layer
-    int n_rt, n_dt;
-    bool prune;                    // last layer: attention, o_proj and the MLP on each prompt's last position alone, by the lists below
-    const int *lt_seq, *lt_q0, *lrt_seq, *lrt_q0, *ldt_seq, *ldt_q0;
-    int n_lt, n_lrt, n_ldt;
-    const int *last_row, *slot;    // [n] each prompt's last packed row and its decode slot
+    PrefillPass pf;                // attn_prefill.h: PrefillMeta, each prompt's last packed row, the work lists of every layer and of the pruned last one
+    int Ti, n;
+    bool prune;                    // last layer: attention, o_proj and the MLP on each prompt's last position alone
     const int* score_rows;         // [R] packed rows of the scored source positions, or null
     int R;
 };
 static void prompt_pass_layers(ntts_backbone* e, const PromptPass& P, hipStream_t st) {
     const ntts_backbone_config& c = e->cfg;
     const int H = e->H, F = e->F, QD = c.num_heads * e->HD, Ti = P.Ti, n = P.n;
-    const int* md = P.md;
-    const PrefillMeta& meta = P.meta;
     NormArgs n0{};
-    n0.gather_ids = md; n0.embed = e->embed; n0.resid_out = e->h_pf; n0.norm_w = e->layers[0].ln1; n0.normed_out = e->xn_pf;
+    n0.gather_ids = P.md; n0.embed = e->embed; n0.resid_out = e->h_pf; n0.norm_w = e->layers[0].ln1; n0.normed_out = e->xn_pf;
     n0.M = Ti; n0.H = H; n0.eps = c.rms_eps;
     if (e->fp8) n0.out_fp8_inv = 1.0f / e->layers[0].xs[0];
     add_rmsnorm_launch(n0, st);
@@ -1622,44 +1622,15 @@ static void prompt_pass_layers(ntts_backbone* e, const PromptPass& P, hipStream_
         const bool last = i + 1 == c.num_layers;
         calib_tap(e, e->xn_pf, Ti, H, 4 * i, st);
         gemm_large<EPI_BF16>(e, gemm_args(e, e->xn_pf, H, w.wqkv, H, w.bqkv, e->qkv_pf, e->NQKV, Ti, e->NQKV, H, w.sqkv, w.xs[0]), st);
-        RopeWriteArgs r{};
-        r.qkv = e->qkv_pf; r.ld_qkv = e->NQKV; r.kpool = e->kv + (size_t)i * e->layer_stride; r.vpool = r.kpool + e->kv_half;
-        r.block_table = e->block_table; r.max_pages = e->max_pages; r.meta = meta; r.rope_cos = e->rope_cos; r.rope_sin = e->rope_sin;
-        r.nh = c.num_heads; r.nkv = c.num_kv_heads; r.T = Ti;
-        // the q heads are rotated by the attention kernel as it loads them (one read + one write of T x 896 values less per layer:
-        // prompt pass 28.16 -> 27.94 ms per chunk, profiles/r02k_sweep_pf_rope_q_fused.log); this kernel rotates k and scatters v
-        r.skip_q = 1;
-        if (e->generic) {   // head_dim 128 and / or qk-norm: q AND k normalised + rotated here (q in place), v scattered (attn_prefill.h)
-            RopeNormArgs g{};
-            g.qkv = e->qkv_pf; g.ld_qkv = e->NQKV; g.kpool = r.kpool; g.vpool = r.vpool; g.block_table = e->block_table; g.max_pages = e->max_pages;
-            g.meta = meta; g.rope_cos = e->rope_cos; g.rope_sin = e->rope_sin; g.q_norm = w.qn; g.k_norm = w.kn; g.eps = c.rms_eps;
-            g.nh = c.num_heads; g.nkv = c.num_kv_heads; g.rows = Ti; g.write_v = 1;
-            const long items = (long)Ti * (c.num_heads + 2 * c.num_kv_heads);
-            if (e->HD == 128) NTTS_LAUNCH((rope_norm_kv_write_kernel<128>), dim3((unsigned)((items + 3) / 4)), dim3(256), st, g);
-            else NTTS_LAUNCH((rope_norm_kv_write_kernel<64>), dim3((unsigned)((items + 3) / 4)), dim3(256), st, g);
-        } else
-        NTTS_LAUNCH((rope_kv_write_vec_kernel), dim3((Ti + kRopeTokPerBlock - 1) / kRopeTokPerBlock), dim3(256), st, r);
-        AttnPrefillArgs a{};
-        a.qkv = e->qkv_pf; a.ld_qkv = e->NQKV; a.out = e->attn_pf; a.ld_out = QD; a.kpool = r.kpool; a.vpool = r.vpool;
-        a.block_table = e->block_table; a.max_pages = e->max_pages; a.meta = meta; a.nh = c.num_heads; a.nkv = c.num_kv_heads;
-        if (e->fp8) a.out_fp8_inv = 1.0f / w.xs[1];     // attn_pf rows hold QD e4m3 BYTES (ld_out counts bytes then)
-        a.rope_cos = e->rope_cos; a.rope_sin = e->rope_sin;
-        if (e->generic) a.rope_cos = a.rope_sin = nullptr;   // (q is already normalised and rotated)
-        // Last layer: the KV pages are complete after the rope/KV-write above, and nothing but each prompt's LAST position
+        // Last layer: the KV pages are complete after the rope/KV-write, and nothing but each prompt's LAST position
         // is read afterwards (it alone feeds the lm_head).  Attention runs on the one query tile per prompt that holds
         // it, then that row and its residual row are compacted and o_proj / the MLP run on n rows instead of T.
         // Row-wise results are unchanged (every GEMM / norm row is computed from that row's operands alone).
         const bool prune = last && P.prune;
-        int n_tiles = P.n_tiles, n_rtiles = P.n_rt;
-        if (prune) { a.meta.tile_seq = P.lt_seq; a.meta.tile_q0 = P.lt_q0; n_tiles = P.n_lt; }
-        if (n_tiles) { if (e->HD == 128) attn_prefill_launch_hd128(a, n_tiles, st); else attn_prefill_launch(a, n_tiles, st); }
-        a.meta.tile_seq = P.rt_seq; a.meta.tile_q0 = P.rt_q0;
-        if (prune) { a.meta.tile_seq = P.lrt_seq; a.meta.tile_q0 = P.lrt_q0; n_rtiles = P.n_lrt; }
-        if (n_rtiles) attn_prefill_res_launch(a, n_rtiles, e->pf_res_cap, prune, st);
-        int n_dtiles = P.n_dt;
-        a.meta.tile_seq = P.dt_seq; a.meta.tile_q0 = P.dt_q0;
-        if (prune) { a.meta.tile_seq = P.ldt_seq; a.meta.tile_q0 = P.ldt_q0; n_dtiles = P.n_ldt; }
-        if (n_dtiles) attn_prefill_deep_launch(a, n_dtiles, e->pf_res_cap, e->pf_deep_cap, prune, st);
+        bf16_t* kpool = e->kv + (size_t)i * e->layer_stride;
+        prefill_attn_layer(e->qkv_pf, e->NQKV, e->attn_pf, QD, e->fp8 ? 1.0f / w.xs[1] : 0.f, kpool, kpool + e->kv_half, e->block_table, e->max_pages,
+                           P.pf, c.num_heads, c.num_kv_heads, e->HD, e->rope_cos, e->rope_sin, w.qn, w.kn, c.rms_eps, e->generic, Ti,
+                           e->pf_res_cap, e->pf_deep_cap, prune, st);
         const int Mi = prune ? n : Ti;                       // rows from here on
         const bf16_t* attn_in = e->attn_pf;
         bf16_t* hres = e->h_pf;
@@ -1667,8 +1638,8 @@ static void prompt_pass_layers(ntts_backbone* e, const PromptPass& P, hipStream_
             bf16_t* attn_c = e->qkv_pf;
             bf16_t* h_c = e->qkv_pf + (size_t)n * QD;
             const int qe = e->fp8 ? QD / 2 : QD;   // attention rows in bf16 units (fp8: QD bytes)
-            NTTS_LAUNCH((gather_rows_kernel), dim3(n), dim3(256), st, (const bf16_t*)e->attn_pf, (long)qe, P.last_row, attn_c, (long)qe, qe);
-            NTTS_LAUNCH((gather_rows_kernel), dim3(n), dim3(256), st, (const bf16_t*)e->h_pf, (long)H, P.last_row, h_c, (long)H, H);
+            NTTS_LAUNCH((gather_rows_kernel), dim3(n), dim3(256), st, (const bf16_t*)e->attn_pf, (long)qe, P.pf.last_row, attn_c, (long)qe, qe);
+            NTTS_LAUNCH((gather_rows_kernel), dim3(n), dim3(256), st, (const bf16_t*)e->h_pf, (long)H, P.pf.last_row, h_c, (long)H, H);
             attn_in = attn_c;
             hres = h_c;
         }
@@ -1708,11 +1679,22 @@ static void prompt_pass_layers(ntts_backbone* e, const PromptPass& P, hipStream_
             if (e->fp8) n2.out_fp8_inv = 1.0f / e->xs_head;
         } else {  // only each prompt's last position feeds the lm_head: gather it into its decode-slot row
             n2.resid_out = e->h_dec; n2.norm_w = e->final_norm; n2.normed_out = e->xn_dec; n2.M = n;
-            n2.in_rows = prune ? nullptr : P.last_row; n2.out_rows = P.slot;
+            n2.in_rows = prune ? nullptr : P.pf.last_row; n2.out_rows = P.pf.meta.slot;
             if (e->fp8) n2.out_fp8_inv = 1.0f / e->xs_head;
         }
         add_rmsnorm_launch(n2, st);
     }
+}
+
+static int bits(float f) { int b; memcpy(&b, &f, 4); return b; }   // a float field of the (int) meta block
+// [bt_rows n * max_pages] of a meta block: the pages of each sequence's slot, the unused entries 0; returns where the rows start
+static size_t put_bt_rows(const ntts_backbone* e, int n, const int32_t* slots, std::vector<int>& m) {
+    const size_t at = m.size();
+    for (int i = 0; i < n; ++i) {
+        const HostSlot& s = e->slots[slots[i]];
+        for (int k = 0; k < e->max_pages; ++k) m.push_back(k < (int)s.pages.size() ? s.pages[k] : 0);
+    }
+    return at;
 }
 
 // Prompt pass.  With donor_slot / shared_len (ntts_backbone_prefill_shared): prompt i re-uses the KV pages that hold the
@@ -1794,33 +1776,24 @@ static int prefill_impl(ntts_backbone* e, int32_t n, const int32_t* ids, const i
             return fail(e, NTTS_ENOMEM, "KV page pool exhausted (%d pages)", e->num_pages);
         }
     }
-    // ---- meta block: [ids T][tok_seq T][tok_base n][seq_len n][slot n][min_new n][max_len n][eos n][last_row n]
-    //                  [tile_seq nt][tile_q0 nt][bt_rows n*max_pages]
-    // (the attention work lists -- three tiers by position, deepest first, and the last layer's -- are built by attn_prefill.h prefill_work_lists)
-    const PrefillWorkLists wl = prefill_work_lists(n, lens, pos0.data(), e->pf_res_cap, e->pf_deep_cap);
-    const std::vector<int>&tile_seq = wl.tile_seq, &tile_q0 = wl.tile_q0, &rtile_seq = wl.rtile_seq, &rtile_q0 = wl.rtile_q0, &dtile_seq = wl.dtile_seq, &dtile_q0 = wl.dtile_q0;
+    // ---- meta block, in this order:
+    //   [ids T]                                                       the packed token ids: new tokens only (first: NormArgs::gather_ids reads md + 0)
+    //   [tok_seq T][tok_base n][seq_len n][pos0 n][slot n][last_row n][the work lists of every layer and of the pruned last one]
+    //                                                                 attn_prefill.h prefill_pack (three tiers by position, deepest first)
+    //   [min_new n][max_len n][eos n][top_k n][temperature n][top_p n][min_p n][penalty n]     (floats as their bits)
+    //   [mark_off n + 1][seed 2 n][bt_rows n * max_pages]
     std::vector<int> m;
     m.reserve(2 * T + 16 * n);
-    for (int i = 0; i < n; ++i) m.insert(m.end(), ids + id_off[i] + pos0[i], ids + id_off[i] + lens[i]);   // packed: new tokens only
-    const size_t o_tok_seq = m.size();
-    m.insert(m.end(), wl.tok_seq.begin(), wl.tok_seq.end());
-    const size_t o_base = m.size();
-    m.insert(m.end(), wl.tok_base.begin(), wl.tok_base.end());
-    const size_t o_len = m.size();   m.insert(m.end(), lens, lens + n);
-    const size_t o_pos0 = m.size();  m.insert(m.end(), pos0.begin(), pos0.end());
-    const size_t o_slot = m.size();  m.insert(m.end(), slots, slots + n);
+    for (int i = 0; i < n; ++i) m.insert(m.end(), ids + id_off[i] + pos0[i], ids + id_off[i] + lens[i]);
+    const PrefillPacked packed = prefill_pack(prefill_work_lists(n, lens, pos0.data(), e->pf_res_cap, e->pf_deep_cap), n, lens, pos0.data(), slots, m);
     const size_t o_min = m.size();   for (int i = 0; i < n; ++i) m.push_back(samp[i].min_new_tokens);
     const size_t o_max = m.size();   for (int i = 0; i < n; ++i) m.push_back(samp[i].max_length);
     const size_t o_eos = m.size();   for (int i = 0; i < n; ++i) m.push_back(samp[i].eos_token_id);
     const size_t o_topk = m.size();  for (int i = 0; i < n; ++i) m.push_back(samp[i].do_sample ? samp[i].top_k : 0);
-    const size_t o_temp = m.size();
-    for (int i = 0; i < n; ++i) { int b; const float t = samp[i].do_sample ? samp[i].temperature : 1.0f; memcpy(&b, &t, 4); m.push_back(b); }
-    const size_t o_topp = m.size();
-    for (int i = 0; i < n; ++i) { int b; const float t = samp[i].do_sample ? samp[i].top_p : 1.0f; memcpy(&b, &t, 4); m.push_back(b); }
-    const size_t o_minp = m.size();
-    for (int i = 0; i < n; ++i) { int b; const float t = samp[i].do_sample ? samp[i].min_p : 0.0f; memcpy(&b, &t, 4); m.push_back(b); }
-    const size_t o_pen = m.size();
-    for (int i = 0; i < n; ++i) { int b; const float t = rep_penalty_of(samp[i]); memcpy(&b, &t, 4); m.push_back(b); }
+    const size_t o_temp = m.size();  for (int i = 0; i < n; ++i) m.push_back(bits(samp[i].do_sample ? samp[i].temperature : 1.0f));
+    const size_t o_topp = m.size();  for (int i = 0; i < n; ++i) m.push_back(bits(samp[i].do_sample ? samp[i].top_p : 1.0f));
+    const size_t o_minp = m.size();  for (int i = 0; i < n; ++i) m.push_back(bits(samp[i].do_sample ? samp[i].min_p : 0.0f));
+    const size_t o_pen = m.size();   for (int i = 0; i < n; ++i) m.push_back(bits(rep_penalty_of(samp[i])));
     // the lm_head columns every penalised request's prompt marks in its bitmap row: ids[prompt_ignore_length ..] of the FULL prompt (a shared prefix
     // counts like any other token), mapped to columns -- with a restricted head [range | EOS], ids it does not have are dropped
     std::vector<int> mark_cols;
@@ -1840,25 +1813,7 @@ static int prefill_impl(ntts_backbone* e, int32_t n, const int32_t* ids, const i
     m.push_back((int)mark_cols.size());
     const size_t o_seed = m.size();
     for (int i = 0; i < n; ++i) { m.push_back((int)(uint32_t)samp[i].seed); m.push_back((int)(uint32_t)(samp[i].seed >> 32)); }
-    const size_t o_last = m.size();  m.insert(m.end(), wl.last_row.begin(), wl.last_row.end());
-    const size_t o_tseq = m.size();  m.insert(m.end(), tile_seq.begin(), tile_seq.end());
-    const size_t o_tq0 = m.size();   m.insert(m.end(), tile_q0.begin(), tile_q0.end());
-    const size_t o_rtseq = m.size(); m.insert(m.end(), rtile_seq.begin(), rtile_seq.end());
-    const size_t o_rtq0 = m.size();  m.insert(m.end(), rtile_q0.begin(), rtile_q0.end());
-    const size_t o_dtseq = m.size(); m.insert(m.end(), dtile_seq.begin(), dtile_seq.end());
-    const size_t o_dtq0 = m.size();  m.insert(m.end(), dtile_q0.begin(), dtile_q0.end());
-    const std::vector<int>&lt_seq = wl.lt_seq, &lt_q0 = wl.lt_q0, &lrt_seq = wl.lrt_seq, &lrt_q0 = wl.lrt_q0, &ldt_seq = wl.ldt_seq, &ldt_q0 = wl.ldt_q0;
-    const size_t o_ltseq = m.size();  m.insert(m.end(), lt_seq.begin(), lt_seq.end());
-    const size_t o_ltq0 = m.size();   m.insert(m.end(), lt_q0.begin(), lt_q0.end());
-    const size_t o_lrtseq = m.size(); m.insert(m.end(), lrt_seq.begin(), lrt_seq.end());
-    const size_t o_lrtq0 = m.size();  m.insert(m.end(), lrt_q0.begin(), lrt_q0.end());
-    const size_t o_ldtseq = m.size(); m.insert(m.end(), ldt_seq.begin(), ldt_seq.end());
-    const size_t o_ldtq0 = m.size();  m.insert(m.end(), ldt_q0.begin(), ldt_q0.end());
-    const size_t o_bt = m.size();
-    for (int i = 0; i < n; ++i) {
-        const HostSlot& s = e->slots[slots[i]];
-        for (int k = 0; k < e->max_pages; ++k) m.push_back(k < (int)s.pages.size() ? s.pages[k] : 0);
-    }
+    const size_t o_bt = put_bt_rows(e, n, slots, m);
     if (m.size() > e->meta_cap) {
         for (int i = 0; i < n; ++i) drop_pages(e, e->slots[slots[i]]);
         return fail(e, NTTS_EINVAL, "prefill meta block too large");
@@ -1921,11 +1876,11 @@ static int prefill_impl(ntts_backbone* e, int32_t n, const int32_t* ids, const i
     hipStream_t st = e->stream;
     HIPCHK(e, upload_meta(e, m.data(), m.size(), st));
     const int* md = e->meta_dev;
-    PrefillMeta meta{md + o_base, md + o_len, md + o_pos0, md + o_slot, md + o_tok_seq, md + o_tseq, md + o_tq0};
+    const PrefillPass pf = packed.bind(md);
 
     HIPCHK(e, hipEventRecord(e->ev[0], st));
     PrefillInit pi{};
-    pi.slot = md + o_slot; pi.seq_len = md + o_len; pi.min_new = md + o_min; pi.max_len = md + o_max; pi.eos = md + o_eos;
+    pi.slot = pf.meta.slot; pi.seq_len = pf.meta.seq_len; pi.min_new = md + o_min; pi.max_len = md + o_max; pi.eos = md + o_eos;
     pi.top_k = md + o_topk; pi.temp_bits = md + o_temp; pi.top_p_bits = md + o_topp; pi.min_p_bits = md + o_minp; pi.pen_bits = md + o_pen; pi.seed = md + o_seed;
     pi.seen = e->seen; pi.seen_pitch = e->seen_pitch;
     pi.bt_rows = md + o_bt; pi.block_table = e->block_table; pi.max_pages = e->max_pages; pi.n = n; pi.sl = e->sl;
@@ -1938,26 +1893,19 @@ static int prefill_impl(ntts_backbone* e, int32_t n, const int32_t* ids, const i
             HIPCHK(e, hipEventRecord(e->seen_ev, st));
             e->seen_ev_used = true;
         }
-        SeenMarkArgs sm{md + o_slot, md + o_moff, e->seen_cols, e->seen, e->seen_pitch};
+        SeenMarkArgs sm{pf.meta.slot, md + o_moff, e->seen_cols, e->seen, e->seen_pitch};
         NTTS_LAUNCH((seen_mark_prompt_kernel), dim3(n), dim3(256), st, sm);
     }
 
     const int Ti = (int)T;
     PromptPass pp{};
-    pp.md = md; pp.meta = meta; pp.Ti = Ti; pp.n = n;
-    pp.n_tiles = (int)tile_seq.size();
-    pp.rt_seq = md + o_rtseq; pp.rt_q0 = md + o_rtq0; pp.n_rt = (int)rtile_seq.size();
-    pp.dt_seq = md + o_dtseq; pp.dt_q0 = md + o_dtq0; pp.n_dt = (int)dtile_seq.size();
-    pp.lt_seq = md + o_ltseq; pp.lt_q0 = md + o_ltq0; pp.n_lt = (int)lt_seq.size();
-    pp.lrt_seq = md + o_lrtseq; pp.lrt_q0 = md + o_lrtq0; pp.n_lrt = (int)lrt_seq.size();
-    pp.ldt_seq = md + o_ldtseq; pp.ldt_q0 = md + o_ldtq0; pp.n_ldt = (int)ldt_seq.size();
-    pp.last_row = md + o_last; pp.slot = md + o_slot;
+    pp.md = md; pp.pf = pf; pp.Ti = Ti; pp.n = n;
     pp.prune = T >= 4L * n && !e->calib;    // (calibration mode looks at EVERY position's GEMM inputs, the last layer's included)
     prompt_pass_layers(e, pp, st);
     if (e->calib) {        // the lm_head's input: the final norm of EVERY position (the decode steps feed the head one row per step and
         NormArgs nc{};     // sequence -- a record of the prompts' last positions only would be 64 rows for 64 calibration prompts); scratch output
         nc.o_bf16 = e->h_pf; nc.norm_w = e->final_norm;   // (no pruning in calibration mode: h_pf holds every row)
-        nc.norm_w = e->final_norm; nc.normed_out = e->xn_pf; nc.M = Ti; nc.H = H; nc.eps = c.rms_eps;
+        nc.normed_out = e->xn_pf; nc.M = Ti; nc.H = H; nc.eps = c.rms_eps;
         add_rmsnorm_launch(nc, st);
         calib_tap(e, e->xn_pf, Ti, H, 4 * c.num_layers, st);
     }
@@ -2080,29 +2028,15 @@ extern "C" int ntts_backbone_score(ntts_backbone* e, int32_t n, const int32_t* i
     } pages{e, slots, n};
     for (int i = 0; i < n; ++i)
         if (alloc_pages(e, e->slots[slots[i]], lens[i]) != NTTS_OK) return fail(e, NTTS_ENOMEM, "KV page pool exhausted (%d pages)", e->num_pages);
-    // ---- meta block: [ids T][tok_seq T][tok_base n][seq_len n][pos0 n][slot n][tile lists][bt_rows n*max_pages]; the scored rows and their targets
-    //      go to sc_rows (2 T more ints would not fit the prompt pass's block)
+    // ---- meta block: [ids T][attn_prefill.h prefill_pack's part][bt_rows n * max_pages] -- the prompt pass's block without the sampler fields, so it is
+    //      the shorter of the two for the same lengths (last_row and the last layer's lists, 3 n ints, ride along unread); the scored rows and their
+    //      targets go to sc_rows (2 T more ints would not fit the prompt pass's block)
     const std::vector<int> pos0(n, 0);
-    const PrefillWorkLists wl = prefill_work_lists(n, lens, pos0.data(), e->pf_res_cap, e->pf_deep_cap);
     std::vector<int> m;
     m.reserve(2 * T + 16 * n);
     m.insert(m.end(), ids, ids + T);
-    const size_t o_tok_seq = m.size(); m.insert(m.end(), wl.tok_seq.begin(), wl.tok_seq.end());
-    const size_t o_base = m.size();    m.insert(m.end(), wl.tok_base.begin(), wl.tok_base.end());
-    const size_t o_len = m.size();     m.insert(m.end(), lens, lens + n);
-    const size_t o_pos0 = m.size();    m.insert(m.end(), pos0.begin(), pos0.end());
-    const size_t o_slot = m.size();    m.insert(m.end(), slots, slots + n);
-    const size_t o_tseq = m.size();    m.insert(m.end(), wl.tile_seq.begin(), wl.tile_seq.end());
-    const size_t o_tq0 = m.size();     m.insert(m.end(), wl.tile_q0.begin(), wl.tile_q0.end());
-    const size_t o_rtseq = m.size();   m.insert(m.end(), wl.rtile_seq.begin(), wl.rtile_seq.end());
-    const size_t o_rtq0 = m.size();    m.insert(m.end(), wl.rtile_q0.begin(), wl.rtile_q0.end());
-    const size_t o_dtseq = m.size();   m.insert(m.end(), wl.dtile_seq.begin(), wl.dtile_seq.end());
-    const size_t o_dtq0 = m.size();    m.insert(m.end(), wl.dtile_q0.begin(), wl.dtile_q0.end());
-    const size_t o_bt = m.size();
-    for (int i = 0; i < n; ++i) {
-        const HostSlot& s = e->slots[slots[i]];
-        for (int k = 0; k < e->max_pages; ++k) m.push_back(k < (int)s.pages.size() ? s.pages[k] : 0);
-    }
+    const PrefillPacked packed = prefill_pack(prefill_work_lists(n, lens, pos0.data(), e->pf_res_cap, e->pf_deep_cap), n, lens, pos0.data(), slots, m);
+    const size_t o_bt = put_bt_rows(e, n, slots, m);
     if (m.size() > e->meta_cap) return fail(e, NTTS_EINVAL, "score meta block too large");
     std::vector<int> rows;                                   // [R] source rows, then [R] targets
     rows.reserve(2 * R);
@@ -2116,15 +2050,12 @@ extern "C" int ntts_backbone_score(ntts_backbone* e, int32_t n, const int32_t* i
     pages.queued = true;
     HIPCHK(e, upload_meta(e, m.data(), m.size(), st));
     const int* md = e->meta_dev;
-    PrefillMeta meta{md + o_base, md + o_len, md + o_pos0, md + o_slot, md + o_tok_seq, md + o_tseq, md + o_tq0};
-    NTTS_LAUNCH((score_block_table_kernel), dim3(n), dim3(64), st, md + o_slot, md + o_bt, e->block_table, e->max_pages);
+    const PrefillPass pf = packed.bind(md);
+    NTTS_LAUNCH((score_block_table_kernel), dim3(n), dim3(64), st, pf.meta.slot, md + o_bt, e->block_table, e->max_pages);
 
     // ---- the prompt pass over every position: no pruning of the last layer, no first token; the final norm on the scored source rows only
     PromptPass pp{};
-    pp.md = md; pp.meta = meta; pp.Ti = (int)T; pp.n = n;
-    pp.n_tiles = (int)wl.tile_seq.size();
-    pp.rt_seq = md + o_rtseq; pp.rt_q0 = md + o_rtq0; pp.n_rt = (int)wl.rtile_seq.size();
-    pp.dt_seq = md + o_dtseq; pp.dt_q0 = md + o_dtq0; pp.n_dt = (int)wl.dtile_seq.size();
+    pp.md = md; pp.pf = pf; pp.Ti = (int)T; pp.n = n;
     pp.score_rows = e->sc_rows; pp.R = (int)R;
     prompt_pass_layers(e, pp, st);
     // ---- lm_head + merge, chunk by chunk: partials of one chunk at a time, outputs of the whole call in sc_out
@@ -2301,41 +2232,50 @@ extern "C" int ntts_backbone_poll_end(ntts_backbone* e, int32_t* state, int32_t*
     return NTTS_OK;
 }
 
-extern "C" int ntts_backbone_read_finished(ntts_backbone* e, int32_t slot, int32_t* out_ids, int32_t cap, int32_t* n_out) {
-    if (!e || slot < 0 || slot >= e->cfg.max_batch || !n_out) return fail(e, NTTS_EINVAL, "bad argument");
-    const int B = e->cfg.max_batch;
-    // The snapshot entry speaks for the request that occupied the slot when poll_begin was enqueued: a release (+ a new prefill) since
-    // then -- before or after poll_end -- makes it stale, and the rows it points at are being overwritten by the new occupant
+// The two reads of a slot's record, shared by the ids (sl.out_tokens) and the log-probabilities (out_logprobs): `base` holds out_stride entries of
+// `elem` bytes per slot, the first n_new of them valid; at most `cap` are copied, *n_out = n_new either way.
+// Of a FINISHED slot, out of the last completed snapshot.  The snapshot entry speaks for the request that occupied the slot when poll_begin was
+// enqueued: a release (+ a new prefill) since then -- before or after poll_end -- makes it stale, and the rows it points at are being overwritten by
+// the new occupant
+static int read_finished_row(ntts_backbone* e, int slot, const void* base, size_t elem, void* out, int cap, int32_t* n_out) {
     if (!e->snap_valid || e->snap_host[slot] != SLOT_FINISHED || e->slots[slot].state == SLOT_FREE || e->snap_gen[slot] != e->slots[slot].gen)
         return fail(e, NTTS_ESTATE, "slot %d was not finished in the last completed snapshot (or was released / refilled since it was taken)", slot);
     HIPCHK(e, hipSetDevice(e->device));
-    // A finished slot's ids do not change until it is released, and the snapshot that showed it finished has completed: the
+    // A finished slot's record does not change until it is released, and the snapshot that showed it finished has completed: the
     // copy needs no ordering against the decode steps still queued on the engine's stream, so it goes around them
-    const int nn = e->snap_host[B + slot];
+    const int nn = e->snap_host[e->cfg.max_batch + slot];
     const int k = nn < cap ? nn : cap;
-    if (out_ids && k > 0) {
-        HIPCHK(e, hipMemcpyAsync(out_ids, e->sl.out_tokens + (size_t)slot * e->sl.out_stride, k * sizeof(int), hipMemcpyDeviceToHost, e->copy_stream));
+    if (out && k > 0) {
+        HIPCHK(e, hipMemcpyAsync(out, (const char*)base + (size_t)slot * e->sl.out_stride * elem, k * elem, hipMemcpyDeviceToHost, e->copy_stream));
         HIPCHK(e, hipStreamSynchronize(e->copy_stream));
     }
     *n_out = nn;
     return NTTS_OK;
 }
+// Of any slot, behind everything queued on the engine's stream (a free slot reads as empty); `finished` may be null
+static int read_row(ntts_backbone* e, int slot, const void* base, size_t elem, void* out, int cap, int32_t* n_out, int32_t* finished) {
+    HIPCHK(e, hipSetDevice(e->device));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    int st = 0, nn = 0;
+    if (finished) HIPCHK(e, hipMemcpy(&st, e->sl.state + slot, sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHK(e, hipMemcpy(&nn, e->sl.n_new + slot, sizeof(int), hipMemcpyDeviceToHost));
+    if (e->slots[slot].state == SLOT_FREE) { st = SLOT_FREE; nn = 0; }
+    const int k = nn < cap ? nn : cap;
+    if (out && k > 0) HIPCHK(e, hipMemcpy(out, (const char*)base + (size_t)slot * e->sl.out_stride * elem, k * elem, hipMemcpyDeviceToHost));
+    *n_out = nn;
+    if (finished) *finished = (st == SLOT_FINISHED) ? 1 : 0;
+    return NTTS_OK;
+}
+
+extern "C" int ntts_backbone_read_finished(ntts_backbone* e, int32_t slot, int32_t* out_ids, int32_t cap, int32_t* n_out) {
+    if (!e || slot < 0 || slot >= e->cfg.max_batch || !n_out) return fail(e, NTTS_EINVAL, "bad argument");
+    return read_finished_row(e, slot, e->sl.out_tokens, sizeof(int), out_ids, cap, n_out);
+}
 
 extern "C" int ntts_backbone_read(ntts_backbone* e, int32_t slot, int32_t* out_ids, int32_t cap, int32_t* n_out,
                                   int32_t* finished) {
     if (!e || slot < 0 || slot >= e->cfg.max_batch || !n_out) return fail(e, NTTS_EINVAL, "bad argument");
-    HIPCHK(e, hipSetDevice(e->device));
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-    int st = 0, nn = 0;
-    HIPCHK(e, hipMemcpy(&st, e->sl.state + slot, sizeof(int), hipMemcpyDeviceToHost));
-    HIPCHK(e, hipMemcpy(&nn, e->sl.n_new + slot, sizeof(int), hipMemcpyDeviceToHost));
-    if (e->slots[slot].state == SLOT_FREE) { st = SLOT_FREE; nn = 0; }
-    const int k = nn < cap ? nn : cap;
-    if (out_ids && k > 0)
-        HIPCHK(e, hipMemcpy(out_ids, e->sl.out_tokens + (size_t)slot * e->sl.out_stride, k * sizeof(int), hipMemcpyDeviceToHost));
-    *n_out = nn;
-    if (finished) *finished = (st == SLOT_FINISHED) ? 1 : 0;
-    return NTTS_OK;
+    return read_row(e, slot, e->sl.out_tokens, sizeof(int), out_ids, cap, n_out, finished);
 }
 
 // Per-token log-probabilities: the engine-level switch and the two reads (the twins of ntts_backbone_read / ntts_backbone_read_finished)
@@ -2369,34 +2309,13 @@ extern "C" int ntts_backbone_set_logprobs(ntts_backbone* e, int32_t enable) {
 extern "C" int ntts_backbone_read_logprobs(ntts_backbone* e, int32_t slot, float* out, int32_t cap, int32_t* n_out) {
     if (!e || slot < 0 || slot >= e->cfg.max_batch || !n_out) return fail(e, NTTS_EINVAL, "bad argument");
     if (!e->logprobs_on) return fail(e, NTTS_ESTATE, "log-probabilities are not recorded: call ntts_backbone_set_logprobs(e, 1) first");
-    HIPCHK(e, hipSetDevice(e->device));
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-    int nn = 0;
-    HIPCHK(e, hipMemcpy(&nn, e->sl.n_new + slot, sizeof(int), hipMemcpyDeviceToHost));
-    if (e->slots[slot].state == SLOT_FREE) nn = 0;
-    const int k = nn < cap ? nn : cap;
-    if (out && k > 0)
-        HIPCHK(e, hipMemcpy(out, e->out_logprobs + (size_t)slot * e->sl.out_stride, k * sizeof(float), hipMemcpyDeviceToHost));
-    *n_out = nn;
-    return NTTS_OK;
+    return read_row(e, slot, e->out_logprobs, sizeof(float), out, cap, n_out, nullptr);
 }
 
 extern "C" int ntts_backbone_read_finished_logprobs(ntts_backbone* e, int32_t slot, float* out, int32_t cap, int32_t* n_out) {
     if (!e || slot < 0 || slot >= e->cfg.max_batch || !n_out) return fail(e, NTTS_EINVAL, "bad argument");
     if (!e->logprobs_on) return fail(e, NTTS_ESTATE, "log-probabilities are not recorded: call ntts_backbone_set_logprobs(e, 1) first");
-    const int B = e->cfg.max_batch;
-    if (!e->snap_valid || e->snap_host[slot] != SLOT_FINISHED || e->slots[slot].state == SLOT_FREE || e->snap_gen[slot] != e->slots[slot].gen)
-        return fail(e, NTTS_ESTATE, "slot %d was not finished in the last completed snapshot (or was released / refilled since it was taken)", slot);
-    HIPCHK(e, hipSetDevice(e->device));
-    // (ntts_backbone_read_finished's rule: a finished slot's record does not change until the slot is released)
-    const int nn = e->snap_host[B + slot];
-    const int k = nn < cap ? nn : cap;
-    if (out && k > 0) {
-        HIPCHK(e, hipMemcpyAsync(out, e->out_logprobs + (size_t)slot * e->sl.out_stride, k * sizeof(float), hipMemcpyDeviceToHost, e->copy_stream));
-        HIPCHK(e, hipStreamSynchronize(e->copy_stream));
-    }
-    *n_out = nn;
-    return NTTS_OK;
+    return read_finished_row(e, slot, e->out_logprobs, sizeof(float), out, cap, n_out);
 }
 
 extern "C" int ntts_backbone_read_all(ntts_backbone* e, int32_t* out_ids, int32_t cap, int32_t* n_out, int32_t* finished) {

@@ -616,8 +616,9 @@ extern "C" int ntts_k_head_score_probe(const void* X_dev, const void* W_dev, int
 }
 
 // ---- attention probes: the decode launch of one form and one layer's prompt-pass attention (writer + the three tiers over the engine's own work
-//      lists) on caller-supplied pools and block tables, against tests/attention_spec.py.  Argument structs and launches only: the instantiations,
-//      grids and work lists are attn_decode.h's / attn_prefill.h's own (attn_decode_launch_form, prefill_work_lists), the ones the engine calls.
+//      lists) on caller-supplied pools and block tables, against tests/attention_spec.py.  Argument checks and one call each: the instantiations, grids,
+//      work lists, the meta block's packing and the launch sequence are attn_decode.h's / attn_prefill.h's own (attn_decode_launch_form,
+//      prefill_work_lists, prefill_pack, prefill_attn_layer), the ones the engine calls.
 extern "C" int ntts_k_attn_decode_form(int32_t batch, int32_t nkv, int32_t max_ctx, int32_t nt_pages, int32_t head_dim) {
     if (batch < 1 || nkv < 1 || max_ctx < 1 || (head_dim != 64 && head_dim != 128)) return NTTS_EINVAL;
     return attn_decode_form(batch, nkv, max_ctx, nt_pages, head_dim);
@@ -704,48 +705,14 @@ extern "C" int ntts_k_attn_prefill_probe(void* qkv_dev, int64_t ld_qkv, void* ou
     int cap = 0, dcap = 0;
     prefill_clamp_caps(res_cap, deep_cap, &cap, &dcap);
     if (generic) cap = dcap = 0;                                        // every query on the (head_dim-templated) two-sweep kernel
-    const PrefillWorkLists wl = prefill_work_lists(n, lens, pos0, cap, dcap);
-    std::vector<int> m;
-    auto put = [&](const std::vector<int>& v) { const size_t o = m.size(); m.insert(m.end(), v.begin(), v.end()); return o; };
-    const size_t o_tok_seq = put(wl.tok_seq), o_base = put(wl.tok_base), o_len = put(std::vector<int>(lens, lens + n)),
-                 o_pos0 = put(std::vector<int>(pos0, pos0 + n)), o_slot = put(std::vector<int>(slots, slots + n));
-    const bool prune = only_last != 0;
-    const size_t o_tseq = put(prune ? wl.lt_seq : wl.tile_seq), o_tq0 = put(prune ? wl.lt_q0 : wl.tile_q0);
-    const size_t o_rtseq = put(prune ? wl.lrt_seq : wl.rtile_seq), o_rtq0 = put(prune ? wl.lrt_q0 : wl.rtile_q0);
-    const size_t o_dtseq = put(prune ? wl.ldt_seq : wl.dtile_seq), o_dtq0 = put(prune ? wl.ldt_q0 : wl.dtile_q0);
-    const int n_tiles = (int)(prune ? wl.lt_seq : wl.tile_seq).size(), n_rtiles = (int)(prune ? wl.lrt_seq : wl.rtile_seq).size(),
-              n_dtiles = (int)(prune ? wl.ldt_seq : wl.dtile_seq).size();
+    std::vector<int> m;                                                 // the probe's own block: the packer's part alone (no ids in front)
+    const PrefillPacked packed = prefill_pack(prefill_work_lists(n, lens, pos0, cap, dcap), n, lens, pos0, slots, m);
     DevBuf mb;
     if (hipMalloc(&mb.p, m.size() * sizeof(int)) != hipSuccess) return NTTS_ENOMEM;
     if (hipMemcpy(mb.p, m.data(), m.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) return NTTS_EHIP;
-    const int* md = (const int*)mb.p;
-    const PrefillMeta meta{md + o_base, md + o_len, md + o_pos0, md + o_slot, md + o_tok_seq, md + o_tseq, md + o_tq0};
-    const hipStream_t st = (hipStream_t)0;
-    const int Ti = (int)T;
-    if (generic) {   // q AND k normalised + rotated by the writer (q in place), v scattered
-        RopeNormArgs g{};
-        g.qkv = (bf16_t*)qkv_dev; g.ld_qkv = ld_qkv; g.kpool = (bf16_t*)kpool_dev; g.vpool = (bf16_t*)vpool_dev; g.block_table = block_table_dev;
-        g.max_pages = max_pages; g.meta = meta; g.rope_cos = (const bf16_t*)rope_cos_dev; g.rope_sin = (const bf16_t*)rope_sin_dev;
-        g.q_norm = (const bf16_t*)q_norm_dev; g.k_norm = (const bf16_t*)k_norm_dev; g.eps = eps; g.nh = nh; g.nkv = nkv; g.rows = Ti; g.write_v = 1;
-        const long items = (long)Ti * (nh + 2 * nkv);
-        if (head_dim == 128) NTTS_LAUNCH((rope_norm_kv_write_kernel<128>), dim3((unsigned)((items + 3) / 4)), dim3(256), st, g);
-        else NTTS_LAUNCH((rope_norm_kv_write_kernel<64>), dim3((unsigned)((items + 3) / 4)), dim3(256), st, g);
-    } else {         // k rotated into its page, v scattered; the attention kernels rotate q as they load it
-        RopeWriteArgs r{};
-        r.qkv = (bf16_t*)qkv_dev; r.ld_qkv = ld_qkv; r.kpool = (bf16_t*)kpool_dev; r.vpool = (bf16_t*)vpool_dev; r.block_table = block_table_dev;
-        r.max_pages = max_pages; r.meta = meta; r.rope_cos = (const bf16_t*)rope_cos_dev; r.rope_sin = (const bf16_t*)rope_sin_dev;
-        r.nh = nh; r.nkv = nkv; r.T = Ti; r.skip_q = 1;
-        NTTS_LAUNCH((rope_kv_write_vec_kernel), dim3((Ti + kRopeTokPerBlock - 1) / kRopeTokPerBlock), dim3(256), st, r);
-    }
-    AttnPrefillArgs a{};
-    a.qkv = (const bf16_t*)qkv_dev; a.ld_qkv = ld_qkv; a.out = (bf16_t*)out_dev; a.ld_out = (long)nh * head_dim; a.out_fp8_inv = out_fp8_inv;
-    a.kpool = (const bf16_t*)kpool_dev; a.vpool = (const bf16_t*)vpool_dev; a.block_table = block_table_dev; a.max_pages = max_pages;
-    a.meta = meta; a.nh = nh; a.nkv = nkv;
-    if (!generic) { a.rope_cos = (const bf16_t*)rope_cos_dev; a.rope_sin = (const bf16_t*)rope_sin_dev; }
-    if (n_tiles) { if (head_dim == 128) attn_prefill_launch_hd128(a, n_tiles, st); else attn_prefill_launch(a, n_tiles, st); }
-    a.meta.tile_seq = md + o_rtseq; a.meta.tile_q0 = md + o_rtq0;
-    if (n_rtiles) attn_prefill_res_launch(a, n_rtiles, cap, prune, st);
-    a.meta.tile_seq = md + o_dtseq; a.meta.tile_q0 = md + o_dtq0;
-    if (n_dtiles) attn_prefill_deep_launch(a, n_dtiles, cap, dcap, prune, st);
+    prefill_attn_layer((bf16_t*)qkv_dev, ld_qkv, (bf16_t*)out_dev, (long)nh * head_dim, out_fp8_inv, (bf16_t*)kpool_dev, (bf16_t*)vpool_dev,
+                       block_table_dev, max_pages, packed.bind((const int*)mb.p), nh, nkv, head_dim, (const bf16_t*)rope_cos_dev,
+                       (const bf16_t*)rope_sin_dev, (const bf16_t*)q_norm_dev, (const bf16_t*)k_norm_dev, eps, generic, (int)T, cap, dcap,
+                       only_last != 0, (hipStream_t)0);
     return hipDeviceSynchronize() == hipSuccess && hipGetLastError() == hipSuccess ? NTTS_OK : NTTS_EHIP;
 }

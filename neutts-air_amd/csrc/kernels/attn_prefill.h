@@ -965,8 +965,8 @@ NTTS_KERNEL(512) void attn_prefill_deep_kernel(AttnPrefillArgs p) {
     }
 }
 
-// ---- host side: the work lists of one prompt pass, from the prompts' lengths alone (plain vectors in and out: ntts_backbone_prefill and the parity
-// probe kapi.cpp ntts_k_attn_prefill_probe both call this, so the probe runs the kernels over exactly the lists the engine would build).
+// ---- host side: the work lists of one prompt pass, from the prompts' lengths alone (plain vectors in and out: ntts_backbone_prefill,
+// ntts_backbone_score and the parity probe kapi.cpp ntts_k_attn_prefill_probe all call this, so the probe runs the kernels over exactly the lists the engine would build).
 struct PrefillWorkLists {
     std::vector<int> tok_seq, tok_base, last_row;                                   // PrefillMeta arrays ([T], [n]) and each prompt's last packed row
     std::vector<int> tile_seq, tile_q0, rtile_seq, rtile_q0, dtile_seq, dtile_q0;   // two-sweep tiles, resident and deep work items (deepest first)
@@ -1027,6 +1027,46 @@ inline PrefillWorkLists prefill_work_lists(int n, const int* lens, const int* po
         else { const int b0 = pos0[i] > dcap ? pos0[i] : dcap; lt_seq.push_back(i); lt_q0.push_back(b0 + (last - b0) / 64 * 64); }
     }
     return w;
+}
+
+// ---- the prompt-pass part of a meta block, packed in ONE place for ntts_backbone_prefill, ntts_backbone_score and the parity probe.  Appended to `m`
+// (whatever it already holds -- the engine's packed token ids -- stays in front), in this order:
+//   [tok_seq T] [tok_base n] [seq_len n] [pos0 n] [slot n] [last_row n]
+//   [tile_seq | tile_q0] [rtile_seq | rtile_q0] [dtile_seq | dtile_q0]      two-sweep, resident and deep work lists of every layer
+//   [lt_seq | lt_q0]     [lrt_seq | lrt_q0]     [ldt_seq | ldt_q0]          the same three tiers of the pruned last layer
+struct PrefillTier { const int *seq, *q0; int n; };   // one tier's work list on the device
+struct PrefillPass {                                   // a packed pass on the device
+    PrefillMeta meta;                                  // (tile_seq / tile_q0: the two-sweep list of every layer; prefill_attn_layer points them at the tier it launches)
+    const int* last_row;                               // [n] each prompt's last packed row
+    PrefillTier all[3], last[3];                       // two-sweep, resident, deep: every layer's lists / the last layer's when it is pruned
+};
+struct PrefillPacked {                                 // where prefill_pack put things: offsets into the block
+    size_t tok_seq, per_prompt, tier[6];
+    int n, count[6];
+    PrefillPass bind(const int* md) const {
+        const int* p = md + per_prompt;
+        PrefillPass v{};
+        for (int k = 0; k < 6; ++k) (k < 3 ? v.all[k] : v.last[k - 3]) = PrefillTier{md + tier[k], md + tier[k] + count[k], count[k]};
+        v.meta = PrefillMeta{p, p + n, p + 2 * n, p + 3 * n, md + tok_seq, v.all[0].seq, v.all[0].q0};
+        v.last_row = p + 4 * n;
+        return v;
+    }
+};
+inline PrefillPacked prefill_pack(const PrefillWorkLists& w, int n, const int* lens, const int* pos0, const int* slots, std::vector<int>& m) {
+    PrefillPacked o{};
+    auto put = [&](const int* b, size_t k) { const size_t at = m.size(); m.insert(m.end(), b, b + k); return at; };
+    o.n = n;
+    o.tok_seq = put(w.tok_seq.data(), w.tok_seq.size());
+    o.per_prompt = put(w.tok_base.data(), n);
+    put(lens, n); put(pos0, n); put(slots, n); put(w.last_row.data(), n);
+    const std::vector<int>* tiers[6][2] = {{&w.tile_seq, &w.tile_q0}, {&w.rtile_seq, &w.rtile_q0}, {&w.dtile_seq, &w.dtile_q0},
+                                           {&w.lt_seq, &w.lt_q0},     {&w.lrt_seq, &w.lrt_q0},     {&w.ldt_seq, &w.ldt_q0}};
+    for (int k = 0; k < 6; ++k) {
+        o.count[k] = (int)tiers[k][0]->size();
+        o.tier[k] = put(tiers[k][0]->data(), o.count[k]);
+        put(tiers[k][1]->data(), o.count[k]);
+    }
+    return o;
 }
 // the caps as ntts_backbone_create clamps them: whole pages, at most kPfResPages / kPfDeepPages pages, deep >= res
 inline void prefill_clamp_caps(int res_cap, int deep_cap, int* res_out, int* deep_out) {
@@ -1090,6 +1130,41 @@ inline void attn_prefill_launch_hd128(const AttnPrefillArgs& p, int n_tiles, hip
     if (group == 1 || pairs * group <= 256) { NTTS_LAUNCH((attn_prefill_gqa_kernel<1, 128>), dim3(p.nkv, n_tiles, group), dim3(256), s, p); return; }
     if (group == 2 || pairs * ((group + 1) / 2) <= 256) { NTTS_LAUNCH((attn_prefill_gqa_kernel<2, 128>), dim3(p.nkv, n_tiles, (group + 1) / 2), dim3(256), s, p); return; }
     NTTS_LAUNCH((attn_prefill_gqa_kernel<4, 128>), dim3(p.nkv, n_tiles, (group + 3) / 4), dim3(256), s, p);
+}
+
+// One layer's prompt-pass attention over T packed rows, between the QKV GEMM and o_proj: the page writer, then the two-sweep, the resident and the
+// deep tier over the lists of `P` (the pruned last layer's with only_last), each skipped when its list is empty.  The engine's prompt pass and the
+// parity probe (kapi.cpp ntts_k_attn_prefill_probe) both run THIS sequence, so the op-level tests hold the engine's own to the spec.
+// generic = head_dim 128 and / or qk-norm (q_norm / k_norm may be null): the writer normalises + rotates q AND k (q in place) and the attention kernels
+// load q as it is.  Otherwise the writer rotates k into its page and scatters v, and the attention kernels rotate q as they load it (one read + one
+// write of T x 896 values less per layer: prompt pass 28.16 -> 27.94 ms per chunk, profiles/r02k_sweep_pf_rope_q_fused.log).
+// out_fp8_inv > 0: `out` rows hold e4m3 BYTES (ld_out counts bytes then).
+inline void prefill_attn_layer(bf16_t* qkv, long ld_qkv, bf16_t* out, long ld_out, float out_fp8_inv, bf16_t* kpool, bf16_t* vpool,
+                               const int* block_table, int max_pages, const PrefillPass& P, int nh, int nkv, int head_dim,
+                               const bf16_t* rope_cos, const bf16_t* rope_sin, const bf16_t* q_norm, const bf16_t* k_norm, float eps, bool generic,
+                               int T, int res_cap, int deep_cap, bool only_last, hipStream_t s) {
+    if (generic) {
+        RopeNormArgs g{};
+        g.qkv = qkv; g.ld_qkv = ld_qkv; g.kpool = kpool; g.vpool = vpool; g.block_table = block_table; g.max_pages = max_pages; g.meta = P.meta;
+        g.rope_cos = rope_cos; g.rope_sin = rope_sin; g.q_norm = q_norm; g.k_norm = k_norm; g.eps = eps; g.nh = nh; g.nkv = nkv; g.rows = T; g.write_v = 1;
+        const long items = (long)T * (nh + 2 * nkv);
+        if (head_dim == 128) NTTS_LAUNCH((rope_norm_kv_write_kernel<128>), dim3((unsigned)((items + 3) / 4)), dim3(256), s, g);
+        else NTTS_LAUNCH((rope_norm_kv_write_kernel<64>), dim3((unsigned)((items + 3) / 4)), dim3(256), s, g);
+    } else {
+        RopeWriteArgs r{};
+        r.qkv = qkv; r.ld_qkv = ld_qkv; r.kpool = kpool; r.vpool = vpool; r.block_table = block_table; r.max_pages = max_pages; r.meta = P.meta;
+        r.rope_cos = rope_cos; r.rope_sin = rope_sin; r.nh = nh; r.nkv = nkv; r.T = T; r.skip_q = 1;
+        NTTS_LAUNCH((rope_kv_write_vec_kernel), dim3((T + kRopeTokPerBlock - 1) / kRopeTokPerBlock), dim3(256), s, r);
+    }
+    AttnPrefillArgs a{};
+    a.qkv = qkv; a.ld_qkv = ld_qkv; a.out = out; a.ld_out = ld_out; a.out_fp8_inv = out_fp8_inv; a.kpool = kpool; a.vpool = vpool;
+    a.block_table = block_table; a.max_pages = max_pages; a.meta = P.meta; a.nh = nh; a.nkv = nkv;
+    if (!generic) { a.rope_cos = rope_cos; a.rope_sin = rope_sin; }
+    const PrefillTier* tier = only_last ? P.last : P.all;
+    auto has = [&](const PrefillTier& t) { a.meta.tile_seq = t.seq; a.meta.tile_q0 = t.q0; return t.n > 0; };
+    if (has(tier[0])) { if (head_dim == 128) attn_prefill_launch_hd128(a, tier[0].n, s); else attn_prefill_launch(a, tier[0].n, s); }
+    if (has(tier[1])) attn_prefill_res_launch(a, tier[1].n, res_cap, only_last, s);
+    if (has(tier[2])) attn_prefill_deep_launch(a, tier[2].n, res_cap, deep_cap, only_last, s);
 }
 
 }  // namespace ntts

@@ -128,6 +128,35 @@ def test_prompt_pass_attention_tiers_logits(emu_lib, monkeypatch):
         assert torch.equal(rows[("512", "1024")][u], rows[("0", "1024")][u])    # the resident and the deep kernel are the same arithmetic
 
 
+@pytest.mark.parametrize("caps", [None, ("32", "64")])
+def test_full_prompt_pass_fits_the_meta_block(emu_lib, monkeypatch, caps):
+    """The largest calls an engine of 4 slots, context 128 and 512 prefill tokens admits must fit its meta block: one prefill that fills all four
+    slots with 127-token prompts (508 packed rows, the most `len < max_length <= max_context` allows) and decodes a step, then, after release, one
+    score call of four 128-token sequences (512 rows = max_prefill_tokens, score_from 1: 508 values).  With the default tiers (everything resident)
+    and with cuts at 32 / 64 around engine creation, where every prompt has work items in all three tiers (the longest work lists)."""
+    if caps:
+        monkeypatch.setenv("NTTS_PF_RES_CAP", caps[0])
+        monkeypatch.setenv("NTTS_PF_DEEP_CAP", caps[1])
+    cfg = br.BackboneConfig(vocab_size=600, hidden_size=128, intermediate_size=256, num_layers=2, num_heads=2, num_kv_heads=1)
+    w = br.make_weights(cfg, 23)
+    eng = make_engine(cfg, w, emu_lib, max_batch=4, max_context=128, max_prefill_tokens=512)
+    if caps:
+        monkeypatch.delenv("NTTS_PF_RES_CAP")
+        monkeypatch.delenv("NTTS_PF_DEEP_CAP")
+    eos = cfg.vocab_size - 1
+    samp = _hip.Sampling(max_length=128, min_new_tokens=1, eos_token_id=eos, do_sample=False)
+    eng.prefill([br.synthetic_prompt(cfg, u, 127) for u in range(4)], [0, 1, 2, 3], [samp] * 4)
+    eng.decode(1)
+    for s in range(4):
+        ids, fin = eng.read(s)
+        assert fin and len(ids) == 1 and 0 <= ids[0] < eos
+        eng.release(s)
+    lp, am, alp = eng.score_call([br.synthetic_prompt(cfg, 4 + u, 128) for u in range(4)], [0, 1, 2, 3], [1] * 4)
+    assert len(lp) == len(am) == len(alp) == 508
+    assert np.isfinite(lp).all() and (lp <= alp).all() and (alp <= 0).all() and ((0 <= am) & (am < cfg.vocab_size)).all()
+    eng.close()
+
+
 def test_xcd_row_block_placement(emu_lib, monkeypatch):
     """NTTS_XCD_AFFINE=7 (the default above batch 128): split-K GEMMs, the norms behind them and decode attention place the rows of a
     64-row m-block on one group of XCDs (gemm.h xcd_maffine, norm.h xcd_row).  A pure permutation of which workgroup does what:

@@ -176,6 +176,34 @@ def test_prompt_pass_attention_split_by_position(lib, monkeypatch, caps):
     eng.close()
 
 
+@pytest.mark.parametrize("caps", [None, ("32", "64")])
+def test_full_prompt_pass_fits_the_meta_block(lib, monkeypatch, caps):
+    """The twin of tests/test_emu_engine.py's test of the same name: the largest prefill (4 x 127 tokens, then one decode step) and the largest
+    score call (4 x 128 tokens, 508 values) of a 4-slot engine with context 128 and 512 prefill tokens fit its meta block, with the default tiers
+    and with cuts at 32 / 64 (work items in all three tiers for every prompt)."""
+    if caps:
+        monkeypatch.setenv("NTTS_PF_RES_CAP", caps[0])
+        monkeypatch.setenv("NTTS_PF_DEEP_CAP", caps[1])
+    cfg = br.BackboneConfig(vocab_size=600, hidden_size=128, intermediate_size=256, num_layers=2, num_heads=2, num_kv_heads=1)
+    w = br.make_weights(cfg, 23)
+    eng = make_engine(cfg, w, lib, max_batch=4, max_context=128, max_prefill_tokens=512)
+    if caps:
+        monkeypatch.delenv("NTTS_PF_RES_CAP")
+        monkeypatch.delenv("NTTS_PF_DEEP_CAP")
+    eos = cfg.vocab_size - 1
+    samp = _hip.Sampling(max_length=128, min_new_tokens=1, eos_token_id=eos, do_sample=False)
+    eng.prefill([br.synthetic_prompt(cfg, u, 127) for u in range(4)], [0, 1, 2, 3], [samp] * 4)
+    eng.decode(1)
+    for s in range(4):
+        ids, fin = eng.read(s)
+        assert fin and len(ids) == 1 and 0 <= ids[0] < eos
+        eng.release(s)
+    lp, am, alp = eng.score_call([br.synthetic_prompt(cfg, 4 + u, 128) for u in range(4)], [0, 1, 2, 3], [1] * 4)
+    assert len(lp) == len(am) == len(alp) == 508
+    assert np.isfinite(lp).all() and (lp <= alp).all() and (alp <= 0).all() and ((0 <= am) & (am < cfg.vocab_size)).all()
+    eng.close()
+
+
 def test_prompt_pass_attention_tiers_logits(lib, monkeypatch):
     """The id-for-id tier tests above run on walk weights, whose next id barely depends on attention (that is their point).  This one is the
     sensitive one: RANDOM-init weights (flat logits, every layer's attention matters), 4 layers at NeuTTS-Air's width, prompts of 1100 / 700 /
