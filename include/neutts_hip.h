@@ -188,13 +188,23 @@ int ntts_backbone_activate(ntts_backbone* e, int32_t n, const int32_t* park_slot
  * deviation from HF is at most half a bf16 ulp of the penalised logit (relative 2^-8) and touches penalised tokens only: the one place where the
  * processed logits (ntts_backbone_read_logits) are not HF's value for value.  -inf (a masked EOS) stays -inf for any valid p; no NaN arises.
  * With repetition_penalty = 1 (or 0, a zeroed field) a request computes exactly what it computed under ABI 10, and an engine that has no penalised
- * request in flight runs exactly the kernels it ran under ABI 10. */
+ * request in flight runs exactly the kernels it ran under ABI 10.
+ * top_k = NTTS_TOP_K_OFF (-1; transformers spells it top_k=0 / None, serving stacks -1): no top-k cut.  Temperature, top_p and min_p act on the WHOLE
+ * vocabulary and the draw is over the model's own distribution -- the one `logprobs` and ntts_backbone_score describe.  Same struct, same ABI version:
+ * the value was NTTS_EINVAL before.  The contract (tests/sampling_full_spec.py): e_a = fp32 exp((x_a - max) * (1 / T)), the mass of token a is the
+ * INTEGER q_a = floor(e_a * 2^32), every sum is an exact integer sum; top_p: ranked by value descending, ties by token id ascending, a token survives
+ * while the mass strictly before it is < floor(top_p * sum q) (the first always survives); min_p: e_a >= min_p; both evaluated on the whole row and
+ * ANDed; draw: the first survivor, in token-id order, whose running mass exceeds (u24 * S) >> 24, S the survivors' mass, u24 the top 24 bits of
+ * Philox(seed, step)[0].  The ids depend on the row and the parameters only -- not on slot, batch or the order of any additions.  A token whose
+ * probability is below 2^-32 of the likeliest token's has mass 0 and is never drawn. */
+#define NTTS_TOP_K_OFF (-1)
 typedef struct ntts_sampling {
     int32_t max_length;      /* total length cap (prompt + new), <= max_context        [2048] */
     int32_t min_new_tokens;  /* EOS logit = -inf while fewer new tokens than this      [50]   */
     int32_t eos_token_id;    /* <|SPEECH_GENERATION_END|>                                      */
     int32_t do_sample;       /* 0 = greedy argmax (first max wins); 1 = temperature, top-k, multinomial [1] */
-    int32_t top_k;           /* [50]  >= 1; logits below the k-th largest are dropped, ties at the k-th kept (<= 512 kept) */
+    int32_t top_k;           /* [50]  >= 1; logits below the k-th largest are dropped, ties at the k-th kept (<= 512 kept: a larger k is capped there --
+                              * NTTS_TOP_K_OFF (-1) samples over the whole vocabulary instead).  0 and anything below -1: NTTS_EINVAL.  Ignored when do_sample = 0 */
     float temperature;       /* [1.0] > 0 */
     uint64_t seed;           /* Philox4x32-10 key for do_sample=1; the draw of step t depends on (seed, t) only: give each request its own seed */
     float top_p;             /* [1.0] (0, 1].  < 1: nucleus cut over the top-k survivors, ranked by probability descending (ties: lowest token id first) --
@@ -693,6 +703,16 @@ int ntts_k_silu_probe(const void* in_bf16_dev, void* out_bf16_dev, int64_t n, in
 int ntts_k_sample_probe(const void* logits_dev, int64_t ld_logits, int32_t rows, int32_t vocab, int32_t group_width, const int32_t* top_k,
                         const float* temperature, const float* top_p, const float* min_p, const uint64_t* seed, int32_t step,
                         int32_t* token_out, int32_t* n_out, int32_t* ids_out);
+
+/* The whole-vocabulary token choice (ntts_sampling.top_k = NTTS_TOP_K_OFF; the device function the decode step's sampling kernel calls for such a
+ * slot) on caller-supplied rows.  logits_dev, ld_logits, rows, vocab, temperature / top_p / min_p / seed (HOST, per row), step and the validation are
+ * ntts_k_sample_probe's (which keeps refusing top_k < 1: its id list holds 512).  group_width means what it means there -- > 0: the row's maximum is
+ * taken from the maxima of groups of that many columns, as in the decode step; 0: from one more pass over the row -- and the results do not depend
+ * on it.  Out (HOST): token_out[r] the drawn token, n_out[r] the number of survivors, keep_bits_out[r * ((vocab + 31) / 32) ...] their bitmap (bit
+ * c & 31 of word c >> 5), total_out[r] their total integer mass S. */
+int ntts_k_sample_full_probe(const void* logits_dev, int64_t ld_logits, int32_t rows, int32_t vocab, int32_t group_width, const float* temperature,
+                             const float* top_p, const float* min_p, const uint64_t* seed, int32_t step, int32_t* token_out, int32_t* n_out,
+                             uint32_t* keep_bits_out, uint64_t* total_out);
 
 /* ABI 11.  The engine's lm_head launch (the GEMM tile + argmax / penalty epilogue the decode step runs) on caller-supplied data.  X_dev: DEVICE bf16
  * [M][K]; W_dev: DEVICE bf16 [N][K] row-major -- the probe packs it the way the engine packs the head (tile-major; fp8 != 0: quantised per output

@@ -1719,8 +1719,8 @@ static int prefill_impl(ntts_backbone* e, int32_t n, const int32_t* ids, const i
         if (lens[i] < 1) return fail(e, NTTS_EINVAL, "empty prompt %d", i);
         if (samp[i].max_length > c.max_context || samp[i].max_length <= lens[i])
             return fail(e, NTTS_EINVAL, "prompt %d: need len < max_length <= max_context (%d, %d)", i, lens[i], samp[i].max_length);
-        if (samp[i].do_sample && (samp[i].top_k < 1 || !(samp[i].temperature > 0.f)))
-            return fail(e, NTTS_EINVAL, "prompt %d: do_sample needs top_k >= 1 and temperature > 0 (got %d, %g)", i, samp[i].top_k, samp[i].temperature);
+        if (samp[i].do_sample && ((samp[i].top_k < 1 && samp[i].top_k != NTTS_TOP_K_OFF) || !(samp[i].temperature > 0.f)))
+            return fail(e, NTTS_EINVAL, "prompt %d: do_sample needs top_k >= 1 (or -1: the whole vocabulary) and temperature > 0 (got %d, %g)", i, samp[i].top_k, samp[i].temperature);
         // TopPLogitsWarper / MinPLogitsWarper's own ranges (hf:generation/logits_process.py); a NaN fails both comparisons
         if (samp[i].do_sample && !(samp[i].top_p > 0.f && samp[i].top_p <= 1.0f))
             return fail(e, NTTS_EINVAL, "prompt %d: top_p must lie in (0, 1] (got %g)", i, samp[i].top_p);

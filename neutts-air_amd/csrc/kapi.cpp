@@ -419,6 +419,73 @@ extern "C" int ntts_k_sample_probe(const void* logits_dev, int64_t ld_logits, in
     return rc;
 }
 
+namespace {
+struct ProbeBuf { void* p = nullptr; ~ProbeBuf() { if (p) (void)hipFree(p); } };   // a device allocation of a probe, freed on every return path
+}
+
+// ---- whole-vocabulary sampler probe: sample_full_row (top_k = -1) on caller-supplied rows; the survivors come back as a bitmap
+struct SampleFullProbeArgs {
+    SampleProbeArgs s;                 // logits, ld, vocab, part_val / n_part / part_width, fparams, seed, step, token, n_surv, rows (top_k, surv unused)
+    unsigned char* keep;               // [rows][keep_pitch] bytes: bit c & 7 of byte c >> 3
+    long keep_pitch;
+    unsigned long long* total;         // [rows]
+};
+NTTS_KERNEL(256) void sample_full_probe_kernel(SampleFullProbeArgs a) {
+    const SampleProbeArgs& p = a.s;
+    const int b = blockIdx.x;
+    const int tok = sample_full_row(p.logits + (long)b * p.ld, p.vocab, p.fparams[b], p.fparams[p.rows + b], p.fparams[2 * p.rows + b], p.seed[2 * b],
+                                    p.seed[2 * b + 1], p.step, p.part_val ? p.part_val + (long)b * p.n_part : nullptr, p.n_part,
+                                    a.keep + (long)b * a.keep_pitch, p.n_surv + b, a.total + b);
+    if (threadIdx.x == 0) p.token[b] = tok;
+}
+extern "C" int ntts_k_sample_full_probe(const void* logits_dev, int64_t ld_logits, int32_t rows, int32_t vocab, int32_t group_width,
+                                        const float* temperature, const float* top_p, const float* min_p, const uint64_t* seed, int32_t step,
+                                        int32_t* token_out, int32_t* n_out, uint32_t* keep_bits_out, uint64_t* total_out) {
+    if (!logits_dev || !temperature || !top_p || !min_p || !seed || !token_out || !n_out || !keep_bits_out || !total_out) return NTTS_EINVAL;
+    if (rows < 1 || vocab < 1 || ld_logits < vocab || (ld_logits % 8) || ((uintptr_t)logits_dev & 15) || step < 0) return NTTS_EINVAL;
+    if (group_width < 0 || (group_width % 8)) return NTTS_EINVAL;
+    for (int r = 0; r < rows; ++r)
+        if (!(temperature[r] > 0.f) || !(top_p[r] > 0.f && top_p[r] <= 1.0f) || !(min_p[r] >= 0.f && min_p[r] <= 1.0f)) return NTTS_EINVAL;
+    const int n_part = group_width ? (vocab + group_width - 1) / group_width : 0;
+    const size_t kw = ((size_t)vocab + 31) / 32;                    // bitmap words per row
+    // device blocks: [seed 2 rows][token rows][n_surv rows] ints | [temperature, top_p, min_p: 3 rows][part_val rows * n_part] floats |
+    //                [total rows] 64-bit words, then [rows][kw] bitmap words (zeroed: the kernel writes whole bytes up to column vocab - 1)
+    const size_t n_int = (size_t)rows * 4, n_flt = (size_t)rows * (3 + n_part), n_out8 = (size_t)rows * 8 + (size_t)rows * kw * 4;
+    std::vector<int> hi(n_int, 0);
+    std::vector<float> hf((size_t)rows * 3);
+    for (int r = 0; r < rows; ++r) {
+        hi[2 * r] = (int)(uint32_t)seed[r];
+        hi[2 * r + 1] = (int)(uint32_t)(seed[r] >> 32);
+        hf[r] = temperature[r]; hf[rows + r] = top_p[r]; hf[2 * rows + r] = min_p[r];
+    }
+    ProbeBuf di, df, dk;
+    if (hipMalloc(&di.p, n_int * sizeof(int)) != hipSuccess || hipMalloc(&df.p, n_flt * sizeof(float)) != hipSuccess ||
+        hipMalloc(&dk.p, n_out8) != hipSuccess)
+        return NTTS_ENOMEM;
+    if (hipMemcpy(di.p, hi.data(), n_int * sizeof(int), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(df.p, hf.data(), hf.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess || hipMemset(dk.p, 0, n_out8) != hipSuccess)
+        return NTTS_EHIP;
+    SampleFullProbeArgs a{};
+    int* dip = (int*)di.p;
+    float* dfp = (float*)df.p;
+    a.s.logits = (const bf16_t*)logits_dev; a.s.ld = ld_logits; a.s.vocab = vocab; a.s.n_part = n_part; a.s.part_width = group_width;
+    a.s.seed = (const unsigned int*)dip; a.s.token = dip + 2 * rows; a.s.n_surv = dip + 3 * rows;
+    a.s.fparams = dfp; a.s.step = (unsigned int)step; a.s.rows = rows;
+    a.total = (unsigned long long*)dk.p; a.keep = (unsigned char*)dk.p + (size_t)rows * 8; a.keep_pitch = (long)(kw * 4);
+    if (group_width) {
+        NTTS_LAUNCH((group_max_kernel), dim3(rows), dim3(256), (hipStream_t)0, a.s, dfp + 3 * (size_t)rows);
+        a.s.part_val = dfp + 3 * (size_t)rows;
+    }
+    NTTS_LAUNCH((sample_full_probe_kernel), dim3(rows), dim3(256), (hipStream_t)0, a);
+    if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess) return NTTS_EHIP;
+    if (hipMemcpy(hi.data(), di.p, n_int * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(total_out, dk.p, (size_t)rows * 8, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(keep_bits_out, (unsigned char*)dk.p + (size_t)rows * 8, (size_t)rows * kw * 4, hipMemcpyDeviceToHost) != hipSuccess)
+        return NTTS_EHIP;
+    for (int r = 0; r < rows; ++r) { token_out[r] = hi[2 * rows + r]; n_out[r] = hi[3 * rows + r]; }
+    return NTTS_OK;
+}
+
 extern "C" int ntts_k_mfma_probe(float* out_dev_768) {
     if (!out_dev_768) return NTTS_EINVAL;
     NTTS_LAUNCH((mfma_probe_kernel), dim3(1), dim3(64), (hipStream_t)0, out_dev_768);
@@ -428,7 +495,6 @@ extern "C" int ntts_k_mfma_probe(float* out_dev_768) {
 // ---- operands of the lm_head probes, packed by the kernels the engine packs its head with: W [N][K] bf16 row-major -> tile-major bf16, or (fp8) e4m3
 //      bytes + per-row scales, X then quantised to e4m3 at the static scale xscale.  *X_out = the rows the launch reads.
 namespace {
-struct ProbeBuf { void* p = nullptr; ~ProbeBuf() { if (p) (void)hipFree(p); } };
 bool probe_alloc(ProbeBuf& b, size_t bytes) { return hipMalloc(&b.p, bytes) == hipSuccess && hipMemset(b.p, 0, bytes) == hipSuccess; }
 struct ProbeOperands { ProbeBuf wt, ws, xq, xf; };
 int pack_probe_operands(const void* X_dev, const void* W_dev, int M, int N, int K, int fp8, float xscale, ProbeOperands& o, const bf16_t** X_out) {

@@ -9,6 +9,9 @@
 //                  [MinPLogitsWarper, min_p > 0] -> softmax -> multinomial(1)
 //                  (the reference's own call: do_sample=True, temperature=1.0, top_k=50, ref:neutts/neutts.py:338-347; top_p /
 //                  min_p are generate()'s own keyword arguments, off -- 1.0 / 0.0 -- in that call)
+//                  top_k = -1 (transformers' top_k=0 / None, serving stacks' -1): no TopKLogitsWarper -- temperature, top_p and min_p act on the
+//                  whole vocabulary and the draw is over the model's own distribution (sample_full_row below: integer masses of 2^-32 of the
+//                  likeliest token's, so a token less likely than that is never drawn)
 //   -> append -> EosTokenCriteria / MaxLengthCriteria.
 // RepetitionPenaltyLogitsProcessor (repetition_penalty != 1; first in hf:generation/utils.py _get_logits_processor, ahead of MinNewTokensLength and the
 // warpers) also lives in the lm_head epilogue (gemm.h EPI_ARGMAX_PEN): it reads a per-slot bitmap of the lm_head columns the request has seen.  This file
@@ -35,7 +38,7 @@ struct SlotArrays {      // device arrays, one entry per decode slot
     int* max_len;
     int* eos;
     int* mask_eos;       // eos+1 while EOS is masked for the NEXT sampled token (n_new < min_new), else 0
-    int* top_k;          // 0 = greedy (do_sample=0); k >= 1 = sample among the k largest logits
+    int* top_k;          // 0 = greedy (do_sample=0); k >= 1 = sample among the k largest logits; -1 = sample over the whole vocabulary
     float* temperature;  // > 0
     float* top_p;        // (0, 1]; 1 = no nucleus cut
     float* min_p;        // [0, 1]; 0 = no min-p cut
@@ -341,6 +344,269 @@ NTTS_D int sample_topk_row(const bf16_t* row, int V, int k, float temperature, f
     return result;
 }
 
+// ---- whole-vocabulary sampling (top_k = NTTS_TOP_K_OFF = -1): temperature -> top_p -> min_p -> draw over ALL V columns, no top-k cut and no
+// candidate list.  The contract is tests/sampling_full_spec.py; what makes it a function of the row and the parameters alone is that the masses
+// are INTEGERS: e_a = fp32 exp((x_a - max) * (1 / T)) as in sample_topk_row, q_a = floor(e_a * 2^32) (exact, <= 2^32, a maximum has 2^32), and
+// every sum is an exact 64-bit sum of q -- no order of additions to keep, so 256 threads sum in whatever order they like, with no float atomics
+// and no single-thread walk over the row.  A token whose probability is below 2^-32 of the likeliest token's has q = 0 and is never drawn.
+//   top_p < 1: ranked by value descending, ties by token id ascending, rank j survives iff j == 0 or (mass strictly before it) < lim =
+//              floor(top_p * Q) (top_p taken as its exact fp32 value M * 2^-s: lim = (M * Q) >> s).  Tokens of equal logit have equal q, so the
+//              nucleus is "every key above a threshold key K, plus the r lowest ids at K": K by a 16-ary search over the 16-bit bf16_key (four
+//              passes over the row; each LANE has 16 bins of its own in LDS, shared by the four waves with 64-bit LDS atomics -- logits crowd
+//              into three or four exponent bins, bins shared inside a wave would serialise), r = ceil((lim - mass above K) / q_K), and, only when r cuts inside the tie group, the id of the r-th tie;
+//   min_p > 0: survives iff e_a >= min_p; both stages are evaluated on the whole row and ANDed (tests/sampling_spec.survivors);
+//   draw:      survivors in token-id order, S their mass, target = (u24 * S) >> 24 with the sampler's uniform u24 = philox(seed, step)[0] >> 8;
+//              the token is the first survivor whose running mass exceeds target.
+// "The first column, in id order, whose running weight exceeds a target" (the draw, and the r-th tie) is one routine: one pass adds every 8-column
+// unit's weight to its slot of 2048 * g columns in LDS, a block scan over the <= kFullSlots slots finds the slot, its tiles are read again and a
+// scan over the 256 threads finds the unit.  State in LDS and registers only.  pv / n_part: the lm_head's per-group maxima (the row's maximum is
+// theirs), or null: one more pass.  keep_out / n_out / total_out (ntts_k_sample_full_probe; null in the decode step): the survivor bitmap (byte
+// c >> 3, bit c & 7), their number, S.
+// Kept OUT of line: inlined, its code inside sample_greedy_kernel cost the default top-k path 1.0 us of its 26.8 us per decode step (256 rows, Air
+// geometry); as a call that path runs at the speed it had without it (profiles/full_vocab_sampling_bench.txt).
+constexpr int kFullSlots = 1024;
+NTTS_D unsigned long long shfl_u64(unsigned long long v, int src) {
+    const unsigned int lo = (unsigned int)shfl((int)(unsigned int)v, src), hi = (unsigned int)shfl((int)(unsigned int)(v >> 32), src);
+    return ((unsigned long long)hi << 32) | lo;
+}
+NTTS_D unsigned long long mul_shr24(unsigned long long a, unsigned long long x) {      // floor(a * x / 2^24) for a < 2^24, without the 88-bit product
+    return a * (x >> 24) + ((a * (x & 0xFFFFFFull)) >> 24);
+}
+// exclusive prefix of v over the block's 256 threads, in thread order, and the block's total; sc: 4 words of LDS (free again after the call's
+// first barrier).  All threads call it
+NTTS_D unsigned long long block_exscan_u64(unsigned long long v, unsigned long long* sc, unsigned long long& total) {
+    const int lane = lane_id(), w = wave_id();
+    unsigned long long inc = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const unsigned long long o = shfl_u64(inc, (lane - d) & 63);
+        if (lane >= d) inc += o;
+    }
+    sync();
+    if (lane == 63) sc[w] = inc;
+    sync();
+    unsigned long long ex = inc - v;
+    total = 0;
+    for (int ww = 0; ww < 4; ++ww) { if (ww < w) ex += sc[ww]; total += sc[ww]; }
+    return ex;
+}
+__attribute__((noinline)) NTTS_D int sample_full_row(const bf16_t* row, int V, float temperature, float top_p, float min_p, unsigned int s0, unsigned int s1, unsigned int step,
+                           const float* pv, int n_part, unsigned char* keep_out = nullptr, int* n_out = nullptr, unsigned long long* total_out = nullptr) {
+    typedef unsigned long long u64;
+    NTTS_SHARED u64 work[kFullSlots];         // search: bin d of lane l at [d * 64 + l]; locate: one sum per slot
+    NTTS_SHARED u64 red[16][16];
+    NTTS_SHARED u64 msum[16];
+    u64* const tsum = work;
+    NTTS_SHARED u64 sc[4];
+    NTTS_SHARED u64 hit[2];                   // [0] the slot / the column found, [1] the weight before the slot
+    NTTS_SHARED unsigned int wk[4];
+    NTTS_SHARED unsigned int nkeep;
+    const int tid = threadIdx.x;
+    const int nvec = V >> 3, nunit = (V + 7) >> 3;                   // 8-column units: 16-byte loads, the last one scalar if V % 8
+    const int ntile = (nunit + 255) >> 8;                            // 256 units = 2048 columns
+    const int g = (ntile + kFullSlots - 1) / kFullSlots;             // tiles per slot (1 up to 2 M columns)
+    const int nslot = (ntile + g - 1) / g;
+    // unit u of this thread: its first column, its values, how many are columns of the row
+    auto load_unit = [&](int u, bf16x8& v) -> int {
+        if (u < nvec) { v = ld16<bf16x8>(row + (long)u * 8); return 8; }
+        const int cnt = V - u * 8;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = e < cnt ? (short)row[(long)u * 8 + e] : (short)0;
+        return cnt;
+    };
+    auto for_each_elem = [&](auto&& f) {                             // f(unit, column, value)
+        for (int u = tid; u < nunit; u += 256) {
+            bf16x8 v;
+            const int cnt = load_unit(u, v);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) if (e < cnt) f(u, u * 8 + e, (bf16_t)v[e]);
+        }
+    };
+    constexpr unsigned int kInfKey = 0xFF80u;                        // bf16_key(+inf): the keys above it are NaNs
+    // ---- the row's maximum
+    unsigned int mk = 0;
+    if (pv) {
+        for (int i = tid; i < n_part; i += 256) { const unsigned int key = bf16_key(f2bf(pv[i])); if (key <= kInfKey && key > mk) mk = key; }
+    } else {
+        for_each_elem([&](int, int, bf16_t v) { const unsigned int key = bf16_key(v); if (key <= kInfKey && key > mk) mk = key; });
+    }
+#pragma unroll
+    for (int sh = 1; sh < 64; sh <<= 1) { const unsigned int o = (unsigned int)shfl_xor((int)mk, sh); mk = o > mk ? o : mk; }
+    if (lane_id() == 0) wk[wave_id()] = mk;
+    if (tid == 0) { hit[0] = 0; hit[1] = 0; nkeep = 0; }
+    sync();
+    mk = wk[0];
+    for (int w = 1; w < 4; ++w) mk = wk[w] > mk ? wk[w] : mk;
+    auto unkey = [](unsigned int key) { return (bf16_t)((key & 0x8000u) ? (key & 0x7FFFu) : (~key & 0xFFFFu)); };
+    const float m = bf2f(unkey(mk));
+    const float it = 1.0f / temperature;
+    auto e_of = [&](bf16_t v) { return fexp((bf2f(v) - m) * it); };
+    auto q_of_e = [](float e) -> u64 { return e >= 1.0f ? (1ull << 32) : (e > 0.f ? (u64)(unsigned int)(e * 4294967296.0f) : 0ull); };   // (a NaN: 0)
+    // ---- the first column, in id order, at which the running sum of wf(column, value) exceeds the target: (u24 * total) >> 24 if `draw`, else `fixed`
+    //      (< total).  *total_p = the total
+    auto locate = [&](auto&& wf, bool draw, u64 fixed, u64* total_p) -> int {
+        for (int i = tid; i < nslot; i += 256) tsum[i] = 0;
+        sync();
+        for (int u = tid; u < nunit; u += 256) {
+            bf16x8 v;
+            const int cnt = load_unit(u, v);
+            u64 part = 0;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) if (e < cnt) part += wf(u * 8 + e, (bf16_t)v[e]);
+            if (part) __atomic_fetch_add(&tsum[(u >> 8) / g], part, __ATOMIC_RELAXED);
+        }
+        sync();
+        const int spt = (nslot + 255) >> 8;                          // slots per thread, consecutive (<= 4)
+        u64 mine = 0;
+        for (int j = 0; j < spt; ++j) { const int i = tid * spt + j; if (i < nslot) mine += tsum[i]; }
+        u64 total;
+        u64 ex = block_exscan_u64(mine, sc, total);
+        const u64 target = draw ? mul_shr24((u64)fixed, total) : fixed;
+        if (mine && ex <= target && target - ex < mine) {            // (one thread, as target < total)
+            for (int j = 0; j < spt; ++j) {
+                const int i = tid * spt + j;
+                const u64 t = i < nslot ? tsum[i] : 0;
+                if (target - ex < t) { hit[0] = (u64)i; hit[1] = ex; break; }
+                ex += t;
+            }
+        }
+        sync();
+        const int slot = (int)hit[0];
+        u64 rem = target - hit[1];
+        sync();
+        const int t_end = (slot + 1) * g < ntile ? (slot + 1) * g : ntile;
+        for (int tile = slot * g; tile < t_end; ++tile) {            // (block-uniform)
+            const int u = tile * 256 + tid;
+            bf16x8 v;
+            const int cnt = u < nunit ? load_unit(u, v) : 0;
+            u64 part = 0;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) if (e < cnt) part += wf(u * 8 + e, (bf16_t)v[e]);
+            u64 ttot;
+            u64 exu = block_exscan_u64(part, sc, ttot);
+            if (rem < ttot) {
+                if (part && exu <= rem && rem - exu < part) {
+                    int col = -1;
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) {
+                        const u64 t = e < cnt ? wf(u * 8 + e, (bf16_t)v[e]) : 0;
+                        if (col < 0 && rem - exu < t) col = u * 8 + e;
+                        if (col < 0) exu += t;
+                    }
+                    hit[0] = (u64)(col < 0 ? u * 8 : col);
+                }
+                break;
+            }
+            rem -= ttot;
+        }
+        sync();
+        int col = (int)hit[0];
+        if (total_p) *total_p = total;
+        sync();
+        return col < V ? col : V - 1;
+    };
+    // ---- top_p: the threshold key, and the last id kept at it
+    const bool nucleus = top_p < 1.0f;
+    unsigned int thr = 0;
+    int id_last = 0x7fffffff;
+    if (nucleus) {                                                   // (block-uniform, like every branch below)
+        const unsigned int pb = __builtin_bit_cast(unsigned int, top_p);
+        const int pe = (int)(pb >> 23);                              // (top_p in (0, 1): no sign, exponent <= 126)
+        const u64 pm = pe ? ((pb & 0x7FFFFFu) | 0x800000u) : (pb & 0x7FFFFFu);
+        const int ps = (pe ? 150 - pe : 149) - 24;                   // top_p = pm * 2^-(ps + 24), ps >= 0
+        u64 above = 0, lim = 0, mass_k = 0;
+        unsigned int prefix = 0;
+        bool search = true;
+        for (int L = 0; L < 4 && search; ++L) {
+            const int sh = 12 - 4 * L;
+#pragma unroll
+            for (int d = 0; d < 4; ++d) work[d * 256 + tid] = 0;
+            sync();
+            for_each_elem([&](int, int, bf16_t v) {
+                const unsigned int key = bf16_key(v);
+                if ((key >> (sh + 4)) == prefix) {
+                    const u64 q = q_of_e(e_of(v));
+                    if (q) __atomic_fetch_add(&work[((key >> sh) & 15u) * 64 + (tid & 63)], q, __ATOMIC_RELAXED);
+                }
+            });
+            sync();
+            {
+                const int d = tid & 15, grp = tid >> 4;
+                u64 s = 0;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) s += work[d * 64 + grp * 4 + j];
+                red[d][grp] = s;
+            }
+            sync();
+            if (tid < 16) {
+                u64 s = 0;
+#pragma unroll
+                for (int j = 0; j < 16; ++j) s += red[tid][j];
+                msum[tid] = s;
+            }
+            sync();
+            if (L == 0) {
+                u64 Q = 0;
+                for (int d = 0; d < 16; ++d) Q += msum[d];
+                lim = ps < 64 ? (mul_shr24(pm, Q) >> ps) : 0ull;
+                if (lim == 0) search = false;                        // only rank 0 survives: the lowest id at the maximum
+            }
+            if (search) {
+                // walking down from bin 15: the bin that holds the smallest key K with (mass above K) < lim -- the first whose own mass takes the
+                // running mass to lim or past it (`above` < lim holds on entry at every level)
+                int d = 15;
+                for (; d > 0; --d) {
+                    if (above + msum[d] >= lim) break;
+                    above += msum[d];
+                }
+                mass_k = msum[d];
+                prefix = (prefix << 4) | (unsigned int)d;
+            }
+        }
+        u64 r = 1, n_k = 2;                                          // (lim == 0: one id at the maximum; the number of ties is not known)
+        thr = mk;
+        if (search) {
+            thr = prefix;
+            const u64 qk = q_of_e(e_of(unkey(thr)));                 // (> 0: a key of mass 0 has all of Q above it, and lim < Q)
+            n_k = qk ? mass_k / qk : 0;
+            r = qk ? (lim - above + qk - 1) / qk : 0;
+        }
+        if (r < n_k) {                                               // the cut falls inside the ties at thr: the r lowest ids stay
+            const unsigned int tk = thr;
+            id_last = locate([&](int, bf16_t v) -> u64 { return bf16_key(v) == tk ? 1ull : 0ull; }, false, r - 1, nullptr);
+        }
+    }
+    const bool use_min = min_p > 0.0f;
+    auto weight = [&](int col, bf16_t v) -> u64 {                    // q of a survivor, 0 of anything else
+        const unsigned int key = bf16_key(v);
+        if (nucleus && !(key > thr || (key == thr && col <= id_last))) return 0ull;
+        const float e = e_of(v);
+        if (use_min && !(e >= min_p)) return 0ull;
+        return q_of_e(e);
+    };
+    if (keep_out) {                                                  // (probe only; folded away in the decode step)
+        for (int u = tid; u < nunit; u += 256) {
+            bf16x8 v;
+            const int cnt = load_unit(u, v);
+            unsigned int bits = 0;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const unsigned int key = bf16_key((bf16_t)v[e]);
+                const bool kp = e < cnt && (!nucleus || key > thr || (key == thr && u * 8 + e <= id_last)) && (!use_min || e_of((bf16_t)v[e]) >= min_p);
+                bits |= (kp ? 1u : 0u) << e;
+            }
+            keep_out[u] = (unsigned char)bits;
+            if (bits) atomic_add_lds(&nkeep, (unsigned int)popc64((u64)bits));
+        }
+    }
+    unsigned int c[4] = {step, 0u, 0u, 0u};
+    philox4x32(c, s0, s1);
+    u64 S = 0;
+    const int tok = locate(weight, true, (u64)(c[0] >> 8), &S);
+    if (keep_out && tid == 0) { *n_out = (int)nkeep; *total_out = S; }
+    return tok;
+}
+
 // The row's n_part (max, sum of exp(v - max)) pairs -> sum of exp(v - M) over the whole row, M = the row's maximum (block-uniform, from the argmax
 // reduction).  The walk is the argmax's: kU requests in flight, branch-free (an index past the end re-reads the last pair and counts it 0 times).
 // A partial whose maximum is -inf holds sum 0 and exp(-inf - M) = 0; a row without one finite logit (M = -inf) returns 0 without forming an exponent.
@@ -428,6 +694,10 @@ NTTS_KERNEL(256) void sample_greedy_kernel(SampleArgs p) {
         const int step = (p.phase == SLOT_PREFILLED) ? 0 : p.sl.n_new[b];
         sampled = sample_topk_row(p.logits + (long)b * p.ld_logits, p.vocab, k, p.sl.temperature[b], p.sl.top_p[b], p.sl.min_p[b],
                                   p.sl.seed[2 * b], p.sl.seed[2 * b + 1], (unsigned int)step, pv, p.n_part, p.part_width);
+    } else if (k != 0) {                                            // top_k = -1: the whole vocabulary
+        const int step = (p.phase == SLOT_PREFILLED) ? 0 : p.sl.n_new[b];
+        sampled = sample_full_row(p.logits + (long)b * p.ld_logits, p.vocab, p.sl.temperature[b], p.sl.top_p[b], p.sl.min_p[b],
+                                  p.sl.seed[2 * b], p.sl.seed[2 * b + 1], (unsigned int)step, pv, p.n_part);
     }
     const bool lse = live && p.part_sum && p.out_logprobs;      // block-uniform
     float M = -INFINITY, S = 0.f;
@@ -440,9 +710,9 @@ NTTS_KERNEL(256) void sample_greedy_kernel(SampleArgs p) {
             if (sv[w] > best || (sv[w] == best && si[w] < bidx)) { best = sv[w]; bidx = si[w]; }
         SlotArrays& s = p.sl;
         if (live) {
-            int tok = k > 0 ? sampled : bidx;
+            int tok = k != 0 ? sampled : bidx;
             if (lse) {   // log softmax of the whole processed row at the chosen COLUMN: a greedy row's logit is M itself, a drawn one's is in the bf16 row
-                const float vt = (k > 0 && (unsigned int)tok < (unsigned int)p.vocab) ? bf2f(p.logits[(long)b * p.ld_logits + tok]) : M;
+                const float vt = (k != 0 && (unsigned int)tok < (unsigned int)p.vocab) ? bf2f(p.logits[(long)b * p.ld_logits + tok]) : M;
                 const int n0 = (p.phase == SLOT_PREFILLED) ? 0 : s.n_new[b];
                 p.out_logprobs[(long)b * s.out_stride + n0] = (vt - M) - logf(S);
             }

@@ -198,6 +198,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "ntts_k_launch_chain_probe": (C.c_int, [i32, i32, i32, i32, C.POINTER(C.c_double)]),
         "ntts_k_sample_probe": (C.c_int, [p, i64, i32, i32, i32, C.POINTER(i32), C.POINTER(f32), C.POINTER(f32), C.POINTER(f32),
                                           C.POINTER(C.c_uint64), i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
+        "ntts_k_sample_full_probe": (C.c_int, [p, i64, i32, i32, i32, C.POINTER(f32), C.POINTER(f32), C.POINTER(f32), C.POINTER(C.c_uint64), i32,
+                                               C.POINTER(i32), C.POINTER(i32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
         "ntts_k_head_penalty_probe": (C.c_int, [p, p, i32, i32, i32, i32, i32, f32, C.POINTER(C.c_uint32), C.POINTER(f32), C.POINTER(i32),
                                                 C.POINTER(f32), C.POINTER(C.c_uint16), C.POINTER(f32), C.POINTER(i32), i32, C.POINTER(i32),
                                                 C.POINTER(i32)]),
@@ -272,7 +274,8 @@ class Sampling:
     """Keyword arguments of the reference's generate() call (ref:neutts/neutts.py:338-347), plus generate()'s own top_p / min_p (off -- 1.0 / 0.0 --
     in that call): TopPLogitsWarper / MinPLogitsWarper behind top-k, in transformers' order (include/neutts_hip.h: ntts_sampling).
     repetition_penalty / prompt_ignore_length (ABI 11): generate()'s `repetition_penalty` (1.0 = off, the reference's value) and
-    RepetitionPenaltyLogitsProcessor's `prompt_ignore_length`; the penalty applies to greedy and sampled requests alike."""
+    RepetitionPenaltyLogitsProcessor's `prompt_ignore_length`; the penalty applies to greedy and sampled requests alike.
+    top_k = TOP_K_OFF (-1): no top-k cut -- temperature, top_p and min_p act on the whole vocabulary (transformers' top_k=0 / None)."""
     max_length: int = 2048
     min_new_tokens: int = 50
     eos_token_id: int = 0
@@ -291,6 +294,7 @@ class Sampling:
 
 
 SAMPLE_CAP = 512                 # candidates the device sampler keeps (csrc/kernels/sample.h kSampleCap)
+TOP_K_OFF = -1                   # Sampling.top_k: no top-k cut, sample over the whole vocabulary (include/neutts_hip.h NTTS_TOP_K_OFF)
 
 
 def sample_probe(lib, logits_ptr: int, ld_logits: int, rows: int, vocab: int, group_width: int, top_k, temperature, top_p, min_p, seed,
@@ -311,6 +315,27 @@ def sample_probe(lib, logits_ptr: int, ld_logits: int, rows: int, vocab: int, gr
     if rc != 0:
         raise NeuTTSHipError(rc, "ntts_k_sample_probe")
     return tok, [ids[r, : n[r]].copy() for r in range(rows)]
+
+
+def sample_full_probe(lib, logits_ptr: int, ld_logits: int, rows: int, vocab: int, group_width: int, temperature, top_p, min_p, seed, step: int):
+    """ntts_k_sample_full_probe: the engine's whole-vocabulary token choice (top_k = TOP_K_OFF) on `rows` DEVICE bf16 logits rows; parameters per
+    row (scalars are broadcast).  group_width 0: the row's maximum from a pass over the row, else from the maxima of groups of that many columns
+    (the results do not depend on it).  Returns (tokens [rows], survivor counts [rows], survivor bitmaps uint32 [rows][(vocab + 31) // 32] --
+    bit c & 31 of word c >> 5 --, total integer masses uint64 [rows])."""
+    def arr(v, dt):
+        return np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=dt), (rows,)))
+    t, tp, mp, sd = arr(temperature, np.float32), arr(top_p, np.float32), arr(min_p, np.float32), arr(seed, np.uint64)
+    tok = np.zeros(rows, dtype=np.int32)
+    n = np.zeros(rows, dtype=np.int32)
+    keep = np.zeros((rows, (vocab + 31) // 32), dtype=np.uint32)
+    total = np.zeros(rows, dtype=np.uint64)
+    i32p, f32p = C.POINTER(C.c_int32), C.POINTER(C.c_float)
+    rc = lib.ntts_k_sample_full_probe(C.c_void_p(logits_ptr), ld_logits, rows, vocab, group_width, t.ctypes.data_as(f32p), tp.ctypes.data_as(f32p),
+                                      mp.ctypes.data_as(f32p), sd.ctypes.data_as(C.POINTER(C.c_uint64)), step, tok.ctypes.data_as(i32p),
+                                      n.ctypes.data_as(i32p), keep.ctypes.data_as(C.POINTER(C.c_uint32)), total.ctypes.data_as(C.POINTER(C.c_uint64)))
+    if rc != 0:
+        raise NeuTTSHipError(rc, "ntts_k_sample_full_probe")
+    return tok, n, keep, total
 
 
 HEAD_VARIANTS = {"64x64": 0, "128x128": 1, "256x256": 2, "256x288": 4, "gemv": 8}     # ntts_k_head_penalty_probe `variant`

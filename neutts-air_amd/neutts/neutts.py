@@ -153,8 +153,8 @@ def load_audio_16k(path) -> np.ndarray:
 
 def _check_sampling(top_k, temperature, top_p, min_p, who: str = "") -> None:
     """The ranges transformers' warpers accept (TopK / Temperature / TopP / MinPLogitsWarper); ValueError before anything reaches the engine."""
-    if isinstance(top_k, bool) or not isinstance(top_k, (int, np.integer)) or top_k < 1:
-        raise ValueError(f"{who}top_k must be an integer >= 1 (got {top_k!r})")
+    if isinstance(top_k, bool) or not isinstance(top_k, (int, np.integer)) or (top_k < 1 and top_k != _hip.TOP_K_OFF):
+        raise ValueError(f"{who}top_k must be an integer >= 1, or -1 for the whole vocabulary (got {top_k!r})")
     for name, v in (("temperature", temperature), ("top_p", top_p), ("min_p", min_p)):
         if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
             raise ValueError(f"{who}{name} must be a number (got {v!r})")
