@@ -64,6 +64,17 @@ struct ArenaShare {
 };
 static long long now_ns() { return std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
+// The per-request and per-call choices a captured decode step bakes: the gang shape, context-split attention, and whether the lm_head and the sampling
+// kernel get the bf16 logits rows (a sampling request is live), the seen bitmap (a penalised one is) and the partial sums of exp (log-probabilities on)
+struct StepKey {
+    bool shape, split, has_logits, has_seen, has_lse;
+    int index() const { return shape | split << 1 | has_logits << 2 | has_seen << 3 | has_lse << 4; }
+};
+struct StepGraph {
+    hipGraphExec_t exec = nullptr;
+    bool tried = false;
+};
+
 struct ntts_backbone {
     ntts_backbone_config cfg{};
     int device = 0;
@@ -130,10 +141,9 @@ struct ntts_backbone {
     bf16_t* logits_bf16 = nullptr;   // [B][ldl] processed logits for the top-k sampler (allocated on first sampling request)
     long ldl = 0;
     int n_sampling = 0;              // running slots with do_sample=1
-    bool graph_has_logits = false;
     // Repetition penalty (ABI 11): one bit per lm_head column and slot (parking rows included), allocated with the first penalised request the way
     // logits_bf16 is with the first sampling one.  While no penalised request is live the lm_head and the sampling kernel get a null pointer and
-    // run exactly the kernels they ran before; the captured steps bake that choice (graph_has_seen), like graph_has_logits.
+    // run exactly the kernels they ran before (StepKey::has_seen, like has_logits).
     unsigned int* seen = nullptr;    // [B][seen_pitch]
     long seen_pitch = 0;             // words per row (gemm.h seen_pitch_for: the tiles' padding columns included)
     int* seen_cols = nullptr;        // [B * max_context] a prompt pass's columns to mark (sample.h seen_mark_prompt_kernel) ...
@@ -141,14 +151,12 @@ struct ntts_backbone {
     hipEvent_t seen_ev = nullptr;    //     that would stall the host until the prompt stream reaches the copy)
     bool seen_ev_used = false;
     int n_penalised = 0;             // live requests with repetition_penalty != 1
-    bool graph_has_seen = false;
     // Per-token log-probabilities (ntts_backbone_set_logprobs): while on, the lm_head runs the kernels whose epilogue also leaves the partial sums
     // of exp (gemm.h EPI_ARGMAX_LSE) and the sampling kernel records log softmax(row)[token] beside every id.  While off both get null pointers,
-    // nothing is allocated and the step is the step it was; the captured steps bake the choice (graph_has_lse).
+    // nothing is allocated and the step is the step it was (StepKey::has_lse).
     bool logprobs_on = false;
     float* part_sum = nullptr;       // [B][n_part_full], beside part_val
     float* out_logprobs = nullptr;   // [B][max_context], entry for entry beside sl.out_tokens
-    bool graph_has_lse = false;
     // Teacher-forced scoring (ntts_backbone_score): scratch of its own, allocated by the first score call and freed at destroy -- nothing of the decode
     // step's (part_val, xn_dec, the slot arrays) is written, and no captured step names any of it.  The partial arrays hold ONE chunk of scored rows.
     float *sc_part_val = nullptr, *sc_part_sum = nullptr, *sc_target_val = nullptr;   // [sc_chunk_cap][n_part of the score tile] x 2, [sc_chunk_cap]
@@ -181,10 +189,8 @@ struct ntts_backbone {
                                      // the engine itself at every decode call (engines of the same arena that decoded within kGangWindowNs) unless
     int gang_forced = 0;             // ntts_backbone_set_gang pinned it (> 0; tests, sweeps, profiling passes of one engine in the gang's shape)
     static constexpr long long kGangWindowNs = 50LL * 1000 * 1000;
-    hipGraphExec_t graph_shape[2] = {nullptr, nullptr};   // the captured step of the shape not in use (index = side-by-side shape?), kept across switches
-    bool graph_tried_shape[2] = {false, false};
-    int shape = 0;                   // 0 = single-chain shape, 1 = side-by-side shape (what `graph` / `graph_tried` currently belong to)
-    int tall_env = -1, affine_env = -1;   // NTTS_TALL / NTTS_XCD_AFFINE when set (sweeps, tests): they win over the gang's defaults
+    int shape = 0;                   // 0 = single-chain shape, 1 = side-by-side shape (StepKey::shape)
+    int tall_env = -1, affine_env = -1, wstat_env = -1;   // NTTS_TALL / NTTS_XCD_AFFINE / NTTS_QKV_WSTAT when set (sweeps, tests): they win over the gang's defaults
     // WIDE decode step (round 6; max_batch >= 512, e.g. the four 256-utterance batches of the static benchmark as ONE 1024-row chain instead of
     // four 256-row chains side by side): every GEMM of the step sees M = 1024 -- a weight tile enters a CU's LDS once per 64-256 rows, not once per
     // chain -- at the price of one chain's launch boundaries.  Tiles per GEMM (NTTS_WIDE_* override; DESIGN.md section 4l has the sweep):
@@ -262,10 +268,23 @@ struct ntts_backbone {
     bool small_used[kSmallStages] = {};
     int small_next = 0;
 
-    hipGraphExec_t graph = nullptr;
-    hipGraphExec_t graph_split = nullptr;   // the small-batch step with context-split attention (long contexts)
-    bool graph_split_tried = false, split_active = false;
-    bool graph_tried = false, use_graph = true;
+    // The captured decode steps, one per StepKey (ntts_backbone_decode captures a key the first time it runs under it; a capture that failed
+    // is not tried again: that key's steps run eagerly).  A capture is kept while other keys run, so everything ELSE a step bakes has to stay
+    // what it was at capture time, or the call that changes it has to drop_graphs.  What a step bakes, and which call can change it:
+    //   the decode workspaces (h_dec, h_alt, xn_dec, qkv_dec, attn_dec, act_dec, slabs, slabs2, part_val, part_idx), the KV pool, the slot arrays,
+    //   block_table, step_meta, rope_rows, as_scores / as_stats / as_oslabs: allocated by create, freed by destroy -- no call.  ntts_backbone_activate,
+    //   release and the prompt passes change what these arrays HOLD, never where they are;
+    //   the weights, their fp8 scales and the host copies of the input scales (LayerW::xs, xs_head): fixed by finalize / adopt_arena / share_arena,
+    //   all three before the first decode call (share_arena, which moves the pointers, refuses an engine that is finalised or holds a capture);
+    //   logits: set_debug allocates and frees it -- drops;
+    //   head_r / shead_r, lr_*, n_part: set_logits_range -- drops;
+    //   logits_bf16 (+ ldl), seen (+ seen_pitch), part_sum and out_logprobs: allocated once, by the first sampling request, the first penalised
+    //   request and the first set_logprobs(1), and freed by destroy; WHETHER a step uses them is in its key (set_logprobs drops all the same);
+    //   the tile knobs (ks_o, ks_d, wide*, gu_tile, gu_128, head_tile, xcd_xps, xl_min_m, small, attn_split, dec_rows): create -- no call; tall,
+    //   xcd_affine and qkv_wstat follow the key's shape and knobs read at create (apply_gang_shape);
+    //   attn_tl / gemv_tl: null except inside the timeline calls, which capture nothing;  the stream: a capture replays on any stream.
+    StepGraph steps[32];
+    bool use_graph = true;
     hipEvent_t ev[4]{};
     // optional side stream for the prompt pass, restricted to a subset of the CUs (ntts_backbone_set_prefill_cu_mask): a prefill
     // on it leaves the other CUs to whatever else runs on the GPU -- another engine's decode steps, which are launch- and
@@ -325,9 +344,7 @@ static void apply_gang_shape(ntts_backbone* e) {
     e->xcd_affine = e->affine_env >= 0 ? e->affine_env : (B > 128 && !side_by_side ? 7 : 0);
     // QKV column blocks dealt to XCDs whenever the row-block placement is off for a gang (FETCH per launch 17.1 -> 6.1 MB, step -0.7 %:
     // profiles/r05g_*); NTTS_QKV_WSTAT = 0 / 1 overrides
-    const int ws = env_int("NTTS_QKV_WSTAT", -1);
-    e->qkv_wstat = ws >= 0 ? ws != 0 : side_by_side;
-    e->tall_xcd_split = env_int("NTTS_TALL_XCD_SPLIT", 1) != 0;
+    e->qkv_wstat = e->wstat_env >= 0 ? e->wstat_env != 0 : side_by_side;
 }
 
 extern "C" int ntts_backbone_create(const ntts_backbone_config* c, int device, ntts_backbone** out) {
@@ -529,6 +546,8 @@ extern "C" int ntts_backbone_create(const ntts_backbone_config* c, int device, n
     }
     e->xcd_xps = (D == 64 || D == 128 || D == 256 || D == 512) ? 8 / (D / 64) : 0;
     e->affine_env = env_int("NTTS_XCD_AFFINE", -1);
+    e->wstat_env = env_int("NTTS_QKV_WSTAT", -1);   // (read here like the two above, not at every shape switch: the other shape's captured step keeps what it baked)
+    e->tall_xcd_split = env_int("NTTS_TALL_XCD_SPLIT", 1) != 0;
     apply_gang_shape(e);
     e->head_tile = env_int("NTTS_HEAD_TILE", D > 128 ? (e->fp8 || e->wide ? 2 : 4) : D > 64 ? 1 : 0);   // (1024 rows: 256 x 256 424 us, 256 x 288 438)
     if (e->head_tile != 0 && e->head_tile != 1 && e->head_tile != 2 && e->head_tile != 4) e->head_tile = 1;
@@ -610,17 +629,24 @@ extern "C" int ntts_backbone_create(const ntts_backbone_config* c, int device, n
     return NTTS_OK;
 }
 
+static void drop_graphs(ntts_backbone* e) {
+    for (StepGraph& g : e->steps) {
+        if (g.exec) hipGraphExecDestroy(g.exec);
+        g = StepGraph{};
+    }
+}
+static bool holds_graph(const ntts_backbone* e) {
+    return std::any_of(std::begin(e->steps), std::end(e->steps), [](const StepGraph& g) { return g.exec != nullptr; });
+}
+
 extern "C" void ntts_backbone_destroy(ntts_backbone* e) {
     if (!e) return;
     hipSetDevice(e->device);
     hipDeviceSynchronize();
-    if (e->graph) hipGraphExecDestroy(e->graph);
-    if (e->graph_split) hipGraphExecDestroy(e->graph_split);
+    drop_graphs(e);
     if (e->calib) hipFree(e->calib);
     if (e->head_r) hipFree(e->head_r);
     if (e->shead_r) hipFree(e->shead_r);
-    for (hipGraphExec_t g : e->graph_shape)
-        if (g && g != e->graph) hipGraphExecDestroy(g);
     bool last_reader = true;
     if (e->share) { last_reader = e->share->refs.fetch_sub(1) == 1; if (last_reader) delete e->share; else e->share->last_decode_ns[e->share_idx].store(0); }
     void* bufs[] = {last_reader ? e->arena : nullptr, e->gu_map_gate, e->gu_map_up, e->kv, e->ibuf, e->h_dec, e->xn_dec, e->qkv_dec, e->attn_dec,
@@ -1026,7 +1052,7 @@ extern "C" int ntts_backbone_adopt_arena(ntts_backbone* e) {
 extern "C" int ntts_backbone_share_arena(ntts_backbone* e, ntts_backbone* donor) {
     if (!e || !donor || e == donor) return NTTS_EINVAL;
     if (!donor->finalized) return fail(e, NTTS_ESTATE, "share_arena: the donor engine is not finalised");
-    if (e->finalized || e->arena_shared || e->graph || e->graph_split) return fail(e, NTTS_ESTATE, "share_arena: this engine already holds weights");
+    if (e->finalized || e->arena_shared || holds_graph(e)) return fail(e, NTTS_ESTATE, "share_arena: this engine already holds weights");
     const ntts_backbone_config &a = e->cfg, &b = donor->cfg;
     if (e->device != donor->device || e->arena_elems != donor->arena_elems || a.vocab_size != b.vocab_size || a.hidden_size != b.hidden_size ||
         a.intermediate_size != b.intermediate_size || a.num_layers != b.num_layers || a.num_heads != b.num_heads ||
@@ -1055,17 +1081,6 @@ extern "C" int ntts_backbone_share_arena(ntts_backbone* e, ntts_backbone* donor)
     if (rc) return rc;
     e->finalized = true;
     return NTTS_OK;
-}
-
-static void drop_graphs(ntts_backbone* e) {
-    for (hipGraphExec_t& g : e->graph_shape) {           // (the other shape's parked capture)
-        if (g && g != e->graph) hipGraphExecDestroy(g);
-        g = nullptr;
-    }
-    e->graph_tried_shape[0] = e->graph_tried_shape[1] = false;
-    if (e->graph) { hipGraphExecDestroy(e->graph); e->graph = nullptr; }
-    if (e->graph_split) { hipGraphExecDestroy(e->graph_split); e->graph_split = nullptr; }
-    e->graph_tried = e->graph_split_tried = false;
 }
 
 // Opt-in: the lm_head over the token ids [lo, hi) and `eos_id` only (ABI 8; SURVEY.md section 7 "hard parts").  Everything outside gets
@@ -1142,18 +1157,13 @@ extern "C" int ntts_backbone_read_amax(ntts_backbone* e, float* out, int32_t n) 
     return NTTS_OK;
 }
 
-// The decode shape for `chains` chains side by side, with that shape's captured step: both shapes keep their capture, so an engine that
+// The decode shape for `chains` chains side by side.  The shape is part of a captured step's key (StepKey), so an engine that
 // leaves a gang for a while (NeuTTS.infer on engine 0 of a gang: ADVICE r5) and comes back re-captures nothing.  Same arithmetic and the
 // same summation order per output element in both shapes (tests/test_gpu_parity_matrix.py asserts the logits rows bit-identical).
 static void use_shape_for(ntts_backbone* e, int chains) {
     const int B = e->dec_rows;
-    const int want = (chains >= 2 && B > 128 && B <= 256) ? 1 : 0;
     e->gang = chains;
-    if (want == e->shape) return;
-    e->graph_shape[e->shape] = e->graph; e->graph_tried_shape[e->shape] = e->graph_tried;
-    e->shape = want;
-    e->graph = e->graph_shape[want]; e->graph_tried = e->graph_tried_shape[want];
-    e->graph_shape[want] = nullptr;
+    e->shape = (chains >= 2 && B > 128 && B <= 256) ? 1 : 0;
     apply_gang_shape(e);
 }
 // engines of this arena with a decode call inside the window, this one included
@@ -1238,6 +1248,15 @@ static void gemm_large(ntts_backbone* e, const GemmArgs& a, hipStream_t st) {
     gemm_launch<2, 2, 4, EPI, 2>(a, 1, st);
 }
 
+// what the lm_head's epilogue gets, whichever kernel family runs it (GemmArgs: the tiles, GemvArgs: the small-batch step)
+template <class Args>
+static void lm_head_epilogue_args(const ntts_backbone* e, Args& a, bool keep_logits) {
+    a.part_val = e->part_val; a.part_idx = e->part_idx; a.mask_eos = e->sl.mask_eos;
+    a.logits = keep_logits ? e->logits : nullptr; a.ld_logits = e->cfg.vocab_size;
+    a.logits_bf16 = (keep_logits && e->n_sampling > 0) ? e->logits_bf16 : nullptr; a.ld_logits_bf16 = e->ldl;
+    if (e->n_penalised > 0) { a.seen = e->seen; a.seen_pitch = e->seen_pitch; a.rep_pen = e->sl.rep_pen; }
+    if (e->logprobs_on) a.part_sum = e->part_sum;
+}
 static void ks_lm_head(ntts_backbone* e, bool keep_logits);
 // rows: e->dec_rows for a decode step; every slot (cfg.max_batch, parked ones included) for the first token behind a prompt pass
 static void k_lm_head(ntts_backbone* e, bool keep_logits, int rows) {
@@ -1246,11 +1265,7 @@ static void k_lm_head(ntts_backbone* e, bool keep_logits, int rows) {
     GemmArgs a = gemm_args(e, e->xn_dec, H, e->lr_rows ? e->head_r : e->embed_tm, H, nullptr, nullptr, 0, B, e->lr_rows ? e->lr_rows : V, H,
                            e->lr_rows ? e->shead_r : e->shead, e->xs_head);
     if (e->lr_rows) a.eos_col1 = e->lr_rows;          // compacted head: columns = [range | EOS]
-    a.part_val = e->part_val; a.part_idx = e->part_idx; a.mask_eos = e->sl.mask_eos;
-    a.logits = keep_logits ? e->logits : nullptr; a.ld_logits = V;
-    a.logits_bf16 = (keep_logits && e->n_sampling > 0) ? e->logits_bf16 : nullptr; a.ld_logits_bf16 = e->ldl;
-    if (e->n_penalised > 0) { a.seen = e->seen; a.seen_pitch = e->seen_pitch; a.rep_pen = e->sl.rep_pen; }
-    if (e->logprobs_on) a.part_sum = e->part_sum;
+    lm_head_epilogue_args(e, a, keep_logits);
     lm_head_launch(a, e->head_tile, e->fp8, e->stream);     // (gemm.h: the tile per head_tile, with or without the penalty / log-sum-exp epilogue)
 }
 
@@ -1317,7 +1332,8 @@ static void k_qkv(ntts_backbone* e, int i) {
     else qkv_rope_launch<false>(a, place, e->stream, e->qkv_wstat);
 }
 
-static void k_attn(ntts_backbone* e, int i) {
+// decode attention of layer i: what the tile path's and the small-batch step's launches share (attention output = o_proj's input: e4m3 in the fp8 model)
+static AttnDecodeArgs attn_decode_args(const ntts_backbone* e, int i) {
     const ntts_backbone_config& c = e->cfg;
     AttnDecodeArgs a{};
     a.qkv = e->qkv_dec; a.ld_qkv = e->NQKV; a.out = e->attn_dec; a.ld_out = c.num_heads * e->HD;
@@ -1325,18 +1341,24 @@ static void k_attn(ntts_backbone* e, int i) {
     a.block_table = e->block_table; a.max_pages = e->max_pages; a.pos = e->sl.pos; a.state = e->sl.state;
     a.rope_cos = e->rope_cos; a.rope_sin = e->rope_sin; a.nh = c.num_heads; a.nkv = c.num_kv_heads;
     a.tl = e->attn_tl;
-    if (e->HD == 128) { attn_decode_launch_hd128(a, e->dec_rows, e->stream, c.max_context); return; }
+    if (e->fp8) a.out_fp8_inv = 1.0f / e->layers[i].xs[1];
+    return a;
+}
+// context-split attention (+ the tile path's combine pass): the chunk scores, statistics and output slabs around `a`
+static AttnSplitArgs attn_split_args(const ntts_backbone* e, const AttnDecodeArgs& a) {
+    AttnSplitArgs q{};
+    q.a = a; q.scores = e->as_scores; q.ld_scores = e->cfg.max_context + 16; q.stats = e->as_stats; q.oslabs = e->as_oslabs; q.nsplit = e->attn_split;
+    q.a.slab_rows = e->dec_rows;
+    return q;
+}
+
+static void k_attn(ntts_backbone* e, int i, bool split) {
+    AttnDecodeArgs a = attn_decode_args(e, i);
+    if (e->HD == 128) { attn_decode_launch_hd128(a, e->dec_rows, e->stream, e->cfg.max_context); return; }
     a.xcd_rows = ((e->xcd_affine & 4) && !e->attn_tl) ? e->xcd_xps : 0;
     a.nt_pages = e->wide && !e->attn_tl;
-    if (e->fp8) a.out_fp8_inv = 1.0f / e->layers[i].xs[1];   // attention output = o_proj's input
-    if (e->split_active && !e->attn_tl) {       // long contexts below 2 workgroups per CU: context-split attention + combine
-        AttnSplitArgs q{};
-        q.a = a; q.scores = e->as_scores; q.ld_scores = c.max_context + 16; q.stats = e->as_stats; q.oslabs = e->as_oslabs; q.nsplit = e->attn_split;
-        q.a.slab_rows = e->dec_rows;
-        attn_split_launch(q, e->dec_rows, e->stream, true);
-        return;
-    }
-    attn_decode_launch(a, e->dec_rows, e->stream, c.max_context);
+    if (split && !e->attn_tl) attn_split_launch(attn_split_args(e, a), e->dec_rows, e->stream, true);   // long contexts below 2 workgroups per CU: + combine
+    else attn_decode_launch(a, e->dec_rows, e->stream, e->cfg.max_context);
 }
 
 static void k_o_proj(ntts_backbone* e, int i) {
@@ -1439,28 +1461,16 @@ static void ks_qkv(ntts_backbone* e, int i) {
     a.tl = e->gemv_tl;
     gemv_qkv_rope_launch(a, e->stream);
 }
-static void ks_attn(ntts_backbone* e, int i) {
-    const ntts_backbone_config& c = e->cfg;
-    AttnDecodeArgs a{};
-    a.qkv = e->qkv_dec; a.ld_qkv = e->NQKV; a.out = e->attn_dec; a.ld_out = c.num_heads * 64;
+static void ks_attn(ntts_backbone* e, int i, bool split) {
+    AttnDecodeArgs a = attn_decode_args(e, i);     // (head_dim is 64 on this path)
     a.slab_rows = e->dec_rows;
-    a.kpool = e->kv + (size_t)i * e->layer_stride; a.vpool = a.kpool + e->kv_half;
-    a.block_table = e->block_table; a.max_pages = e->max_pages; a.pos = e->sl.pos; a.state = e->sl.state;
-    a.rope_cos = e->rope_cos; a.rope_sin = e->rope_sin; a.nh = c.num_heads; a.nkv = c.num_kv_heads;
-    a.tl = e->attn_tl;
-    if (e->fp8) a.out_fp8_inv = 1.0f / e->layers[i].xs[1];       // attention output = o_proj's e4m3 input
-    if (e->split_active && !e->attn_tl) {
-        AttnSplitArgs q{};
-        q.a = a; q.scores = e->as_scores; q.ld_scores = c.max_context + 16; q.stats = e->as_stats; q.oslabs = e->as_oslabs; q.nsplit = e->attn_split;
-        attn_split_launch(q, e->dec_rows, e->stream);
-        return;
-    }
-    attn_decode_launch_small(a, e->dec_rows, e->stream);
+    if (split && !e->attn_tl) attn_split_launch(attn_split_args(e, a), e->dec_rows, e->stream);
+    else attn_decode_launch_small(a, e->dec_rows, e->stream);
 }
-static void ks_o_proj(ntts_backbone* e, int i) {
+static void ks_o_proj(ntts_backbone* e, int i, bool split) {
     const int QD = e->cfg.num_heads * 64;
     GemvArgs a = gemv_args(e, e->attn_dec, QD, e->layers[i].wo, QD, e->slabs, e->H, e->H, QD, e->layers[i].so, e->layers[i].xs[1]);
-    if (e->split_active && !e->attn_tl) { a.xslabs = e->as_oslabs; a.n_xslab = e->attn_split; }   // context-split attention: chunk outputs summed here
+    if (split && !e->attn_tl) { a.xslabs = e->as_oslabs; a.n_xslab = e->attn_split; }   // context-split attention: chunk outputs summed here
     if (e->fp8) gemv_launch<EPI_SPLITK, false, 4, true>(a, ntts_backbone::kSksO, e->stream);
     else gemv_launch<EPI_SPLITK, false>(a, ntts_backbone::kSksO, e->stream);
 }
@@ -1492,20 +1502,16 @@ static void ks_lm_head(ntts_backbone* e, bool keep_logits) {
     GemvArgs a = gemv_args(e, e->xn_dec, H, e->lr_rows ? e->head_r : e->embed_tm, H, nullptr, 0, e->lr_rows ? (e->lr_rows + 15) / 16 * 16 : V, H,
                            e->lr_rows ? e->shead_r : e->shead, e->xs_head);
     if (e->lr_rows) { a.eos_col1 = e->lr_rows; a.n_valid = e->lr_rows; }   // compacted head: columns = [range | EOS | padding to 16]
-    a.part_val = e->part_val; a.part_idx = e->part_idx; a.mask_eos = e->sl.mask_eos;
-    a.logits = keep_logits ? e->logits : nullptr; a.ld_logits = V;
-    a.logits_bf16 = (keep_logits && e->n_sampling > 0) ? e->logits_bf16 : nullptr; a.ld_logits_bf16 = e->ldl;
-    if (e->n_penalised > 0) { a.seen = e->seen; a.seen_pitch = e->seen_pitch; a.rep_pen = e->sl.rep_pen; }
-    if (e->logprobs_on) a.part_sum = e->part_sum;
+    lm_head_epilogue_args(e, a, keep_logits);
     lm_head_gemv_launch(a, e->fp8, e->stream);
 }
 
-static void decode_step_small(ntts_backbone* e) {
+static void decode_step_small(ntts_backbone* e, bool split) {
     k_step_meta(e);
     for (int i = 0; i < e->cfg.num_layers; ++i) {
         ks_qkv(e, i);
-        ks_attn(e, i);
-        ks_o_proj(e, i);
+        ks_attn(e, i, split);
+        ks_o_proj(e, i, split);
         ks_gate_up(e, i);
         ks_down(e, i);
     }
@@ -1513,8 +1519,9 @@ static void decode_step_small(ntts_backbone* e) {
     lm_head_and_sample(e, SLOT_RUNNING);
 }
 
-static void decode_step(ntts_backbone* e) {
-    if (e->small) { decode_step_small(e); return; }
+// split: this step's attention is the context-split one (ntts_backbone_decode decides per step; StepKey::split)
+static void decode_step(ntts_backbone* e, bool split) {
+    if (e->small) { decode_step_small(e, split); return; }
     const ntts_backbone_config& c = e->cfg;
     const int B = e->dec_rows, H = e->H, F = e->F, QD = c.num_heads * e->HD;
     NormArgs n0{};
@@ -1530,7 +1537,7 @@ static void decode_step(ntts_backbone* e) {
     for (int i = 0; i < c.num_layers; ++i) {
         const bool last = i + 1 == c.num_layers;
         k_qkv(e, i);
-        k_attn(e, i);
+        k_attn(e, i, split);
         k_o_proj(e, i);
         k_add_norm(e, QD, e->ks_o, e->layers[i].ln2, e->h_dec, e->xn_dec, e->layers[i].xs[2], 1);
         k_gate_up(e, i);
@@ -1538,6 +1545,24 @@ static void decode_step(ntts_backbone* e) {
         k_add_norm(e, F, e->ks_d, last ? e->final_norm : e->layers[i + 1].ln1, e->h_dec, e->xn_dec, last ? e->xs_head : e->layers[i + 1].xs[0], 2);
     }
     lm_head_and_sample(e, SLOT_RUNNING);
+}
+
+// One launch of the step's kernel `which` on layer i outside a step, on the engine's path (small-batch or tiles), without context-split attention:
+// 0 attention, 1 QKV (+ RoPE + K append; small-batch: incl. the fused slab-reduce + residual + RMSNorm prologue), 2 o_proj, 3 gate/up (small-batch:
+// incl. its fused prologue), 4 down_proj, 5 lm_head, 6 the norm pass (small-batch: the final norm; tiles: the one behind o_proj, into the prompt
+// pass's scratch rows).  ntts_backbone_time_kernel's numbering; the timelines use it too.
+static void launch_step_kernel(ntts_backbone* e, int which, int i) {
+    const bool s = e->small;
+    switch (which) {
+        case 0: s ? ks_attn(e, i, false) : k_attn(e, i, false); break;
+        case 1: s ? ks_qkv(e, i) : k_qkv(e, i); break;
+        case 2: s ? ks_o_proj(e, i, false) : k_o_proj(e, i); break;
+        case 3: s ? ks_gate_up(e, i) : k_gate_up(e, i); break;
+        case 4: s ? ks_down(e, i) : k_down(e, i); break;
+        case 5: k_lm_head(e, false, e->dec_rows); break;
+        case 6: s ? ks_final_norm(e) : k_add_norm(e, e->cfg.num_heads * e->HD, e->ks_o, e->layers[i].ln2, e->o_pf, e->xn_pf, e->layers[i].xs[2]); break;
+        default: break;
+    }
 }
 
 static int alloc_pages(ntts_backbone* e, HostSlot& s, int tokens) {
@@ -2138,46 +2163,35 @@ extern "C" int ntts_backbone_decode(ntts_backbone* e, int32_t n_steps) {
         const int nt = (int)trip.size() / 3;
         NTTS_LAUNCH((bt_update_kernel), dim3((nt + 63) / 64), dim3(64), st, (const int*)e->meta_dev, nt, e->block_table, e->max_pages);
     }
-    if ((e->graph || e->graph_split || e->graph_shape[0] || e->graph_shape[1]) &&
-        (e->graph_has_logits != (e->n_sampling > 0) || e->graph_has_seen != (e->n_penalised > 0) || e->graph_has_lse != e->logprobs_on))   // the step's launch arguments (and the lm_head's kernel) changed:
-        drop_graphs(e);                                                                             // every capture is stale
-    // small-batch path: steps whose longest context has reached attn_split_ctx run the context-split attention (its own graph)
+    // steps whose longest context has reached attn_split_ctx run the context-split attention (a key of its own)
     const bool can_split = e->attn_split > 0 && !e->attn_tl;
     auto wants_split = [&](int step) { return can_split && ctx_now + step >= e->attn_split_ctx; };
-    auto capture = [&](int steps, hipGraphExec_t* out) {
-        hipGraph_t g = nullptr;
-        if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-            for (int k = 0; k < steps; ++k) decode_step(e);
-            if (hipStreamEndCapture(st, &g) == hipSuccess && g) {
-                if (hipGraphInstantiate(out, g, nullptr, nullptr, 0) != hipSuccess) *out = nullptr;
-                hipGraphDestroy(g);
+    // the captured step for the engine's state at this call (ntts_backbone::steps), captured now if this key has not been tried; null = run the step eagerly
+    auto step_graph = [&](bool split) -> hipGraphExec_t {
+        const StepKey key{e->shape != 0, split, e->n_sampling > 0, e->n_penalised > 0, e->logprobs_on};
+        StepGraph& sg = e->steps[key.index()];
+        if (e->use_graph && !sg.tried) {
+            sg.tried = true;
+            hipGraph_t g = nullptr;
+            if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) == hipSuccess) {
+                decode_step(e, split);   // several steps per graph were measured: -0.3 % per step (profiles/r02a_sweep_nt_graphsteps.jsonl), not kept
+                if (hipStreamEndCapture(st, &g) == hipSuccess && g) {
+                    if (hipGraphInstantiate(&sg.exec, g, nullptr, nullptr, 0) != hipSuccess) sg.exec = nullptr;
+                    hipGraphDestroy(g);
+                }
             }
+            (void)hipGetLastError();
         }
-        (void)hipGetLastError();
+        return sg.exec;
     };
-    if (e->use_graph && can_split && wants_split(n_steps - 1) && !e->graph_split_tried) {
-        e->graph_split_tried = true;
-        e->graph_has_logits = e->n_sampling > 0;
-        e->graph_has_seen = e->n_penalised > 0;
-        e->graph_has_lse = e->logprobs_on;
-        e->split_active = true;
-        capture(1, &e->graph_split);
-        e->split_active = false;
-    }
-    if (e->use_graph && !e->graph_tried) {
-        e->graph_tried = true;
-        e->graph_has_logits = e->n_sampling > 0;
-        e->graph_has_seen = e->n_penalised > 0;
-        e->graph_has_lse = e->logprobs_on;
-        capture(1, &e->graph);   // several steps per graph were measured: -0.3 % per step (profiles/r02a_sweep_nt_graphsteps.jsonl), not kept
-    }
+    // both captures before the first replay (and outside the timed window): the split one as soon as the call's last step wants it
+    const hipGraphExec_t gx_split = wants_split(n_steps - 1) ? step_graph(true) : nullptr;
+    const hipGraphExec_t gx_plain = wants_split(0) ? nullptr : step_graph(false);
     HIPCHK(e, hipEventRecord(e->ev[2], st));
-    for (int s = 0; s < n_steps;) {
+    for (int s = 0; s < n_steps; ++s) {
         const bool sp = wants_split(s);
-        hipGraphExec_t gx = sp ? e->graph_split : e->graph;
-        if (gx) HIPCHK(e, hipGraphLaunch(gx, st));
-        else { e->split_active = sp; decode_step(e); e->split_active = false; }
-        ++s;
+        if (hipGraphExec_t gx = sp ? gx_split : gx_plain) HIPCHK(e, hipGraphLaunch(gx, st));
+        else decode_step(e, sp);
     }
     HIPCHK(e, hipEventRecord(e->ev[3], st));
     e->have_dec_time = true;
@@ -2633,15 +2647,13 @@ extern "C" int ntts_backbone_attn_timeline(ntts_backbone* e, int32_t layer, uint
     HIPCHK(e, hipMalloc(&buf.p, n * 8));
     unsigned long long* tl = (unsigned long long*)buf.p;
     HIPCHK(e, hipMemsetAsync(tl, 0, n * 8, e->stream));
-    auto attn = [&](int i) { if (e->small) ks_attn(e, i); else k_attn(e, i); };
-    auto qkv = [&](int i) { if (e->small) ks_qkv(e, i); else k_qkv(e, i); };
     k_step_meta(e);
     // the fused QKV kernel writes this step's K entry and the q | v row the attention kernel reads (the real step runs it first, too)
-    qkv((layer + 1) % e->cfg.num_layers);
-    qkv(layer);
-    attn((layer + 1) % e->cfg.num_layers);     // another layer first: this launch is neither the first nor cache-warm
+    launch_step_kernel(e, 1, (layer + 1) % e->cfg.num_layers);
+    launch_step_kernel(e, 1, layer);
+    launch_step_kernel(e, 0, (layer + 1) % e->cfg.num_layers);     // another layer first: this launch is neither the first nor cache-warm
     e->attn_tl = tl;
-    attn(layer);
+    launch_step_kernel(e, 0, layer);
     e->attn_tl = nullptr;
     HIPCHK(e, hipStreamSynchronize(e->stream));
     HIPCHK(e, hipMemcpy(out, tl, n * 8, hipMemcpyDeviceToHost));
@@ -2659,14 +2671,10 @@ extern "C" int ntts_backbone_gemv_timeline(ntts_backbone* e, int32_t which, int3
     HIPCHK(e, hipMalloc(&buf.p, n * 8));
     unsigned long long* tl = (unsigned long long*)buf.p;
     HIPCHK(e, hipMemsetAsync(tl, 0, n * 8, e->stream));
-    auto run = [&](int i) {
-        if (e->small) { if (which == 1) ks_qkv(e, i); else if (which == 2) ks_o_proj(e, i); else if (which == 3) ks_gate_up(e, i); else ks_down(e, i); }
-        else { if (which == 1) k_qkv(e, i); else if (which == 2) k_o_proj(e, i); else if (which == 3) k_gate_up(e, i); else k_down(e, i); }
-    };
     if (which == 1) k_step_meta(e);
-    run((layer + 1) % e->cfg.num_layers);      // another layer first: this launch is neither the first nor cache-warm
+    launch_step_kernel(e, which, (layer + 1) % e->cfg.num_layers);      // another layer first: this launch is neither the first nor cache-warm
     e->gemv_tl = tl;
-    run(layer);
+    launch_step_kernel(e, which, layer);
     e->gemv_tl = nullptr;
     HIPCHK(e, hipStreamSynchronize(e->stream));
     HIPCHK(e, hipMemcpy(out, tl, n * 8, hipMemcpyDeviceToHost));
@@ -2705,31 +2713,6 @@ extern "C" int ntts_backbone_time_kernel(ntts_backbone* e, int32_t which, int32_
     // Every replay works on the NEXT layer's weights / KV pool, as consecutive launches of this kernel do inside the
     // decode step: one layer's operands (84 MB of KV at batch 256) would sit in the 256 MB Infinity Cache when replayed
     // alone, all layers together (2 GB) do not -- so the timing below is HBM-cold like the in-graph launches.
-    auto run = [&](int k, int i) {
-        if (e->small) {
-            switch (k) {
-                case 0: ks_attn(e, i); break;
-                case 1: ks_qkv(e, i); break;         // incl. the fused slab-reduce + residual + RMSNorm prologue
-                case 2: ks_o_proj(e, i); break;
-                case 3: ks_gate_up(e, i); break;     // incl. its fused prologue
-                case 4: ks_down(e, i); break;
-                case 5: k_lm_head(e, false, e->dec_rows); break;
-                case 6: ks_final_norm(e); break;
-                default: break;
-            }
-            return;
-        }
-        switch (k) {
-            case 0: k_attn(e, i); break;                        // paged decode attention (+RoPE, +KV append)
-            case 1: k_qkv(e, i); break;
-            case 2: k_o_proj(e, i); break;
-            case 3: k_gate_up(e, i); break;
-            case 4: k_down(e, i); break;
-            case 5: k_lm_head(e, false, e->dec_rows); break;
-            case 6: k_add_norm(e, QD, e->ks_o, e->layers[i].ln2, e->o_pf, e->xn_pf, e->layers[i].xs[2]); break;   // scratch outputs
-            default: break;
-        }
-    };
     // algorithmic bytes per launch: the weights of the GEMM + its activations in/out; for attention K/V only
     const int kso = e->small ? ntts_backbone::kSksO : e->ks_o, ksd = e->small ? ntts_backbone::kSksD : e->ks_d;
     switch (which) {
@@ -2751,10 +2734,10 @@ extern "C" int ntts_backbone_time_kernel(ntts_backbone* e, int32_t which, int32_
     if (which == 6 && B > e->Tmax) return fail(e, NTTS_EINVAL, "scratch too small");
     k_step_meta(e);   // the fused QKV kernel appends at the CURRENT position (not yet written), like the step it replays
     if (which == 0)
-        for (int i = 0; i < L; ++i) run(1, i);   // every layer's K entry + q | v row for the attention replays (untimed)
-    run(which, L - 1);  // warm (code, TLBs); the timed replays start from layer 0
+        for (int i = 0; i < L; ++i) launch_step_kernel(e, 1, i);   // every layer's K entry + q | v row for the attention replays (untimed)
+    launch_step_kernel(e, which, L - 1);  // warm (code, TLBs); the timed replays start from layer 0
     HIPCHK(e, hipEventRecord(e->ev[2], st));
-    for (int i = 0; i < iters; ++i) run(which, i % L);
+    for (int i = 0; i < iters; ++i) launch_step_kernel(e, which, i % L);
     HIPCHK(e, hipEventRecord(e->ev[3], st));
     HIPCHK(e, hipStreamSynchronize(st));
     float ms = 0;

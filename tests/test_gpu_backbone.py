@@ -46,6 +46,49 @@ def test_small_walk_exact(lib, graph, monkeypatch):
         assert_walk_exact(ids, z[f"bf16_ids_{u}"].tolist())
 
 
+@pytest.mark.parametrize("split", [False, True], ids=["plain", "split-attention"])
+def test_captured_steps_follow_the_sampler_state(lib, split, monkeypatch):
+    """The captured decode steps are kept per (shape, split attention, sampling rows, seen bitmap, log-probabilities): a greedy walk in slot 0
+    over 30 steps in several decode calls, while a sampling request (slot 1) and later a penalised one (slot 2) enter, finish after 8 steps and
+    are released -- n_sampling 0 -> 1 -> 0, then n_penalised 0 -> 1 -> 0 across calls, each flip another key and each return an earlier capture
+    replayed.  Every slot's ids are the same with and without graphs, and slot 0's are HF's whatever its neighbours do.  Second case: the
+    context-split attention from context S + 10 on, a threshold slot 0 crosses INSIDE the first call the sampling request is live in (two eager
+    or replayed steps on either side of it), so the split keys meet the sampler's."""
+    z, cfg, w = load_fixture("backbone_small_walk")
+    S, eos, N0, NV = int(z["s_len"]), int(z["eos"]), 31, 9
+    if split:
+        monkeypatch.setenv("NTTS_ATTN_SPLIT", "2")
+        monkeypatch.setenv("NTTS_ATTN_SPLIT_CTX", str(S + 10))
+
+    def script(no_graph):
+        monkeypatch.setenv("NTTS_NO_GRAPH", no_graph)                       # (read at create)
+        eng = make_engine(cfg, w, lib, max_batch=4, max_context=160, bf16_upload=True)
+        out = {}
+
+        def visit(slot, **kw):                                              # a request that lives for 8 of slot 0's steps
+            samp = _hip.Sampling(max_length=S + NV, min_new_tokens=NV, eos_token_id=eos, **kw)
+            eng.prefill([br.synthetic_prompt(cfg, slot, S)], [slot], [samp])
+            eng.decode(4)
+            eng.decode(4)
+            out[slot], fin = eng.read(slot)
+            assert fin and len(out[slot]) == NV
+            eng.release(slot)
+        eng.prefill([br.synthetic_prompt(cfg, 0, S)], [0], [_hip.Sampling(max_length=S + N0, min_new_tokens=N0, eos_token_id=eos, do_sample=False)])
+        eng.decode(4)
+        eng.decode(4)
+        visit(1, do_sample=True, top_k=8, seed=1234)
+        eng.decode(3)
+        visit(2, do_sample=False, repetition_penalty=1.3)
+        eng.decode(3)
+        out[0], fin = eng.read(0)
+        assert fin
+        eng.close()
+        return out
+    eager, graphs = script("1"), script("0")
+    assert graphs == eager
+    assert_walk_exact(graphs[0], z["bf16_ids_0"][:N0].tolist())
+
+
 @pytest.mark.parametrize("knobs", [
     {"NTTS_HEAD_TILE": "0"},                                             # 64 x 64 skinny tile (the default up to batch 64)
     {"NTTS_HEAD_TILE": "1"},                                             # 128 x 128
@@ -510,8 +553,8 @@ def test_air_golden_slot_in_a_full_ragged_dirty_batch(air, chains):
                 eng.prefill(ps[i:j], slots[i:j], [samp(p, N + extra) for p in ps[i:j]])
                 i = j
         fill(50_000, 4)
-        junk = br.synthetic_prompt(cfg, 777, S)
-        eng.prefill([junk], [137], [samp(junk, N + 4)])
+        junk = br.synthetic_prompt(cfg, 777, S)      # (a SAMPLING request: while it lives the steps run under another key of this shape; (1)'s capture returns with the golden run)
+        eng.prefill([junk], [137], [_hip.Sampling(max_length=S + N + 4, min_new_tokens=N + 4, eos_token_id=eos, do_sample=True, top_k=8, seed=777)])
         eng.decode(N + 2)
         eng.release_many(list(range(256)))
         fill(60_000, 0)
