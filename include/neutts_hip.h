@@ -664,7 +664,8 @@ int ntts_encoder_last_timing(ntts_encoder* e, float* ms);
 /* DEVICE pointers, bf16 unless noted, row-major; run on the NULL stream and block).           */
 /* ------------------------------------------------------------------------------------------ */
 /* C[M,N] = A[M,K] (lda) * W[N,K]^T (+ bias[N]); fp32 accumulate on MFMA, one RNE rounding to bf16.
- * variant: 0 = auto, 1 = 128x128 tile, 2 = 64x64 tile, 3 = 64x64 split-K slabs + reduce, 4 = 256x256 tile. */
+ * variant: 0 = auto, 1 = 128x128 tile, 2 = 64x64 tile, 3 = 64x64 split-K slabs + reduce, 4 = 256x256 tile,
+ * 5 / 6 = 256x256 / 128x128 on ring slots of K = 32, 7 = 256x288 natural-order tile, 8 = 320x192 tile (12 waves), 9 = 320x128 tile (8 waves). */
 int ntts_k_gemm_bf16(const void* A, int64_t lda, const void* W, const void* bias, void* C, int64_t ldc,
                      int32_t M, int32_t N, int32_t K, int32_t variant);
 /* fp8 probes (tests): out[i] = e4m3(clamp(in[i] * inv_scale, +-448)), round-to-nearest-even -- the conversion every fp8

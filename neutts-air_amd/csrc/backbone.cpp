@@ -199,7 +199,8 @@ struct ntts_backbone {
     bool wide = false;
     int wide_qkv = 2, wide_o = 1, wide_down = 1;
     int gu_tile = 0;                 // gate/up tile (NTTS_GU_TILE): 0 = 128 x 128 / 8 waves / 3 slots (above batch 128; 64 x 64 below), 1 = 256 x 192 / 12 waves / 2 slots,
-                                     // 2 = 256 x 256 / 16 waves / 2 slots, 3 = 128 x 128 / 2 slots (two workgroups per CU)
+                                     // 2 = 256 x 256 / 16 waves / 2 slots, 3 = 128 x 128 / 2 slots (two workgroups per CU), 4 = 320 x 192 / 12 waves / 2 slots (bf16)
+    int gu_alone = 0, gu_gang = 0;   // ... what create() chose for a chain alone on the chip and for chains side by side (apply_gang_shape; the knob sets both)
     // Tile path: the QKV projection with bias, rounding, RoPE and the K append in its epilogue (qkv_rope.h); the attention kernel
     // then has no prologue.  step_meta / rope_rows: the per-step row records that kernel reads (step_meta_kernel, once per step).
     int* step_meta = nullptr;
@@ -280,8 +281,8 @@ struct ntts_backbone {
     //   head_r / shead_r, lr_*, n_part: set_logits_range -- drops;
     //   logits_bf16 (+ ldl), seen (+ seen_pitch), part_sum and out_logprobs: allocated once, by the first sampling request, the first penalised
     //   request and the first set_logprobs(1), and freed by destroy; WHETHER a step uses them is in its key (set_logprobs drops all the same);
-    //   the tile knobs (ks_o, ks_d, wide*, gu_tile, gu_128, head_tile, xcd_xps, xl_min_m, small, attn_split, dec_rows): create -- no call; tall,
-    //   xcd_affine and qkv_wstat follow the key's shape and knobs read at create (apply_gang_shape);
+    //   the tile knobs (ks_o, ks_d, wide*, gu_alone, gu_gang, gu_128, head_tile, xcd_xps, xl_min_m, small, attn_split, dec_rows): create -- no call; tall,
+    //   xcd_affine, qkv_wstat and gu_tile follow the key's shape and knobs read at create (apply_gang_shape);
     //   attn_tl / gemv_tl: null except inside the timeline calls, which capture nothing;  the stream: a capture replays on any stream.
     StepGraph steps[32];
     bool use_graph = true;
@@ -331,7 +332,7 @@ static int env_int(const char* name, int dflt) {
 
 // (max, first index) pairs the lm_head leaves per row for a head of N columns (gemm.h / gemv.h EPI_ARGMAX: one per wave tile)
 static int n_part_for(const ntts_backbone* e, int N) {
-    return e->small ? (N + 15) / 16 : e->head_tile == 0 ? (N + 63) / 64 : e->head_tile == 4 ? ((N + 287) / 288) * 3 : e->head_tile == 2 ? ((N + 255) / 256) * 4 : ((N + 127) / 128) * 2;
+    return e->small ? (N + 15) / 16 : e->head_tile == 0 ? (N + 63) / 64 : e->head_tile == 4 ? ((N + 287) / 288) * 3 : e->head_tile == 3 ? ((N + 191) / 192) * 3 : e->head_tile == 2 ? ((N + 255) / 256) * 4 : ((N + 127) / 128) * 2;
 }
 
 // The decode step's shape as a function of how many chains share the chip (ntts_backbone_set_gang; measured on MI355X with
@@ -345,6 +346,7 @@ static void apply_gang_shape(ntts_backbone* e) {
     // QKV column blocks dealt to XCDs whenever the row-block placement is off for a gang (FETCH per launch 17.1 -> 6.1 MB, step -0.7 %:
     // profiles/r05g_*); NTTS_QKV_WSTAT = 0 / 1 overrides
     e->qkv_wstat = e->wstat_env >= 0 ? e->wstat_env != 0 : side_by_side;
+    e->gu_tile = e->gang >= 2 ? e->gu_gang : e->gu_alone;
 }
 
 extern "C" int ntts_backbone_create(const ntts_backbone_config* c, int device, ntts_backbone** out) {
@@ -536,8 +538,18 @@ extern "C" int ntts_backbone_create(const ntts_backbone_config* c, int device, n
     e->wide_down = env_int("NTTS_WIDE_DOWN", 1);
     // (wide engines whose rows are a multiple of 128 but not of 256 -- 640: bench.py's engines for the driver's --steps 20 -- would leave half of the last
     //  256-row block empty: the 2-slot 128 x 128 tile instead, 3.02 -> 2.89 ms per step alone, 1.97 -> 1.95 in a gang of four; same bits, profiles/r06h_sweep_gang_640.txt)
-    e->gu_tile = env_int("NTTS_GU_TILE", e->wide ? ((D % 256) == 128 ? 3 : 1) : 0);
-    if (e->gu_tile < 0 || e->gu_tile > 3) e->gu_tile = 0;
+    // (bf16 wide engines take the m-block, 256 or 320 rows, that issues fewer rows past D -- 576, 640, 896 rows: 320; 512, 768, 1024: 256 -- for the lm_head
+    //  always and for gate/up when chains share the chip: 320 x 192 is 2 x 51 workgroups per 640-row chain, -1 % per gang step next to the 2-slot 128 x 128 tile,
+    //  -2.2 % with the lm_head.  A chain ALONE on the chip keeps gate/up's earlier tile unless it has three 320-row blocks -- 640 rows: 18.7 -> 27.4 us per
+    //  launch, 2.90 -> 3.12 ms per step; 896 rows: 29.3 -> 27.3 us.  Same bits either way: profiles/r07a_sweep_gang_tile320.txt)
+    const bool m320 = e->wide && !e->fp8 && (D + 319) / 320 * 320 < (D + 255) / 256 * 256;
+    const int gu_old = e->wide ? ((D % 256) == 128 ? 3 : 1) : 0;
+    e->gu_gang = env_int("NTTS_GU_TILE", m320 ? 4 : gu_old);
+    e->gu_alone = env_int("NTTS_GU_TILE", m320 && D > 640 ? 4 : gu_old);
+    for (int* t : {&e->gu_gang, &e->gu_alone}) {
+        if (*t < 0 || *t > 4) *t = 0;
+        if (e->fp8 && *t > 3) *t = 3;                           // (the 320-row tile is bf16 only)
+    }
     if (e->wide && e->wide_down == 1 && !e->fp8 && env_int("NTTS_KS_D", 0) <= 0) e->ks_d = 4;   // 8 x 7 tiles of 128 x 128 x 4 K slices = 224 workgroups
     e->xl_min_m = env_int("NTTS_XL_MIN_M", 0);
     {   // 0 = every query on the two-sweep kernel; whole pages, at most what the resident kernel holds
@@ -549,9 +561,9 @@ extern "C" int ntts_backbone_create(const ntts_backbone_config* c, int device, n
     e->wstat_env = env_int("NTTS_QKV_WSTAT", -1);   // (read here like the two above, not at every shape switch: the other shape's captured step keeps what it baked)
     e->tall_xcd_split = env_int("NTTS_TALL_XCD_SPLIT", 1) != 0;
     apply_gang_shape(e);
-    e->head_tile = env_int("NTTS_HEAD_TILE", D > 128 ? (e->fp8 || e->wide ? 2 : 4) : D > 64 ? 1 : 0);   // (1024 rows: 256 x 256 424 us, 256 x 288 438)
-    if (e->head_tile != 0 && e->head_tile != 1 && e->head_tile != 2 && e->head_tile != 4) e->head_tile = 1;
-    if (e->fp8 && e->head_tile == 4) e->head_tile = 2;          // (the natural-order tile is bf16 only)
+    e->head_tile = env_int("NTTS_HEAD_TILE", D > 128 ? (m320 ? 3 : e->fp8 || e->wide ? 2 : 4) : D > 64 ? 1 : 0);   // (1024 rows: 256 x 256 424 us, 256 x 288 438)
+    if (e->head_tile < 0 || e->head_tile > 4) e->head_tile = 1;
+    if (e->fp8 && e->head_tile >= 3) e->head_tile = 2;          // (the 320-row and the natural-order tile are bf16 only)
     e->gu_128 = D > 128;
     e->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
 
@@ -1163,7 +1175,7 @@ extern "C" int ntts_backbone_read_amax(ntts_backbone* e, float* out, int32_t n) 
 static void use_shape_for(ntts_backbone* e, int chains) {
     const int B = e->dec_rows;
     e->gang = chains;
-    e->shape = (chains >= 2 && B > 128 && B <= 256) ? 1 : 0;
+    e->shape = (chains >= 2 && ((B > 128 && B <= 256) || e->gu_gang != e->gu_alone)) ? 1 : 0;
     apply_gang_shape(e);
 }
 // engines of this arena with a decode call inside the window, this one included
@@ -1391,6 +1403,8 @@ static void k_gate_up(ntts_backbone* e, int i) {
     } else if (e->gu_tile == 3) {   // 128 x 128, 8 waves, 2 slots
         if (e->fp8) gemm_launch<4, 2, 2, EPI_SILU_MUL, 2, 0, 64, false, true>(gu, 1, e->stream);
         else gemm_launch<4, 2, 2, EPI_SILU_MUL, 2>(gu, 1, e->stream);
+    } else if (e->gu_tile == 4) {   // 320 x 192, 12 waves (bf16: create() keeps fp8 engines off it)
+        gemm_launch<4, 3, 5, EPI_SILU_MUL, 2>(gu, 1, e->stream);
     } else if (e->gu_128) {   // 128 x 128, 8 waves
         if (e->fp8) gemm_launch<4, 2, 2, EPI_SILU_MUL, 3, 0, 64, false, true>(gu, 1, e->stream);
         else gemm_launch<4, 2, 2, EPI_SILU_MUL, 3>(gu, 1, e->stream);

@@ -29,6 +29,8 @@ extern "C" int ntts_k_gemm_bf16(const void* A, int64_t lda, const void* W, const
     else if (variant == 5) gemm_launch<4, 4, 4, EPI_BF16, 4, 0, 32>(a, 1, (hipStream_t)0);   // XL tile, 4 ring slots of K = 32
     else if (variant == 6) gemm_launch<2, 2, 4, EPI_BF16, 3, 0, 32>(a, 1, (hipStream_t)0);   // L tile, 3 ring slots of K = 32
     else if (variant == 7) gemm_launch<4, 3, 4, EPI_BF16, 2, 0, 64, false, false, 6>(a, 1, (hipStream_t)0);   // natural-order 256 x 288 tile, 12 waves (prefill QKV)
+    else if (variant == 8) gemm_launch<4, 3, 5, EPI_BF16, 2>(a, 1, (hipStream_t)0);   // 320 x 192, 12 waves (80 x 64 per wave): decode gate/up and lm_head of 576- / 640- / 896-row engines
+    else if (variant == 9) gemm_launch<4, 2, 5, EPI_BF16, 2>(a, 1, (hipStream_t)0);   // 320 x 128, 8 waves
     else if (variant == 3) {  // split-K slabs reduced by the norm kernel (the decode o_proj / down_proj path)
         if (bias || (N % 16) || ldc != N) return NTTS_EINVAL;
         const int ks = 4, ns = gemm_nsplit(K, ks);
@@ -172,6 +174,8 @@ static void probe_dispatch(int config, const GemmArgs& a, int ks, int abl) {
         case 55: probe_launch<4, 4, 5, 2>(a, ks, abl); break;   // 320 x 256, 16 waves (80 x 64 per wave): 11 % fewer LDS-DMA bytes per FLOP than 256 x 256; 144 KB
         case 57: probe_launch<2, 4, 10, 2>(a, ks, abl); break;  // 320 x 256, 8 waves (160 x 64 per wave, 2 waves per SIMD: up to 256 registers each)
         case 58: probe_launch<2, 4, 12, 2>(a, ks, abl); break;  // 384 x 256, 8 waves (192 x 64 per wave)
+        case 59: probe_launch<4, 3, 5, 2>(a, ks, abl); break;   // 320 x 192, 12 waves (80 x 64 per wave): 128 KB
+        case 60: probe_launch<4, 2, 5, 2>(a, ks, abl); break;   // 320 x 128, 8 waves: 112 KB
         case 56: probe_launch<4, 4, 6, 2>(a, ks, abl); break;   // 384 x 256, 16 waves (96 x 64 per wave): 17 % fewer; 160 KB = all of a CU's LDS
         default: break;
     }

@@ -783,6 +783,14 @@ NTTS_KERNEL(WM * WN * 64) void gemm_kernel(GemmArgs p) {
 // 104.7 us.  Under the board's power limit the two halves do not overlap any better than before, and at K = 896 a quarter to a third of a tile's time is
 // its epilogue on two waves per SIMD (gate/up: 620 -> 430 us with the stores ablated), which no main-loop schedule touches: +-5 % by shape, not adopted.
 
+// The 320-row tiles (wave tile 80 x 64, TM = 5) exist for decode engines of 576 / 640 / 896 rows, which two or three 320-row blocks fit without the half-empty
+// last block of the 256-row tiles.  Kept: 320 x 192 on 12 waves (155 registers, 128 KB ring, 64 loader instructions over 12 waves) for the lm_head and,
+// in an engine gang, for gate/up (backbone.cpp create()).  Measured on MI355X and not kept (four 640-row chains side by side, ms per chain step at the same
+// context, two runs each; profiles/r07a_sweep_gang_tile320.txt): gate/up on 320 x 128 / 8 waves / 2 slots, 152 workgroups per chain instead of 102:
+// 1.961 vs 1.946 on 320 x 192 and 1.944 on 128 x 128; down_proj on 320 x 128 / 8 waves / 2 slots at the same four K slices (bit-identical slabs, 56 workgroups
+// per chain of 19 k-steps instead of 140): 1.966-1.975 vs 1.956-1.963 by itself, 29.4 vs 17.8 us per launch alone on the chip; next to the two kept tiles it
+// did take another 0.7 % off the gang step (1.890-1.905 vs 1.909-1.912), not enough for a tile that costs a chain alone 10 % of its step (2.91 -> 3.19 ms).
+
 // ------------------------------------------------------------------------------------------------
 // host launchers
 // ------------------------------------------------------------------------------------------------
@@ -841,7 +849,8 @@ inline void gemm_launch(GemmArgs p, int ksplit, hipStream_t s) {
 #define NTTS_GEMM_S(EPI, p, ks, s) ::ntts::gemm_launch<4, 1, 1, EPI, 4>(p, ks, s)
 
 // The decode lm_head (backbone.cpp k_lm_head; kapi.cpp ntts_k_head_penalty_probe runs the same launch on caller-supplied data).  head_tile: 0 = 64 x 64
-// skinny / 4-slot ring, 1 = 128 x 128, 2 = 256 x 256 (16 waves), 4 = natural-order 256 x 288 (12 waves, bf16 only); the 256-row tiles stream W with the
+// skinny / 4-slot ring, 1 = 128 x 128, 2 = 256 x 256 (16 waves), 3 = 320 x 192 (12 waves, 80 x 64 per wave, bf16 only: row counts that two or three
+// 320-row blocks fit better than 256-row ones), 4 = natural-order 256 x 288 (12 waves, bf16 only); the 256- and 320-row tiles stream W with the
 // non-temporal policy (read once per step).  a.seen != null selects the kernels with the repetition penalty in their epilogue, a.part_sum != null
 // those that also reduce the row's log-sum-exp, a.target != null (with part_sum and target_val) the scoring kernels.
 template <int EPI>
@@ -852,6 +861,7 @@ inline void lm_head_launch_epi(const GemmArgs& a, int head_tile, bool fp8, hipSt
             else gemm_launch<4, 1, 1, EPI, 4>(a, 1, s);
             break;
         case 4: gemm_launch<4, 3, 4, EPI, 2, 0, 64, true, false, 6>(a, 1, s); break;
+        case 3: gemm_launch<4, 3, 5, EPI, 2, 0, 64, true>(a, 1, s); break;
         case 2:
             if (fp8) gemm_launch<4, 4, 4, EPI, 2, 0, 64, true, true>(a, 1, s);
             else gemm_launch<4, 4, 4, EPI, 2, 0, 64, true>(a, 1, s);
