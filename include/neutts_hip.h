@@ -530,6 +530,40 @@ int ntts_codec_decode_dev_fmt(ntts_codec* c, int32_t n, const int32_t* codes_dev
 int ntts_codec_convert(ntts_codec* c, int32_t n, const float* wav, int64_t in_stride, const int32_t* n_samples,
                        const ntts_wav_format* fmt, void* out, int64_t out_stride, int32_t* out_lens);
 
+/* Speed: a pitch-preserving time stretch on the device, between overlap-add and the output stage.  NEW SYMBOLS ONLY: NTTS_ABI_VERSION stays 11.
+ *
+ * The reference has no such knob (a codec-token language model has no duration input); its users resample, which moves the pitch, or run a
+ * time-stretch library on the 24 kHz float waveform on the host.  Here it is WSOLA (waveform-similarity overlap-add) at the native 24 kHz, stated so
+ * that the choice of every segment is a function of the row and the speed alone -- integer arithmetic, no order of additions:
+ * L = 720 (30 ms), Hs = 360, D = 240 (+-10 ms).  Speed is an integer per mille pm in [500, 2000]; n_out = ceil(n_in * 1000 / pm), K = ceil(n_out / Hs)
+ * output frames.  pm = 1000 copies the row bit for bit (positions k * Hs), and a call whose rows are all 1000 launches nothing of this stage.
+ * The search signal is s = PCM16(x) (the rounding of the output stage); x and s read as zero outside [0, n_in) of their own utterance;
+ * pmax = max(0, n_in - L).  Frame 0: p_0 = 0, out[0 .. Hs) = x[0 .. Hs).  Frame k >= 1: t_k = p_{k-1} + Hs (the natural continuation),
+ * a_k = (k * Hs * pm + 500) / 1000, candidates c from clamp(a_k - D) to clamp(a_k + D) with clamp to [0, pmax],
+ * D(c) = sum_{i < Hs} |s[t_k + i] - s[c + i]|, p_k = the c that minimises the tuple (D, |c - t_k|, c), and
+ * out[k * Hs + i] = fmaf(f[i], x[p_k + i] - x[t_k + i], x[t_k + i]) in fp32 with f[i] = 0.5 - 0.5 cos(pi (i + 0.5) / Hs) built in double and rounded once:
+ * the input bit for bit wherever p_k == t_k.  Up to the last 30 ms of an utterance may be compressed or dropped; rows shorter than L come out as the
+ * rule says and mean nothing.  tests/time_stretch_spec.py states all of this in numpy and is the authority.
+ *
+ * ntts_wav_stretch_len: n_out of n_in samples at a speed; pure host arithmetic (message through ntts_codec_last_error(NULL)).
+ * ntts_codec_stretch: the stage alone (and the output stage behind it) on HOST float32 waveforms, the twin of ntts_codec_convert -- for a host library
+ * between the codec and the output (a watermarker) and for the tests.  speed_permille[n]; out_lens[i] = the samples of row i in `fmt`;
+ * positions (may be NULL): row i receives p_0 .. p_{K_i - 1} at offset i * pos_stride.  Blocking.
+ * ntts_codec_decode_speed / ntts_codec_decode_dev_speed: ntts_codec_decode_fmt / ntts_codec_decode_dev_fmt with speed_permille[n]; NULL means all
+ * 1000, and that (like an array of 1000s) makes the very same calls as those entry points, bit for bit.
+ * Refused with NTTS_EINVAL and a message, nothing run, the engine stays usable: a speed outside [500, 2000], out_stride below the largest out_lens,
+ * pos_stride below the largest K, and what ntts_codec_convert / ntts_codec_decode_fmt refuse.
+ * ntts_codec_last_stretch_timing: GPU milliseconds of the search and the render kernel of the most recent stretch (NTTS_ESTATE before the first). */
+int ntts_wav_stretch_len(int32_t speed_permille, int64_t n_in, int64_t* n_out);
+int ntts_codec_stretch(ntts_codec* c, int32_t n, const float* wav, int64_t in_stride, const int32_t* n_samples, const int32_t* speed_permille,
+                       const ntts_wav_format* fmt, void* out, int64_t out_stride, int32_t* out_lens, int32_t* positions, int64_t pos_stride);
+int ntts_codec_decode_speed(ntts_codec* c, int32_t n, const int32_t* codes, const int32_t* lens, const int32_t* speed_permille,
+                            const ntts_wav_format* fmt, void* out, int64_t out_stride, int32_t* out_lens);
+int ntts_codec_decode_dev_speed(ntts_codec* c, int32_t n, const int32_t* codes_dev, int32_t codes_stride, const int32_t* lens,
+                                const int32_t* speed_permille, void* out, int64_t out_stride, int32_t out_on_device, void* producer_stream,
+                                const ntts_wav_format* fmt, int32_t* out_lens);
+int ntts_codec_last_stretch_timing(ntts_codec* c, float* search_ms, float* render_ms);
+
 /* The output stage on a signal that arrives in CHUNKS (a stream).  NEW SYMBOLS ONLY: NTTS_ABI_VERSION stays 11.
  *
  * After N input samples in all a stream has emitted M(N) output samples: M = N at 24 kHz; otherwise M = ((N - width) / orig) * new once

@@ -76,6 +76,15 @@ struct ntts_codec {
     std::map<std::pair<int, int>, WavTable> wav_tables;
     void* fbuf = nullptr;
     size_t fbuf_cap = 0;         // bytes
+    // time stretch (ntts_codec_stretch / _decode_speed): the stretched 24 kHz waveforms and their frame positions, allocated with the first call
+    // that needs them for twice the waveform workspace (speed 0.5 doubles a row); the fade table; events around the two kernels
+    float* sbuf = nullptr;
+    size_t sbuf_cap = 0;         // floats
+    int* spos = nullptr;
+    size_t spos_cap = 0;         // ints
+    float* sfade = nullptr;
+    hipEvent_t ev_s[3]{};
+    bool have_stretch_time = false;
 };
 
 static int cfail(ntts_codec* c, int code, const char* fmt, ...) {
@@ -111,6 +120,10 @@ extern "C" void ntts_codec_destroy(ntts_codec* c) {
     for (void* p : c->allocs) hipFree(p);
     if (c->tap) hipFree(c->tap);
     if (c->fbuf) hipFree(c->fbuf);
+    if (c->sbuf) hipFree(c->sbuf);
+    if (c->spos) hipFree(c->spos);
+    for (auto& e : c->ev_s)
+        if (e) hipEventDestroy(e);
     for (auto& e : c->ev)
         if (e) hipEventDestroy(e);
     if (c->ev_in) hipEventDestroy(c->ev_in);
@@ -525,6 +538,69 @@ static int wav_format_launch(ntts_codec* c, const WavFmt& w, const float* in, lo
     return NTTS_OK;
 }
 
+// ---- time stretch between overlap-add and the output stage (kernels/codec.h wav_stretch_*; tests/time_stretch_spec.py is the contract)
+static int64_t stretch_len(int64_t n_in, int pm) { return (n_in * 1000 + pm - 1) / pm; }
+static int64_t stretch_frames(int64_t n_out) { return (n_out + kStretchHop - 1) / kStretchHop; }
+// every speed inside [500, 2000]; *any = one of them is not 1000 (otherwise nothing of the stage is run)
+static int stretch_check(ntts_codec* c, const int32_t* speed, int n, bool* any) {
+    *any = false;
+    for (int i = 0; i < n; ++i) {
+        if (speed[i] < 500 || speed[i] > 2000) return cfail(c, NTTS_EINVAL, "utterance %d: speed %d per mille outside [500, 2000]", i, speed[i]);
+        if (speed[i] != 1000) *any = true;
+    }
+    if (*any && (int64_t)c->cfg.max_frames * c->cfg.hop_length >= (1 << 22))
+        return cfail(c, NTTS_EINVAL, "speed: an engine of %ld samples per utterance exceeds the search kernel's 2^22", (long)c->cfg.max_frames * c->cfg.hop_length);
+    return NTTS_OK;
+}
+
+extern "C" int ntts_wav_stretch_len(int32_t speed_permille, int64_t n_in, int64_t* n_out) {
+    if (!n_out || n_in < 0) return cfail(nullptr, NTTS_EINVAL, "ntts_wav_stretch_len: null / negative argument");
+    if (speed_permille < 500 || speed_permille > 2000) return cfail(nullptr, NTTS_EINVAL, "ntts_wav_stretch_len: speed %d per mille outside [500, 2000]", speed_permille);
+    *n_out = stretch_len(n_in, speed_permille);
+    return NTTS_OK;
+}
+
+// in [n][in_stride] (utterance b: lens_dev[b] * len_mul samples, speed pm_dev[b], nout_dev[b] output samples) -> c->sbuf [n][n_out_max] float32,
+// c->spos [n][stretch_frames(n_out_max)]
+static int wav_stretch_launch(ntts_codec* c, const float* in, long in_stride, const int* lens_dev, int len_mul, const int* pm_dev, const int* nout_dev,
+                              int n, int64_t n_out_max, hipStream_t st) {
+    const int64_t k_max = stretch_frames(n_out_max);
+    const size_t need = (size_t)n * n_out_max, need_pos = (size_t)n * k_max;
+    if (c->sbuf_cap < need || c->spos_cap < need_pos || !c->sfade) {
+        CHIP(c, hipStreamSynchronize(st));
+        if (!c->sfade) {
+            std::vector<float> f(kStretchHop);
+            for (int i = 0; i < kStretchHop; ++i) f[i] = (float)(0.5 - 0.5 * cos(M_PI * (i + 0.5) / kStretchHop));
+            const int rc = dalloc(c, &c->sfade, f.size());
+            if (rc != NTTS_OK) return rc;
+            CHIP(c, hipMemcpy(c->sfade, f.data(), f.size() * sizeof(float), hipMemcpyHostToDevice));
+            for (auto& e : c->ev_s) CHIP(c, hipEventCreate(&e));
+        }
+        if (c->sbuf_cap < need) {
+            const size_t whole = 2 * c->wav_cap + (size_t)c->max_rows;
+            if (c->sbuf) { hipFree(c->sbuf); c->sbuf = nullptr; c->sbuf_cap = 0; }
+            CHIP(c, hipMalloc((void**)&c->sbuf, std::max(need, whole) * sizeof(float)));
+            c->sbuf_cap = std::max(need, whole);
+        }
+        if (c->spos_cap < need_pos) {
+            const size_t whole = 2 * c->wav_cap / kStretchHop + 2 * (size_t)c->max_rows;
+            if (c->spos) { hipFree(c->spos); c->spos = nullptr; c->spos_cap = 0; }
+            CHIP(c, hipMalloc((void**)&c->spos, std::max(need_pos, whole) * sizeof(int)));
+            c->spos_cap = std::max(need_pos, whole);
+        }
+    }
+    WavStretchArgs a{};
+    a.in = in; a.in_stride = in_stride; a.lens = lens_dev; a.len_mul = len_mul; a.pm = pm_dev; a.n_out = nout_dev;
+    a.pos = c->spos; a.pos_stride = k_max; a.fade = c->sfade; a.out = c->sbuf; a.out_stride = n_out_max;
+    CHIP(c, hipEventRecord(c->ev_s[0], st));
+    NTTS_LAUNCH((wav_stretch_search_kernel), dim3(n), dim3(256), st, a);
+    CHIP(c, hipEventRecord(c->ev_s[1], st));
+    NTTS_LAUNCH((wav_stretch_render_kernel), dim3(n, (unsigned)((n_out_max + 255) / 256)), dim3(256), st, a);
+    CHIP(c, hipEventRecord(c->ev_s[2], st));
+    c->have_stretch_time = true;
+    return NTTS_OK;
+}
+
 // codes: HOST packed codes (codes_dev == null), or DEVICE codes, utterance i at codes_dev + i * codes_stride (already in range:
 // they come from ntts_backbone_export_codes).  out_kind: 0 = host destination, blocking (the classic entry point);
 // 1 = host destination (pinned), asynchronous; 2 = device destination, asynchronous.  producer: a HIP stream whose work so far
@@ -533,10 +609,16 @@ static int wav_format_launch(ntts_codec* c, const WavFmt& w, const float* in, lo
 // receives every utterance's samples.
 static int codec_decode_impl(ntts_codec* c, int32_t n, const int32_t* codes, const int32_t* codes_dev, int32_t codes_stride,
                              const int32_t* lens, void* wav_out, int64_t wav_stride, int out_kind, hipStream_t producer,
-                             const WavFmt* wf = nullptr, int32_t* out_lens = nullptr) {
+                             const WavFmt* wf = nullptr, int32_t* out_lens = nullptr, const int32_t* speed = nullptr) {
     if (!c || n < 1 || (!codes && !codes_dev) || !lens || !wav_out) return cfail(c, NTTS_EINVAL, "null/empty argument");
     if (!c->finalized) return cfail(c, NTTS_ESTATE, "weights not finalised");
     if (wf && wf->plain()) wf = nullptr;
+    if (speed) {                           // speed_permille: all 1000 (or null) is the pass without the stage, call for call
+        bool any;
+        const int rc = stretch_check(c, speed, n, &any);
+        if (rc != NTTS_OK) return rc;
+        if (!any) speed = nullptr;
+    }
     CHIP(c, hipSetDevice(c->device));
     const int H = c->H, hop = c->cfg.hop_length;
     int Tmax = 0;
@@ -553,11 +635,20 @@ static int codec_decode_impl(ntts_codec* c, int32_t n, const int32_t* codes, con
             if (codes[i] < 0 || codes[i] >= ncodes) return cfail(c, NTTS_EINVAL, "code %d out of range [0, %ld)", codes[i], ncodes);
     if (codes_dev && codes_stride < Tmax) return cfail(c, NTTS_EINVAL, "codes_stride %d < longest utterance %d", codes_stride, Tmax);
     // samples per row of the hand-over (the longest utterance's, in the output format) and bytes per sample
-    const int64_t row_len = wf ? wf->out_len((int64_t)hop * Tmax) : (int64_t)hop * Tmax;
+    // (with a speed: of the longest STRETCHED utterance)
+    int64_t s_max = (int64_t)hop * Tmax;
+    if (speed) {
+        s_max = 0;
+        for (int i = 0; i < n; ++i) s_max = std::max(s_max, stretch_len((int64_t)hop * lens[i], speed[i]));
+    }
+    const int64_t row_len = wf ? wf->out_len(s_max) : s_max;
     const size_t esz = wf ? wf->esz : sizeof(float);
     if (wav_stride < row_len) return cfail(c, NTTS_EINVAL, "wav_stride %ld < %ld samples", (long)wav_stride, (long)row_len);
     if (out_lens)
-        for (int i = 0; i < n; ++i) out_lens[i] = (int32_t)(wf ? wf->out_len((int64_t)hop * lens[i]) : (int64_t)hop * lens[i]);
+        for (int i = 0; i < n; ++i) {
+            const int64_t s_i = speed ? stretch_len((int64_t)hop * lens[i], speed[i]) : (int64_t)hop * lens[i];
+            out_lens[i] = (int32_t)(wf ? wf->out_len(s_i) : s_i);
+        }
     const int Tp = Tmax + 2 * kPadRows;
     const long rows = total + 2L * kPadRows * n;          // packed: every utterance brings its own frames + pad rows (codec.h)
     if (rows > c->max_rows) return cfail(c, NTTS_EINVAL, "%ld rows exceed max_rows %ld: decode fewer utterances per call", rows, c->max_rows);
@@ -568,7 +659,8 @@ static int codec_decode_impl(ntts_codec* c, int32_t n, const int32_t* codes, con
     if (!(c->attn_resident && npages <= kAttnResPages) && (long)n * npages * kPage > c->max_rows + (c->max_rows / (1 + 2 * kPadRows) + 1) * kPage)
         return cfail(c, NTTS_EINVAL, "%d utterances x %d pages exceed the V^T workspace: decode fewer utterances per call", n, npages);
     // ---- meta: [lens n][code_off n][row_off n + 1][codes total], built in a page-locked ring slot: the copy is asynchronous, no stream-wide wait
-    const size_t m_size = 3 * (size_t)n + 1 + (codes ? (size_t)total : 0);
+    // (with a speed: [speed n][stretched samples n] behind them)
+    const size_t m_size = 3 * (size_t)n + 1 + (codes ? (size_t)total : 0) + (speed ? 2 * (size_t)n : 0);
     if (m_size > c->meta_cap) return cfail(c, NTTS_EINVAL, "meta block too large");
     hipStream_t st = c->stream;
     {
@@ -584,6 +676,10 @@ static int codec_decode_impl(ntts_codec* c, int32_t n, const int32_t* codes, con
         for (int i = 0; i < n; ++i) { m[at++] = (int)roff; roff += lens[i] + 2 * kPadRows; }
         m[at++] = (int)roff;
         if (codes) { memcpy(m + at, codes, (size_t)total * sizeof(int)); at += total; }
+        if (speed) {
+            memcpy(m + at, speed, (size_t)n * sizeof(int)); at += n;
+            for (int i = 0; i < n; ++i) m[at++] = (int)stretch_len((int64_t)hop * lens[i], speed[i]);
+        }
         CHIP(c, hipMemcpyAsync(c->meta, m, at * sizeof(int), hipMemcpyHostToDevice, st));
         c->meta_used[k] = true;
         CHIP(c, hipEventRecord(c->meta_ev[k], st));
@@ -665,8 +761,18 @@ static int codec_decode_impl(ntts_codec* c, int32_t n, const int32_t* codes, con
     oa.scale = c->fmt == kOpF16 ? 1.0f / kDftScale : 1.0f;
     NTTS_LAUNCH((ola_kernel), dim3(n, (unsigned)(((long)hop * Tmax + 255) / 256)), dim3(256), st, oa);
     const void* src = c->wav;
+    const float* fin = c->wav;             // what the output stage reads: [n][fin_stride], utterance b of fin_lens[b] * fin_mul samples
+    long fin_stride = (long)hop * Tmax;
+    const int* fin_lens = R.lens;
+    int fin_mul = hop;
+    if (speed) {                           // the time stretch: the stretched buffer becomes the copy's source, or the output stage's input
+        const int* sp = c->meta + (m_size - 2 * (size_t)n);
+        const int rc = wav_stretch_launch(c, c->wav, (long)hop * Tmax, R.lens, hop, sp, sp + n, n, s_max, st);
+        if (rc != NTTS_OK) return rc;
+        src = fin = c->sbuf; fin_stride = (long)s_max; fin_lens = sp + n; fin_mul = 1;
+    }
     if (wf) {                              // the output stage: the formatted buffer becomes the copy's source
-        const int rc = wav_format_launch(c, *wf, c->wav, (long)hop * Tmax, R.lens, hop, n, row_len, st);
+        const int rc = wav_format_launch(c, *wf, fin, fin_stride, fin_lens, fin_mul, n, row_len, st);
         if (rc != NTTS_OK) return rc;
         src = c->fbuf;
     }
@@ -778,6 +884,119 @@ extern "C" int ntts_codec_convert(ntts_codec* c, int32_t n, const float* wav, in
         CHIP(c, hipStreamSynchronize(st));
         CHIP(c, hipGetLastError());
     }
+    return NTTS_OK;
+}
+
+// ntts_codec_decode_fmt / ntts_codec_decode_dev_fmt with a speed per utterance (per mille; null = all 1000: the very same calls)
+extern "C" int ntts_codec_decode_speed(ntts_codec* c, int32_t n, const int32_t* codes, const int32_t* lens, const int32_t* speed_permille,
+                                       const ntts_wav_format* fmt, void* out, int64_t out_stride, int32_t* out_lens) {
+    if (!c) return NTTS_EINVAL;
+    if (!codes || !out_lens) return cfail(c, NTTS_EINVAL, "null/empty argument");
+    WavFmt w;
+    const int rc = wav_fmt_check(c, fmt, &w);
+    if (rc != NTTS_OK) return rc;
+    return codec_decode_impl(c, n, codes, nullptr, 0, lens, out, out_stride, 0, nullptr, &w, out_lens, speed_permille);
+}
+
+extern "C" int ntts_codec_decode_dev_speed(ntts_codec* c, int32_t n, const int32_t* codes_dev, int32_t codes_stride, const int32_t* lens,
+                                           const int32_t* speed_permille, void* out, int64_t out_stride, int32_t out_on_device,
+                                           void* producer_stream, const ntts_wav_format* fmt, int32_t* out_lens) {
+    if (!c) return NTTS_EINVAL;
+    if (!codes_dev || !out_lens) return cfail(c, NTTS_EINVAL, "null/empty argument");
+    WavFmt w;
+    const int rc = wav_fmt_check(c, fmt, &w);
+    if (rc != NTTS_OK) return rc;
+    return codec_decode_impl(c, n, nullptr, codes_dev, codes_stride, lens, out, out_stride, out_on_device ? 2 : 1, (hipStream_t)producer_stream, &w,
+                             out_lens, speed_permille);
+}
+
+// The time stretch (and the output stage behind it) alone on the caller's 24 kHz float32 waveforms: ntts_codec_convert's twin, the same rounds.  Blocking.
+extern "C" int ntts_codec_stretch(ntts_codec* c, int32_t n, const float* wav, int64_t in_stride, const int32_t* n_samples,
+                                  const int32_t* speed_permille, const ntts_wav_format* fmt, void* out, int64_t out_stride, int32_t* out_lens,
+                                  int32_t* positions, int64_t pos_stride) {
+    if (!c) return NTTS_EINVAL;
+    if (n < 1 || !wav || !n_samples || !speed_permille || !out || !out_lens || in_stride < 0) return cfail(c, NTTS_EINVAL, "null/empty argument");
+    WavFmt w;
+    int rc = wav_fmt_check(c, fmt, &w);
+    if (rc != NTTS_OK) return rc;
+    bool any;
+    rc = stretch_check(c, speed_permille, n, &any);
+    if (rc != NTTS_OK) return rc;
+    const int64_t cap = (int64_t)c->cfg.max_frames * c->cfg.hop_length;
+    int64_t Lmax = 0, s_max = 0;
+    for (int i = 0; i < n; ++i) {
+        if (n_samples[i] < 0 || n_samples[i] > in_stride)
+            return cfail(c, NTTS_EINVAL, "utterance %d: n_samples %d outside [0, in_stride %ld]", i, n_samples[i], (long)in_stride);
+        if (n_samples[i] > cap) return cfail(c, NTTS_EINVAL, "utterance %d: %d samples exceed the engine's %ld (max_frames x hop)", i, n_samples[i], (long)cap);
+        Lmax = std::max<int64_t>(Lmax, n_samples[i]);
+        s_max = std::max(s_max, stretch_len(n_samples[i], speed_permille[i]));
+    }
+    const int64_t row_len = w.out_len(s_max), k_max = stretch_frames(s_max);
+    if (out_stride < row_len) return cfail(c, NTTS_EINVAL, "out_stride %ld < %ld samples", (long)out_stride, (long)row_len);
+    if (positions && pos_stride < k_max) return cfail(c, NTTS_EINVAL, "pos_stride %ld < %ld frames", (long)pos_stride, (long)k_max);
+    if (!any) {                            // every row a copy: the output stage alone, nothing of this one is launched
+        rc = ntts_codec_convert(c, n, wav, in_stride, n_samples, fmt, out, out_stride, out_lens);
+        if (rc == NTTS_OK && positions)
+            for (int i = 0; i < n; ++i)
+                for (int64_t k = 0; k < stretch_frames(n_samples[i]); ++k) positions[(size_t)i * pos_stride + k] = (int32_t)(k * kStretchHop);
+        return rc;
+    }
+    for (int i = 0; i < n; ++i) out_lens[i] = (int32_t)w.out_len(stretch_len(n_samples[i], speed_permille[i]));
+    if (Lmax == 0) return NTTS_OK;
+    CHIP(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    const size_t esz = w.plain() ? sizeof(float) : w.esz, row_bytes = (size_t)row_len * esz;
+    const int per_round = (int)std::min<int64_t>(std::min<int64_t>((int64_t)c->wav_cap / Lmax, c->max_rows), (int64_t)c->meta_cap / 3);
+    std::vector<int32_t> pos_host;
+    for (int i0 = 0; i0 < n; i0 += per_round) {
+        const int nb = std::min(per_round, n - i0);
+        const int k = c->meta_next;            // [samples nb][speed nb][stretched samples nb] through the page-locked meta ring
+        c->meta_next = (k + 1) % ntts_codec::kMetaStages;
+        if (c->meta_used[k]) CHIP(c, hipEventSynchronize(c->meta_ev[k]));
+        int* m = c->meta_host[k];
+        memcpy(m, n_samples + i0, (size_t)nb * sizeof(int));
+        memcpy(m + nb, speed_permille + i0, (size_t)nb * sizeof(int));
+        for (int i = 0; i < nb; ++i) m[2 * nb + i] = (int)stretch_len(n_samples[i0 + i], speed_permille[i0 + i]);
+        CHIP(c, hipMemcpyAsync(c->meta, m, 3 * (size_t)nb * sizeof(int), hipMemcpyHostToDevice, st));
+        c->meta_used[k] = true;
+        CHIP(c, hipEventRecord(c->meta_ev[k], st));
+        CHIP(c, hipMemcpy2DAsync(c->wav, (size_t)Lmax * sizeof(float), wav + (size_t)i0 * in_stride, (size_t)in_stride * sizeof(float),
+                                 (size_t)Lmax * sizeof(float), nb, hipMemcpyHostToDevice, st));
+        CHIP(c, hipEventRecord(c->ev[0], st));
+        rc = wav_stretch_launch(c, c->wav, (long)Lmax, c->meta, 1, c->meta + nb, c->meta + 2 * nb, nb, s_max, st);
+        if (rc != NTTS_OK) return rc;
+        const void* src = c->sbuf;
+        if (!w.plain()) {
+            rc = wav_format_launch(c, w, c->sbuf, (long)s_max, c->meta + 2 * nb, 1, nb, row_len, st);
+            if (rc != NTTS_OK) return rc;
+            src = c->fbuf;
+        }
+        CHIP(c, hipEventRecord(c->ev[1], st));
+        c->have_time = true;
+        CHIP(c, hipMemcpy2DAsync((char*)out + (size_t)i0 * out_stride * esz, (size_t)out_stride * esz, src, row_bytes, row_bytes, nb,
+                                 hipMemcpyDeviceToHost, st));
+        if (positions) {
+            pos_host.resize((size_t)nb * k_max);
+            CHIP(c, hipMemcpyAsync(pos_host.data(), c->spos, pos_host.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        }
+        CHIP(c, hipStreamSynchronize(st));
+        CHIP(c, hipGetLastError());
+        if (positions)                         // row i receives its own K_i positions, nothing behind them
+            for (int i = 0; i < nb; ++i)
+                memcpy(positions + (size_t)(i0 + i) * pos_stride, pos_host.data() + (size_t)i * k_max,
+                       (size_t)stretch_frames(m[2 * nb + i]) * sizeof(int32_t));
+    }
+    return NTTS_OK;
+}
+
+// GPU milliseconds of the two kernels of the most recent time stretch (search, render)
+extern "C" int ntts_codec_last_stretch_timing(ntts_codec* c, float* search_ms, float* render_ms) {
+    if (!c || !search_ms || !render_ms) return NTTS_EINVAL;
+    if (!c->have_stretch_time) return cfail(c, NTTS_ESTATE, "no time stretch has run on this engine");
+    CHIP(c, hipSetDevice(c->device));
+    CHIP(c, hipEventSynchronize(c->ev_s[2]));
+    CHIP(c, hipEventElapsedTime(search_ms, c->ev_s[0], c->ev_s[1]));
+    CHIP(c, hipEventElapsedTime(render_ms, c->ev_s[1], c->ev_s[2]));
     return NTTS_OK;
 }
 

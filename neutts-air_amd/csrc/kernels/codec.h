@@ -830,4 +830,122 @@ NTTS_KERNEL(256) void wav_stream_kernel(WavStreamArgs p, int job0, int phase) {
     for (int x = blockIdx.y * 256 + threadIdx.x; x < keep; x += gridDim.y * 256) nv[x] = wav_stream_input(j, pv, nx, h0 + x);
 }
 
+// ---- time stretch between overlap-add and the output stage: speed without a pitch shift (WSOLA at 24 kHz) ---------------------------------------
+// The reference has no such stage (a codec-token model has no duration input; ref:neutts/neutts.py:288-291 hands out what the tokens say).  Speed is
+// an integer per mille pm in [500, 2000]; n_out = ceil(n_in * 1000 / pm) and K = ceil(n_out / kStretchHop) output frames are host arithmetic.
+// Frame 0 is x[0 .. hop); frame k >= 1 continues at t_k = p_{k-1} + hop unless a position near a_k = (k * hop * pm + 500) / 1000 matches better:
+// the candidates c in [clamp(a_k - kStretchDelta), clamp(a_k + kStretchDelta)], clamp to [0, max(0, n_in - kStretchWin)], are scored by
+// D(c) = sum_{i < hop} |s[t_k + i] - s[c + i]| on s = wav_pcm16(x) (integers: no order of additions), p_k minimises (D, |c - t_k|, c), and
+// out[k * hop + i] = fma(f[i], x[p_k + i] - x[t_k + i], x[t_k + i]) -- the input itself wherever p_k == t_k.  x and s are zero outside [0, n_in) of
+// their OWN utterance.  pm = 1000 copies the row.  tests/time_stretch_spec.py is the contract.
+constexpr int kStretchWin = 720, kStretchHop = 360, kStretchDelta = 240;
+constexpr int kStretchCand = 2 * kStretchDelta + 1;                  // 481 candidates at most: two per thread
+constexpr int kStretchSpan = 2 * kStretchDelta + kStretchHop;        // 840 staged samples of the candidate window
+constexpr int kStretchImg = 864;                                     // 16-bit elements per LDS image: >= kStretchSpan + 2, and 432 words = 16 mod 32, so the
+                                                                     // even and the odd image of adjacent candidates fall into different ds_read_b32 banks
+struct WavStretchArgs {
+    const float* in;       // [B][in_stride] 24 kHz float32
+    long in_stride;
+    const int* lens;       // [B]; utterance b holds lens[b] * len_mul input samples (as WavFormatArgs)
+    int len_mul;
+    const int* pm;         // [B] speed per mille
+    const int* n_out;      // [B] ceil(n_in * 1000 / pm)
+    int* pos;              // [B][pos_stride]: p_0 .. p_{K-1}
+    long pos_stride;
+    const float* fade;     // [kStretchHop] fp32
+    float* out;            // [B][out_stride] 24 kHz float32
+    long out_stride;
+};
+// the search signal, biased by +32768 into 16 unsigned bits (the differences are the same; v_sad_u16 wants unsigned operands)
+NTTS_D unsigned short stretch_s16(const float* x, long n_in, long idx) {
+    return (unsigned short)((idx >= 0 && idx < n_in ? wav_pcm16(x[idx]) : 0) + 32768);
+}
+// sum of |a[i] - b[i]| over kStretchHop 16-bit values, both 4-byte aligned
+NTTS_D unsigned int stretch_sad(const unsigned short* a, const unsigned short* b) {
+    unsigned int acc = 0;
+#if !defined(NTTS_EMU)
+    const unsigned int* a2 = (const unsigned int*)a;
+    const unsigned int* b2 = (const unsigned int*)b;
+#pragma unroll 12
+    for (int i = 0; i < kStretchHop / 2; ++i) acc = __builtin_amdgcn_sad_u16(a2[i], b2[i], acc);     // v_sad_u16: both halves of the pair
+#else
+    for (int i = 0; i < kStretchHop; ++i) acc += (unsigned int)(a[i] > b[i] ? a[i] - b[i] : b[i] - a[i]);
+#endif
+    return acc;
+}
+// (D, |c - t|, c) as two words that compare in tuple order: D, then dist << 9 | (c - c_lo)   (c - c_lo < 512, dist < 2^22)
+NTTS_D bool stretch_less(unsigned int d0, unsigned int k0, unsigned int d1, unsigned int k1) { return d0 < d1 || (d0 == d1 && k0 < k1); }
+// grid (B): one workgroup walks its utterance's frames in order (p_k needs p_{k-1})
+NTTS_KERNEL(256) void wav_stretch_search_kernel(WavStretchArgs p) {
+    NTTS_SHARED unsigned short ref[kStretchHop + 8];
+    NTTS_SHARED unsigned short img[2][kStretchImg];       // img[0][j] = s[c_lo + j], img[1][j] = s[c_lo + j + 1]: an odd offset reads aligned pairs from img[1]
+    NTTS_SHARED unsigned int red[2][4];
+    const int b = blockIdx.x;
+    const long n_in = (long)p.lens[b] * p.len_mul;
+    const int pm = p.pm[b];
+    const int K = (p.n_out[b] + kStretchHop - 1) / kStretchHop;
+    int* pos = p.pos + (long)b * p.pos_stride;
+    if (pm == 1000) {                                      // a copy: position k * hop by definition (block-uniform: no barrier is reached)
+        for (int k = threadIdx.x; k < K; k += 256) pos[k] = k * kStretchHop;
+        return;
+    }
+    const float* x = p.in + (long)b * p.in_stride;
+    const long pmax = n_in > kStretchWin ? n_in - kStretchWin : 0;
+    if (threadIdx.x == 0 && K > 0) pos[0] = 0;
+    long prev = 0;
+    for (int k = 1; k < K; ++k) {
+        const long t = prev + kStretchHop;
+        const long a = ((long)k * kStretchHop * pm + 500) / 1000;
+        long c_lo = a - kStretchDelta, c_hi = a + kStretchDelta;
+        c_lo = c_lo < 0 ? 0 : c_lo > pmax ? pmax : c_lo;
+        c_hi = c_hi < 0 ? 0 : c_hi > pmax ? pmax : c_hi;
+        const int n_cand = (int)(c_hi - c_lo) + 1;          // 1 .. kStretchCand
+        for (int i = threadIdx.x; i < kStretchHop; i += 256) ref[i] = stretch_s16(x, n_in, t + i);
+        for (int i = threadIdx.x; i < n_cand + kStretchHop; i += 256) {      // one sample more than the window: img[1]'s last
+            const unsigned short v = stretch_s16(x, n_in, c_lo + i);
+            if (i < n_cand + kStretchHop - 1) img[0][i] = v;
+            if (i > 0) img[1][i - 1] = v;
+        }
+        sync();
+        unsigned int bd = 0xffffffffu, bk = 0xffffffffu;
+        for (int j = threadIdx.x; j < n_cand; j += 256) {
+            const unsigned int d = stretch_sad(ref, (j & 1) ? &img[1][j - 1] : &img[0][j]);
+            const long dist = c_lo + j > t ? c_lo + j - t : t - (c_lo + j);
+            const unsigned int key = ((unsigned int)dist << 9) | (unsigned int)j;
+            if (stretch_less(d, key, bd, bk)) { bd = d; bk = key; }
+        }
+        for (int m = 32; m >= 1; m >>= 1) {
+            const unsigned int od = (unsigned int)shfl_xor((int)bd, m), ok = (unsigned int)shfl_xor((int)bk, m);
+            if (stretch_less(od, ok, bd, bk)) { bd = od; bk = ok; }
+        }
+        if (lane_id() == 0) { red[0][threadIdx.x >> 6] = bd; red[1][threadIdx.x >> 6] = bk; }
+        sync();                                             // (also: everybody is done with ref / img before the next frame overwrites them)
+        bd = red[0][0]; bk = red[1][0];
+        for (int w = 1; w < 4; ++w)
+            if (stretch_less(red[0][w], red[1][w], bd, bk)) { bd = red[0][w]; bk = red[1][w]; }
+        prev = c_lo + (long)(bk & 511u);
+        if (threadIdx.x == 0) pos[k] = (int)prev;
+    }
+}
+// grid (B, ceil(longest output / 256)): output sample m of frame k = m / hop
+NTTS_KERNEL(256) void wav_stretch_render_kernel(WavStretchArgs p) {
+    const int b = blockIdx.x;
+    const long n_in = (long)p.lens[b] * p.len_mul;
+    const long m = (long)blockIdx.y * 256 + threadIdx.x;
+    if (m >= p.n_out[b]) return;
+    const float* x = p.in + (long)b * p.in_stride;
+    float y;
+    if (p.pm[b] == 1000) {
+        y = x[m];                                           // n_out == n_in
+    } else {
+        const int k = (int)(m / kStretchHop), i = (int)(m - (long)k * kStretchHop);
+        const int* pos = p.pos + (long)b * p.pos_stride;
+        const long pk = pos[k], tk = k ? (long)pos[k - 1] + kStretchHop : 0;
+        const float xt = tk + i < n_in ? x[tk + i] : 0.f;
+        const float xp = pk + i < n_in ? x[pk + i] : 0.f;
+        y = __builtin_fmaf(p.fade[i], xp - xt, xt);
+    }
+    p.out[(long)b * p.out_stride + m] = y;
+}
+
 }  // namespace ntts

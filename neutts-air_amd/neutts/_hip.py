@@ -167,6 +167,13 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "ntts_codec_decode_fmt": (C.c_int, [p, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(WavFormatC), p, i64, C.POINTER(i32)]),
         "ntts_codec_decode_dev_fmt": (C.c_int, [p, i32, p, i32, C.POINTER(i32), p, i64, i32, p, C.POINTER(WavFormatC), C.POINTER(i32)]),
         "ntts_codec_convert": (C.c_int, [p, i32, C.POINTER(f32), i64, C.POINTER(i32), C.POINTER(WavFormatC), p, i64, C.POINTER(i32)]),
+        "ntts_wav_stretch_len": (C.c_int, [i32, i64, C.POINTER(i64)]),
+        "ntts_codec_stretch": (C.c_int, [p, i32, C.POINTER(f32), i64, C.POINTER(i32), C.POINTER(i32), C.POINTER(WavFormatC), p, i64, C.POINTER(i32),
+                                         C.POINTER(i32), i64]),
+        "ntts_codec_decode_speed": (C.c_int, [p, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(WavFormatC), p, i64, C.POINTER(i32)]),
+        "ntts_codec_decode_dev_speed": (C.c_int, [p, i32, p, i32, C.POINTER(i32), C.POINTER(i32), p, i64, i32, p, C.POINTER(WavFormatC),
+                                                  C.POINTER(i32)]),
+        "ntts_codec_last_stretch_timing": (C.c_int, [p, C.POINTER(f32), C.POINTER(f32)]),
         "ntts_wav_stream_create": (C.c_int, [p, C.POINTER(WavFormatC), i32, i32, C.POINTER(p)]),
         "ntts_wav_stream_destroy": (None, [p]),
         "ntts_wav_stream_last_error": (C.c_char_p, [p]),
@@ -267,6 +274,33 @@ def wav_out_len(n_in: int, sample_rate=None) -> int:
     """Samples at `sample_rate` of n_in samples at 24 kHz: ceil(n_in * rate / 24000) (ntts_wav_out_len's arithmetic)."""
     rate = int(wav_format(sample_rate)[0].sample_rate)
     return -(-int(n_in) * rate // NATIVE_SAMPLE_RATE)
+
+
+# ---- speed: the pitch-preserving time stretch between the codec pass and the output stage (include/neutts_hip.h ntts_codec_stretch)
+SPEED_PERMILLE_MIN, SPEED_PERMILLE_MAX = 500, 2000
+STRETCH_HOP = 360
+
+
+def speed_permille(speed, n: int, who: str = "") -> Optional[np.ndarray]:
+    """Checked speeds of n utterances, one value or one per utterance, as the engine's integers per mille (round(speed * 1000)) -- int32 [n], or
+    None when every utterance runs at 1.0 (None included): the calls of an engine without the stage.  ValueError names the bad value."""
+    if speed is None:
+        return None
+    vals = list(speed) if isinstance(speed, (list, tuple, np.ndarray)) else [speed] * n
+    if len(vals) != n:
+        raise ValueError(f"{who}speed: {len(vals)} values for {n} utterances")
+    pm = np.zeros(n, dtype=np.int32)
+    for i, v in enumerate(vals):
+        ok = not isinstance(v, (bool, np.bool_)) and isinstance(v, (int, float, np.integer, np.floating)) and np.isfinite(v)
+        if not ok or not SPEED_PERMILLE_MIN <= int(round(float(v) * 1000)) <= SPEED_PERMILLE_MAX:
+            raise ValueError(f"{who}speed must be a number in [0.5, 2.0] (got {v!r})")
+        pm[i] = int(round(float(v) * 1000))
+    return None if (pm == 1000).all() else pm
+
+
+def wav_stretch_len(n_in: int, permille: int) -> int:
+    """Samples of n_in samples at a speed per mille: ceil(n_in * 1000 / permille) (ntts_wav_stretch_len's arithmetic)."""
+    return -(-int(n_in) * 1000 // int(permille))
 
 
 @dataclass
@@ -1371,29 +1405,41 @@ class CodecEngine:
             self._pin_ptr, self._pin_cap = ptr, nbytes
         return np.frombuffer((C.c_char * nbytes).from_address(self._pin_ptr.value), dtype=dtype, count=n)
 
-    def _decode_call(self, n: int, flat: np.ndarray, lens: np.ndarray, tmax: int, fmt, reuse_output: bool):
-        """One ntts_codec_decode / ntts_codec_decode_fmt call -> ([n, stride] array of the format's dtype, samples per utterance)."""
+    def _decode_call(self, n: int, flat: np.ndarray, lens: np.ndarray, tmax: int, fmt, reuse_output: bool, pm: Optional[np.ndarray] = None):
+        """One ntts_codec_decode / ntts_codec_decode_fmt / ntts_codec_decode_speed call -> ([n, stride] array of the format's dtype, samples per
+        utterance).  pm: speeds per mille (int32 [n]) or None."""
         fc, dtype, native = fmt
         i32p = C.POINTER(C.c_int32)
-        stride = wav_out_len(self.hop_length * tmax, fc.sample_rate)
+        if pm is None:
+            stride = wav_out_len(self.hop_length * tmax, fc.sample_rate)
+        else:
+            pm = np.ascontiguousarray(pm, dtype=np.int32)
+            stride = wav_out_len(max(wav_stretch_len(self.hop_length * int(t), int(s)) for t, s in zip(lens, pm)), fc.sample_rate)
         wav = (self._pinned(n * stride, dtype) if reuse_output else np.empty(n * stride, dtype=dtype)).reshape(n, stride)
-        if native:        # the plain entry point: the calls and the bits of an engine without the output stage
+        if native and pm is None:        # the plain entry point: the calls and the bits of an engine without the output stage
             self._chk(self.lib.ntts_codec_decode(self.h, n, flat.ctypes.data_as(i32p), lens.ctypes.data_as(i32p),
                                                  wav.ctypes.data_as(C.POINTER(C.c_float)), stride))
             return wav, self.hop_length * lens.astype(np.int64)
         out_lens = np.zeros(n, dtype=np.int32)
-        self._chk(self.lib.ntts_codec_decode_fmt(self.h, n, flat.ctypes.data_as(i32p), lens.ctypes.data_as(i32p), C.byref(fc),
-                                                 C.c_void_p(wav.ctypes.data), stride, out_lens.ctypes.data_as(i32p)))
+        if pm is None:
+            self._chk(self.lib.ntts_codec_decode_fmt(self.h, n, flat.ctypes.data_as(i32p), lens.ctypes.data_as(i32p), C.byref(fc),
+                                                     C.c_void_p(wav.ctypes.data), stride, out_lens.ctypes.data_as(i32p)))
+        else:
+            self._chk(self.lib.ntts_codec_decode_speed(self.h, n, flat.ctypes.data_as(i32p), lens.ctypes.data_as(i32p), pm.ctypes.data_as(i32p),
+                                                       C.byref(fc), C.c_void_p(wav.ctypes.data), stride, out_lens.ctypes.data_as(i32p)))
         return wav, out_lens
 
     def decode(self, codes: Sequence[Sequence[int]], reuse_output: bool = False, sample_rate=None, encoding="f32",
-               filter_width=None) -> List[np.ndarray]:
+               filter_width=None, speed=None) -> List[np.ndarray]:
         """codes: one int sequence per utterance -> list of waveforms: float32 at 24 kHz, hop_length * len samples each, by default;
         sample_rate (one of WAV_RATES) / encoding ("f32", "pcm16" -> int16, "mulaw" -> uint8) / filter_width (the resampler's
         lowpass_filter_width, 1..64, default 6) put the device output stage behind the pass: ceil(hop_length * len * rate / 24000) samples.
+        speed (0.5 .. 2.0, one value or one per utterance; None = 1.0) puts the time stretch between the pass and the output stage: the pitch stays,
+        the utterance takes ceil(hop_length * len / speed) samples at 24 kHz (ntts_codec_decode_speed).
         reuse_output=True returns views into an engine-owned pinned buffer (fast D2H, no copy): they are only valid
         until the next decode() call on this engine."""
         fmt = wav_format(sample_rate, encoding, filter_width)
+        pm = speed_permille(speed, len(codes))
         out: List[Optional[np.ndarray]] = [None] * len(codes)
         order = sorted(range(len(codes)), key=lambda i: -len(codes[i]))   # batch similar lengths together
         i = 0
@@ -1404,28 +1450,80 @@ class CodecEngine:
             lens = np.array([len(codes[j]) for j in grp], dtype=np.int32)
             flat = np.ascontiguousarray(np.concatenate([np.asarray(codes[j], dtype=np.int32) for j in grp]))
             # (pinned fast path when a single call covers the batch)
-            wav, out_lens = self._decode_call(len(grp), flat, lens, tmax, fmt, reuse_output and i == 0 and nb == len(order))
+            wav, out_lens = self._decode_call(len(grp), flat, lens, tmax, fmt, reuse_output and i == 0 and nb == len(order),
+                                              None if pm is None else pm[grp])
             for r, j in enumerate(grp):
                 out[j] = wav[r, : int(out_lens[r])]     # view into this call's buffer: no second copy
             i += nb
         return out  # type: ignore[return-value]
 
     def decode_array(self, codes: np.ndarray, lens: Optional[np.ndarray] = None, reuse_output: bool = False, sample_rate=None,
-                     encoding="f32", filter_width=None) -> np.ndarray:
+                     encoding="f32", filter_width=None, speed=None) -> np.ndarray:
         """Batch fast path: codes [n, T] int (row i valid up to lens[i]; all T when lens is None) -> waveforms
         [n, hop_length * T] float32 in ONE engine call (n * (T + 6) must fit max_rows).  reuse_output=True returns a
         view of the engine's pinned staging buffer, valid until the next decode on this engine.  With an output format (as `decode`):
-        [n, wav_out_len(hop_length * T, sample_rate)] of the encoding's dtype, row i valid up to wav_out_len(hop_length * lens[i], sample_rate)."""
+        [n, wav_out_len(hop_length * T, sample_rate)] of the encoding's dtype, row i valid up to wav_out_len(hop_length * lens[i], sample_rate);
+        with speed (as `decode`) the row length is the longest stretched utterance's."""
         fmt = wav_format(sample_rate, encoding, filter_width)
         codes = np.asarray(codes)
         n, T = codes.shape
+        pm = speed_permille(speed, n)
         if lens is None:
             lens = np.full(n, T, dtype=np.int32)
             flat = np.ascontiguousarray(codes, dtype=np.int32).reshape(-1)
         else:
             lens = np.ascontiguousarray(lens, dtype=np.int32)
             flat = np.ascontiguousarray(np.concatenate([codes[i, : lens[i]] for i in range(n)]), dtype=np.int32)
-        return self._decode_call(n, flat, lens, int(lens.max()), fmt, reuse_output)[0]
+        return self._decode_call(n, flat, lens, int(lens.max()), fmt, reuse_output, pm)[0]
+
+    def stretch_array(self, wav: np.ndarray, n_samples, speed, sample_rate=None, encoding="f32", filter_width=None, out_stride: Optional[int] = None,
+                      pos_stride: Optional[int] = None):
+        """The time stretch alone, and the output stage behind it (ntts_codec_stretch): wav [n, in_stride] float32 at 24 kHz, row i valid up to
+        n_samples[i], speed one value or one per row -> ([n, out_stride] array of the encoding's dtype, samples per row, positions [n, pos_stride]
+        int32, frames per row): row i's positions p_0 .. p_{K_i - 1} are the input offsets its output frames of 360 samples were taken from."""
+        fc, dtype, _ = wav_format(sample_rate, encoding, filter_width)
+        wav = np.ascontiguousarray(wav, dtype=np.float32)
+        n, in_stride = wav.shape
+        n_samples = np.ascontiguousarray(n_samples, dtype=np.int32)
+        if len(n_samples) != n:
+            raise ValueError(f"n_samples: {len(n_samples)} values for {n} waveforms")
+        pm = speed_permille(speed, n)
+        if pm is None:
+            pm = np.full(n, 1000, dtype=np.int32)
+        s_len = [wav_stretch_len(max(0, int(v)), int(s)) for v, s in zip(n_samples, pm)]
+        if out_stride is None:
+            out_stride = wav_out_len(max(s_len) if n else 0, fc.sample_rate)
+        if pos_stride is None:
+            pos_stride = -(-(max(s_len) if n else 0) // STRETCH_HOP)
+        out_stride, pos_stride = int(out_stride), int(pos_stride)
+        buf = np.zeros(max(1, n * max(0, out_stride)), dtype=dtype)       # (never a null pointer, even for n rows of no samples)
+        pos = np.full(max(1, n * max(0, pos_stride)), -1, dtype=np.int32)
+        out_lens = np.zeros(n, dtype=np.int32)
+        i32p = C.POINTER(C.c_int32)
+        self._chk(self.lib.ntts_codec_stretch(self.h, n, wav.ctypes.data_as(C.POINTER(C.c_float)), in_stride, n_samples.ctypes.data_as(i32p),
+                                              pm.ctypes.data_as(i32p), C.byref(fc), C.c_void_p(buf.ctypes.data), out_stride,
+                                              out_lens.ctypes.data_as(i32p), pos.ctypes.data_as(i32p), pos_stride))
+        frames = np.array([-(-v // STRETCH_HOP) for v in s_len], dtype=np.int32)
+        return buf[: n * out_stride].reshape(n, out_stride), out_lens, pos[: n * pos_stride].reshape(n, pos_stride), frames
+
+    def stretch(self, wavs: Sequence[np.ndarray], speed, sample_rate=None, encoding="f32", filter_width=None) -> List[np.ndarray]:
+        """24 kHz float waveforms (one 1-D array each; e.g. what a watermarker handed back) -> the same `speed` times faster, pitch kept, in the
+        output format: what `decode` with these arguments would have produced from them."""
+        wavs = [np.asarray(w, dtype=np.float32).reshape(-1) for w in wavs]
+        if not wavs:
+            return []
+        n_samples = np.array([len(w) for w in wavs], dtype=np.int32)
+        buf = np.zeros((len(wavs), max(1, int(n_samples.max()))), dtype=np.float32)
+        for r, w in enumerate(wavs):
+            buf[r, : len(w)] = w
+        out, out_lens, _, _ = self.stretch_array(buf, n_samples, speed, sample_rate, encoding, filter_width)
+        return [out[r, : int(out_lens[r])] for r in range(len(wavs))]
+
+    def last_stretch_timing(self):
+        """GPU milliseconds (search kernel, render kernel) of the most recent time stretch on this engine."""
+        a, b = C.c_float(), C.c_float()
+        self._chk(self.lib.ntts_codec_last_stretch_timing(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     def convert_array(self, wav: np.ndarray, n_samples, sample_rate=None, encoding="f32", filter_width=None, out_stride: Optional[int] = None):
         """The output stage alone (ntts_codec_convert): wav [n, in_stride] float32 at 24 kHz, row i valid up to n_samples[i] (what follows is
@@ -1484,15 +1582,21 @@ class CodecEngine:
 
     def decode_device(self, codes_dev_ptr: int, codes_stride: int, lens: np.ndarray, producer_stream: int = 0,
                       wav_dev_ptr: Optional[int] = None, wav_stride: Optional[int] = None, reuse_output: bool = True,
-                      sample_rate=None, encoding="f32", filter_width=None):
+                      sample_rate=None, encoding="f32", filter_width=None, speed=None):
         """Codes already on the device (BackboneEngine.export_codes) -> waveforms, asynchronously: returns the [n, stride]
         destination (a view of the engine's pinned host buffer, or None when `wav_dev_ptr` names a device buffer);
         call sync() before reading it.  float32 at 24 kHz by default; with an output format (as `decode`) elements of the encoding's dtype,
-        stride = wav_out_len(hop_length * max(lens), sample_rate) unless given, row i valid up to wav_out_len(hop_length * lens[i], sample_rate)."""
+        stride = wav_out_len(hop_length * max(lens), sample_rate) unless given, row i valid up to wav_out_len(hop_length * lens[i], sample_rate).
+        With speed (as `decode`; ntts_codec_decode_dev_speed) the lengths are those of the stretched utterances."""
         fc, dtype, native = wav_format(sample_rate, encoding, filter_width)
         lens = np.ascontiguousarray(lens, dtype=np.int32)
         n = len(lens)
-        stride = int(wav_stride or wav_out_len(self.hop_length * int(lens.max()), fc.sample_rate))
+        pm = speed_permille(speed, n)
+        if pm is None:
+            longest = self.hop_length * int(lens.max())
+        else:
+            longest = max(wav_stretch_len(self.hop_length * int(t), int(s)) for t, s in zip(lens, pm))
+        stride = int(wav_stride or wav_out_len(longest, fc.sample_rate))
         wav = None
         if wav_dev_ptr is None:
             wav = self._pinned(n * stride, dtype).reshape(n, stride)
@@ -1500,14 +1604,19 @@ class CodecEngine:
         else:
             dst, on_dev = wav_dev_ptr, 1
         i32p = C.POINTER(C.c_int32)
-        if native:
+        if native and pm is None:
             self._chk(self.lib.ntts_codec_decode_dev(self.h, n, C.c_void_p(codes_dev_ptr), codes_stride, lens.ctypes.data_as(i32p),
                                                      C.c_void_p(dst), stride, on_dev, C.c_void_p(producer_stream or None)))
-        else:
+        elif pm is None:
             out_lens = np.zeros(n, dtype=np.int32)
             self._chk(self.lib.ntts_codec_decode_dev_fmt(self.h, n, C.c_void_p(codes_dev_ptr), codes_stride, lens.ctypes.data_as(i32p),
                                                          C.c_void_p(dst), stride, on_dev, C.c_void_p(producer_stream or None), C.byref(fc),
                                                          out_lens.ctypes.data_as(i32p)))
+        else:
+            out_lens = np.zeros(n, dtype=np.int32)
+            self._chk(self.lib.ntts_codec_decode_dev_speed(self.h, n, C.c_void_p(codes_dev_ptr), codes_stride, lens.ctypes.data_as(i32p),
+                                                           pm.ctypes.data_as(i32p), C.c_void_p(dst), stride, on_dev,
+                                                           C.c_void_p(producer_stream or None), C.byref(fc), out_lens.ctypes.data_as(i32p)))
         return wav
 
     def sync(self):

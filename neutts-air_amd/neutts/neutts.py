@@ -230,6 +230,7 @@ class NeuTTS:
         stream_sample_rate: int = 24_000,
         stream_encoding: str = "f32",
         stream_filter_width: Optional[int] = None,
+        speed: float = 1.0,
     ):
         # Consts (ref:neutts/neutts.py:84-91)
         self.sample_rate = 24_000            # the NATIVE rate (the codec's; what a watermarker sees), whatever the output format
@@ -250,6 +251,12 @@ class NeuTTS:
         self.stream_sample_rate = int(stream_sample_rate)
         self.stream_encoding = stream_encoding
         self.stream_filter_width = None if stream_filter_width is None else int(stream_filter_width)
+        # How fast the voice speaks, 0.5 .. 2.0 (a codec-token model has no duration input: the reference offers nothing, its users resample, which
+        # moves the pitch).  A pitch-preserving time stretch (WSOLA) on the device between the codec pass and the output stage (include/neutts_hip.h
+        # ntts_codec_decode_speed): an utterance takes ceil(samples / speed) samples at 24 kHz.  speed= per call overrides it, one value or one per
+        # utterance; the stream entry points take 1.0 only.
+        _hip.speed_permille(speed, 1)
+        self.speed = float(speed)
         self.max_context = 2048
         self.hop_length = 480
         self.streaming_overlap_frames = 1
@@ -457,13 +464,15 @@ class NeuTTS:
         min_p override the instance's sampling attributes for this call (None = the attribute), and so do the two further keywords every entry
         point takes behind them: repetition_penalty= and repetition_ignore_prompt= (anything else is a TypeError).
         best_of=N: N sampled candidates, the one with the highest mean log-probability is synthesised; return_scores=True: (wav, score).
-        sample_rate= / encoding= (two more keywords of the catch-all) override output_sample_rate / output_encoding for this call."""
+        sample_rate= / encoding= (two more keywords of the catch-all) override output_sample_rate / output_encoding for this call, speed= (0.5 .. 2.0)
+        the instance's speed."""
         out = self._resolve_output(repetition.pop("sample_rate", None), repetition.pop("encoding", None))
+        speed = self._resolve_speed(repetition.pop("speed", None), 1)
         best_of, want = self._pop_scoring(1, repetition, "return_scores")
         samp = self._resolve_sampling(1, temperature, top_k, top_p, min_p, repetition)
         prompt_ids = self._apply_chat_template(ref_codes, ref_text, text)
         ids, lps = self._generate_scored([prompt_ids], samp, best_of, want)
-        if out is None:
+        if out is None and speed is None:
             wav = self._decode_ids(ids[0])
             if self.watermarker is not None:
                 wav = self.watermarker.apply_watermark(wav, sample_rate=24_000)
@@ -471,15 +480,17 @@ class NeuTTS:
             speech_ids = self._ids_to_codes(ids[0])
             if len(speech_ids) == 0:
                 raise ValueError("No valid speech tokens found in the output.")
-            wav = self._decode_formatted([speech_ids], out)[0]
+            wav = self._decode_formatted([speech_ids], out, speed)[0]
         return (wav, sequence_score(lps[0])) if want else wav
 
     def infer_batch(self, texts: Sequence[str], ref_codes, ref_texts, *, temperature=None, top_k=None, top_p=None, min_p=None, **repetition) -> List[np.ndarray]:
         """Many utterances at once: continuous batching over the engine's decode slots (over every engine's, with engines > 1),
         one codec pass.  The sampling overrides take one value for the call or one per utterance, and so does best_of= (candidates per
         utterance; only the winners go through the codec); return_scores=True: (wavs, scores), score = mean log-probability of the ids.
-        sample_rate= / encoding= (two more keywords of the catch-all) override output_sample_rate / output_encoding for this call (one format per call)."""
+        sample_rate= / encoding= (two more keywords of the catch-all) override output_sample_rate / output_encoding for this call (one format per call),
+        speed= the instance's speed: one value, or one per utterance."""
         out = self._resolve_output(repetition.pop("sample_rate", None), repetition.pop("encoding", None))
+        speed = self._resolve_speed(repetition.pop("speed", None), len(texts))
         best_of, want = self._pop_scoring(len(texts), repetition, "return_scores")
         samp = self._resolve_sampling(len(texts), temperature, top_k, top_p, min_p, repetition)
         if not isinstance(ref_texts, (list, tuple)):
@@ -490,12 +501,12 @@ class NeuTTS:
         codes = [self._ids_to_codes(x) for x in ids]
         if any(len(c) == 0 for c in codes):
             raise ValueError("No valid speech tokens found in the output.")
-        if out is None:
+        if out is None and speed is None:
             wavs = self.codec.engine.decode(codes)
             if self.watermarker is not None:
                 wavs = [self.watermarker.apply_watermark(w, sample_rate=24_000) for w in wavs]
         else:
-            wavs = self._decode_formatted(codes, out)
+            wavs = self._decode_formatted(codes, out, speed)
         return (wavs, [sequence_score(lp) for lp in lps]) if want else wavs
 
     def infer_stream(self, text: str, ref_codes, ref_text: str, *, temperature=None, top_k=None, top_p=None, min_p=None, **repetition) -> Generator[np.ndarray, None, None]:
@@ -504,6 +515,7 @@ class NeuTTS:
         stream_filter_width= (or the instance's stream_* attributes) say otherwise; sample_rate= / encoding= / a non-native output_* attribute
         stay a ValueError here."""
         self._refuse_stream_output(repetition.pop("sample_rate", None), repetition.pop("encoding", None), "infer_stream")
+        self._refuse_stream_speed(repetition.pop("speed", None), "infer_stream")
         fmt = self._resolve_stream_output(repetition.pop("stream_sample_rate", None), repetition.pop("stream_encoding", None),
                                           repetition.pop("stream_filter_width", None))
         samp = self._resolve_sampling(1, temperature, top_k, top_p, min_p, repetition)
@@ -521,6 +533,7 @@ class NeuTTS:
         At most `max_batch` utterances (the engine's decode slots) per call.  Sampling overrides as `infer_batch`.  Chunk format as
         `infer_stream`: stream_sample_rate= / stream_encoding= / stream_filter_width=, one format per call."""
         self._refuse_stream_output(repetition.pop("sample_rate", None), repetition.pop("encoding", None), "infer_stream_batch")
+        self._refuse_stream_speed(repetition.pop("speed", None), "infer_stream_batch")
         fmt = self._resolve_stream_output(repetition.pop("stream_sample_rate", None), repetition.pop("stream_encoding", None),
                                           repetition.pop("stream_filter_width", None))
         samp = self._resolve_sampling(len(texts), temperature, top_k, top_p, min_p, repetition)
@@ -751,12 +764,31 @@ class NeuTTS:
             return x[(x >= 0) & (x < 65536)].astype(np.int32)
         return np.asarray(self._ids_to_codes(np.asarray(ids).tolist()), dtype=np.int32)
 
-    def decode_codes(self, codes: Sequence[Sequence[int]], sample_rate=None, encoding=None) -> List[np.ndarray]:
-        """Codec codes -> waveforms in the instance's output format (sample_rate= / encoding= override it for this call); no watermark, as before."""
+    def decode_codes(self, codes: Sequence[Sequence[int]], sample_rate=None, encoding=None, speed=None) -> List[np.ndarray]:
+        """Codec codes -> waveforms in the instance's output format and at the instance's speed (sample_rate= / encoding= / speed= override them for
+        this call; speed one value or one per utterance); no watermark, as before."""
         out = self._resolve_output(sample_rate, encoding)
-        if out is None:
+        speed = self._resolve_speed(speed, len(codes))
+        if out is None and speed is None:
             return self.codec.engine.decode(codes)
-        return self.codec.engine.decode(codes, sample_rate=out[0], encoding=out[1], filter_width=out[2])
+        if out is None:
+            return self.codec.engine.decode(codes, speed=speed)
+        return self.codec.engine.decode(codes, sample_rate=out[0], encoding=out[1], filter_width=out[2], speed=speed)
+
+    def _resolve_speed(self, speed, n: int):
+        """Per-call speed: None = the instance attribute.  -> None when every utterance runs at 1.0 (the calls of an instance without the stage), else
+        one checked value per utterance.  ValueError on a bad value, before the engine is touched."""
+        given = speed is not None
+        speed = self.speed if speed is None else speed
+        if _hip.speed_permille(speed, n, "" if given else "instance ") is None:
+            return None
+        return [float(v) for v in speed] if isinstance(speed, (list, tuple, np.ndarray)) else [float(speed)] * n
+
+    def _refuse_stream_speed(self, speed, who: str) -> None:
+        if self._resolve_speed(speed, 1) is not None:
+            what = f"speed={speed!r}" if speed is not None else f"speed={self.speed!r} on the instance"
+            raise ValueError(f"{who} speaks at speed 1.0 only (got {what}): the time stretch is a one-shot stage behind infer / infer_batch / "
+                             "decode_codes; a chunked stretch with history on the device does not exist yet")
 
     def _resolve_output(self, sample_rate=None, encoding=None):
         """Per-call output format: None = the instance attribute.  -> None for the native format (24 kHz float32: the calls of an instance without
@@ -808,15 +840,16 @@ class NeuTTS:
         longest = (self.streaming_frames_per_chunk + self.streaming_lookforward + 2 * self.streaming_overlap_frames) * self.hop_length
         return self.codec.engine.stream_converter(n, fmt[0], fmt[1], fmt[2], max_chunk_samples=longest)
 
-    def _decode_formatted(self, codes: Sequence[Sequence[int]], out) -> List[np.ndarray]:
-        """One codec pass with the device output stage behind it.  A watermarker is a host library that works on the 24 kHz float waveform: with
-        one present the order is decode (native), watermark on the host, then the output stage alone (CodecEngine.convert)."""
-        rate, enc, width = out
+    def _decode_formatted(self, codes: Sequence[Sequence[int]], out, speed=None) -> List[np.ndarray]:
+        """One codec pass with the time stretch (speed: None, or one value per utterance) and the device output stage (out: None = native) behind it.
+        A watermarker is a host library that works on the 24 kHz float waveform: with one present the order is decode with the speed in the native
+        format, watermark on the host, then the output stage alone (CodecEngine.convert)."""
         eng = self.codec.engine
+        fmt = {} if out is None else dict(sample_rate=out[0], encoding=out[1], filter_width=out[2])
         if self.watermarker is None:
-            return eng.decode(codes, sample_rate=rate, encoding=enc, filter_width=width)
-        wavs = [self.watermarker.apply_watermark(w, sample_rate=24_000) for w in eng.decode(codes)]
-        return eng.convert(wavs, sample_rate=rate, encoding=enc, filter_width=width)
+            return eng.decode(codes, speed=speed, **fmt)
+        wavs = [self.watermarker.apply_watermark(w, sample_rate=24_000) for w in eng.decode(codes, speed=speed)]
+        return wavs if out is None else eng.convert(wavs, **fmt)
 
     def _decode_ids(self, ids: Sequence[int]) -> np.ndarray:
         speech_ids = self._ids_to_codes(ids)
