@@ -593,6 +593,36 @@ int ntts_wav_stream_push(ntts_wav_stream* ws, int32_t n, const int32_t* stream, 
                          const int32_t* last, void* out, int64_t out_stride, int32_t* out_lens);
 int ntts_wav_stream_count(const ntts_wav_format* fmt, int64_t n_in_total, int32_t last, int64_t* n_out_total);
 
+/* The time stretch on a signal that arrives in CHUNKS (a stream).  NEW SYMBOLS ONLY: NTTS_ABI_VERSION stays 11.
+ * A stream has one speed pm in [500, 2000] per signal, named with every chunk.  The chunks of a stream at a speed, concatenated, are
+ * ntts_codec_stretch of its concatenated 24 kHz chunks -- positions and samples, bit for bit -- for every chunking (tests/stream_speed_spec.py is
+ * the contract; names as above: frames of 360, search +-240, window 720, a_k = (k * 360 * pm + 500) / 1000).
+ *   Not the last chunk: after N input samples frame k (frame 0 included) is decided and rendered as soon as a_k + 960 <= N.  Then the clamp to
+ *     n_in - 720 cannot bind, the reference window and every candidate window have arrived, and the frame is a whole frame of the final output: its
+ *     position and samples are the one-shot rule's, whatever arrives later.  The stream has emitted F(N) * 360 samples, F(N) = #{k: a_k + 960 <= N}.
+ *   The last chunk: n_in = N is known; the remaining frames follow the one-shot rule as it stands (clamp, zeros behind N, truncation to
+ *     ceil(N * 1000 / pm)).  It may be empty: a pure flush.  The stream is empty afterwards and may start a new signal at another speed.
+ *   Between chunks a stream keeps, ON THE DEVICE, p_{k-1} and the inputs from max(0, min(t_k, a_k - 240, N - 720)) on for its
+ *     next frame k -- at most 1 560 floats, two rows per stream (one read, one written).
+ *   pm = 1000: a copy, no lag, no history, bit for bit.
+ * Output lags input by up to 960 input samples (40 ms) and one frame: a stream's first audio at a speed other than 1 comes that much later, only
+ * its last chunk is longer for it, and a chunk may be empty.
+ * ntts_speed_stream: that stage alone for `n_streams` independent streams of HOST chunks, the output format `fmt` (NULL / zeroed = 24 kHz
+ * float32) behind it with its own history -- the streaming twin of ntts_codec_stretch.
+ * ntts_speed_stream_push: as ntts_wav_stream_push, entry i at speed_permille[i]; out_lens[i] ELEMENTS of the format go to row i of `out`
+ * (out_stride elements apart).  pos (may be NULL): the positions decided in this call, row i (pos_stride apart), n_pos[i] of them (at 1000: k * 360
+ * of the frames that begin in the chunk).  Refused with NTTS_EINVAL and a message (ntts_speed_stream_last_error), nothing run and no stream moved: a
+ * speed outside [500, 2000]; a speed other than the one the stream's current signal began with; and what ntts_wav_stream_push refuses.  Blocking.
+ * ntts_speed_stream_count: 24 kHz samples a stream at that speed has emitted in all after n_in_total inputs; pure host arithmetic. */
+typedef struct ntts_speed_stream ntts_speed_stream;
+int ntts_speed_stream_create(ntts_codec* c, const ntts_wav_format* fmt, int32_t n_streams, int32_t max_chunk_samples, ntts_speed_stream** out);
+void ntts_speed_stream_destroy(ntts_speed_stream* ss);
+const char* ntts_speed_stream_last_error(const ntts_speed_stream* ss);
+int ntts_speed_stream_push(ntts_speed_stream* ss, int32_t n, const int32_t* stream, const int32_t* speed_permille, const float* wav, int64_t in_stride,
+                           const int32_t* n_samples, const int32_t* last, void* out, int64_t out_stride, int32_t* out_lens,
+                           int32_t* pos, int64_t pos_stride, int32_t* n_pos);
+int ntts_speed_stream_count(int32_t speed_permille, int64_t n_in_total, int32_t last, int64_t* n_out_total);
+
 /* ------------------------------------------------------------------------------------------ */
 /* Device-side streaming (ABI 6): the per-chunk post-process of infer_stream for `n` concurrent    */
 /* utterances -- token cache, window assembly, the 27-frame slice and the triangular cross-fade    */
@@ -644,6 +674,13 @@ int ntts_streams_done(ntts_streams* s, int32_t* n_done);
 int ntts_streams_set_format(ntts_streams* s, const ntts_wav_format* fmt);
 int ntts_streams_pump_end_fmt(ntts_streams* s, int32_t cap, int32_t* n_chunks, int32_t* chunk_stream, int32_t* chunk_samples, int32_t* chunk_last,
                               const void** chunks, int64_t* row_stride, int32_t* n_running, int32_t* more);
+/* Chunks at a speed (the chunked time stretch above; NEW SYMBOLS ONLY).  ntts_streams_set_speed: speed_permille[i] of stream i, each in
+ * [500, 2000] (NTTS_EINVAL otherwise); NULL = all 1000.  Legal until the first pump_begin (NTTS_ESTATE after), in either order with set_format.
+ * With a speed other than 1000 in the set the stage runs behind the cross-fade, ahead of the output format's stage if there is one; buffers and
+ * the D2H copy are sized for the stretched rows.  A stream's chunks then lag by up to 40 ms and a frame, may be empty, and a stream that ends
+ * on a window's edge gets a flush chunk of its own.  Both pump_end variants serve a set with speeds in the native format.  A set all at 1000
+ * makes the launches and copies it made before and returns the same bits. */
+int ntts_streams_set_speed(ntts_streams* s, const int32_t* speed_permille);
 
 /* ------------------------------------------------------------------------------------------ */
 /* NeuCodec ENCODER engine: reference enrolment.  Replaces                                       */

@@ -1250,6 +1250,294 @@ extern "C" int ntts_wav_stream_push(ntts_wav_stream* ws, int32_t n, const int32_
     return NTTS_OK;
 }
 
+// ---- the chunked time stretch (wav_stream.h; kernels/codec.h wav_stretch_stream_kernel; tests/stream_speed_spec.py is the contract): per-stream
+// counts on the host, history rows and state records on the device, shared by ntts_speed_stream_* below and ntts_streams_set_speed (stream.cpp)
+struct ntts::SpeedStreamCore {
+    ntts_codec* c = nullptr;
+    int n = 0, max_chunk = 0, max_jobs = 0;
+    long out_stride = 0, pos_stride = 0;
+    std::vector<int64_t> N;                           // per stream: input samples of its current signal
+    std::vector<int> pm, parity;                      // its speed (0 between signals); the history row its next job reads
+    float* hist = nullptr;                            // device [2][n][kSpeedHist]
+    SpeedStreamState* state = nullptr;                // device [n]
+    float* fade = nullptr;                            // device [kStretchHop]
+    float* out = nullptr;                             // device [max_jobs][out_stride]
+    int* pos = nullptr;                               // device [max_jobs][pos_stride]
+    SpeedStreamJob* jobs_dev = nullptr;
+    SpeedStreamJob* jobs_host = nullptr;              // page-locked
+};
+
+// F(N): the frames decided after N samples of a signal that has not ended: a_k + kSpeedLag <= N  <=>  k * hop * pm <= (N - kSpeedLag + 1) * 1000 - 501
+static int64_t speed_frames_ready(int64_t N, int pm) {
+    return N < kSpeedLag ? 0 : ((N - kSpeedLag + 1) * 1000 - 501) / ((int64_t)kStretchHop * pm) + 1;
+}
+int64_t ntts::speed_stream_count_of(int pm, int64_t N, bool last) {
+    if (pm == 1000) return N;
+    return last ? stretch_len(N, pm) : speed_frames_ready(N, pm) * kStretchHop;
+}
+// the most one chunk can emit: its last one, which also brings what the lag held back (stream_speed_spec.chunk_out_max)
+int64_t ntts::speed_chunk_out_max(int64_t max_chunk_samples, int pm) {
+    return pm == 1000 ? max_chunk_samples : stretch_len(max_chunk_samples + kSpeedLag, pm) + 1;
+}
+
+void ntts::speed_core_destroy(SpeedStreamCore* k) {
+    if (!k) return;
+    hipSetDevice(k->c->device);
+    hipStreamSynchronize(k->c->stream);
+    for (void* b : {(void*)k->hist, (void*)k->state, (void*)k->fade, (void*)k->out, (void*)k->pos, (void*)k->jobs_dev})
+        if (b) hipFree(b);
+    if (k->jobs_host) hipHostFree(k->jobs_host);
+    delete k;
+}
+
+int ntts::speed_core_create(ntts_codec* c, int n_streams, int max_chunk_samples, int pm_min, int max_jobs, SpeedStreamCore** out) {
+    if (!c || !out) return NTTS_EINVAL;
+    if (n_streams < 1) return cfail(c, NTTS_EINVAL, "speed stream: n_streams %d < 1", n_streams);
+    if (max_chunk_samples < 1) return cfail(c, NTTS_EINVAL, "speed stream: max_chunk_samples %d < 1", max_chunk_samples);
+    if (max_jobs < 1) return cfail(c, NTTS_EINVAL, "speed stream: max_jobs %d < 1", max_jobs);
+    if (pm_min < 500 || pm_min > 2000) return cfail(c, NTTS_EINVAL, "speed stream: speed %d per mille outside [500, 2000]", pm_min);
+    SpeedStreamCore* k = new SpeedStreamCore();
+    k->c = c; k->n = n_streams; k->max_chunk = max_chunk_samples; k->max_jobs = max_jobs;
+    k->N.assign(n_streams, 0); k->pm.assign(n_streams, 0); k->parity.assign(n_streams, 0);
+    k->out_stride = (long)std::max<int64_t>(max_chunk_samples, speed_chunk_out_max(max_chunk_samples, pm_min < 1000 ? pm_min : 999));
+    k->pos_stride = (k->out_stride + kStretchHop - 1) / kStretchHop + 1;
+    int rc = NTTS_OK;
+#define KHIP(call)                                                                                        \
+    do {                                                                                                  \
+        hipError_t _s = (call);                                                                           \
+        if (_s != hipSuccess) {                                                                           \
+            rc = cfail(c, _s == 2 ? NTTS_ENOMEM : NTTS_EHIP, "%s failed: %s", #call, hipGetErrorString(_s)); \
+            speed_core_destroy(k);                                                                        \
+            return rc;                                                                                    \
+        }                                                                                                 \
+    } while (0)
+    KHIP(hipSetDevice(c->device));
+    KHIP(hipMalloc((void**)&k->hist, 2 * (size_t)n_streams * kSpeedHist * sizeof(float)));
+    KHIP(hipMemset(k->hist, 0, 2 * (size_t)n_streams * kSpeedHist * sizeof(float)));
+    KHIP(hipMalloc((void**)&k->state, (size_t)n_streams * sizeof(SpeedStreamState)));
+    KHIP(hipMemset(k->state, 0, (size_t)n_streams * sizeof(SpeedStreamState)));
+    {
+        std::vector<float> f(kStretchHop);
+        for (int i = 0; i < kStretchHop; ++i) f[i] = (float)(0.5 - 0.5 * cos(M_PI * (i + 0.5) / kStretchHop));
+        KHIP(hipMalloc((void**)&k->fade, f.size() * sizeof(float)));
+        KHIP(hipMemcpy(k->fade, f.data(), f.size() * sizeof(float), hipMemcpyHostToDevice));
+    }
+    KHIP(hipMalloc((void**)&k->out, (size_t)max_jobs * k->out_stride * sizeof(float)));
+    KHIP(hipMemset(k->out, 0, (size_t)max_jobs * k->out_stride * sizeof(float)));
+    KHIP(hipMalloc((void**)&k->pos, (size_t)max_jobs * k->pos_stride * sizeof(int)));
+    KHIP(hipMemset(k->pos, 0, (size_t)max_jobs * k->pos_stride * sizeof(int)));
+    KHIP(hipMalloc((void**)&k->jobs_dev, (size_t)max_jobs * sizeof(SpeedStreamJob)));
+    KHIP(hipHostMalloc((void**)&k->jobs_host, (size_t)max_jobs * sizeof(SpeedStreamJob), hipHostMallocDefault));
+#undef KHIP
+    *out = k;
+    return NTTS_OK;
+}
+
+long ntts::speed_core_out_stride(const SpeedStreamCore* k) { return k->out_stride; }
+long ntts::speed_core_pos_stride(const SpeedStreamCore* k) { return k->pos_stride; }
+float* ntts::speed_core_out(const SpeedStreamCore* k) { return k->out; }
+int* ntts::speed_core_pos(const SpeedStreamCore* k) { return k->pos; }
+int ntts::speed_core_pm(const SpeedStreamCore* k, int u) { return k->pm[u]; }
+int64_t ntts::speed_core_total(const SpeedStreamCore* k, int u) { return k->N[u]; }
+
+int64_t ntts::speed_core_peek(const SpeedStreamCore* k, int u, int pm, int n_new, bool last) {
+    return speed_stream_count_of(pm, k->N[u] + n_new, last) - speed_stream_count_of(pm, k->N[u], false);
+}
+
+int64_t ntts::speed_core_plan(SpeedStreamCore* k, int job, int u, int pm, int n_new, bool last, int phase, int* k0, int* k1) {
+    const int64_t N0 = k->N[u], N1 = N0 + n_new;
+    const int64_t M0 = speed_stream_count_of(pm, N0, false), M1 = speed_stream_count_of(pm, N1, last);
+    SpeedStreamJob& j = k->jobs_host[job];
+    j.n_before = (long)N0; j.m0 = (long)M0; j.m1 = (long)M1; j.u = u; j.pm = pm; j.n_new = n_new;
+    // (at 1000 the frames that BEGIN in this chunk: their positions are k * hop by definition, host arithmetic of the caller)
+    j.k0 = (int)(pm == 1000 ? stretch_frames(N0) : M0 / kStretchHop); j.k1 = (int)stretch_frames(M1);
+    j.parity = k->parity[u]; j.last = last ? 1 : 0; j.phase = phase;
+    if (k0) *k0 = j.k0;
+    if (k1) *k1 = j.k1;
+    if (last) { k->N[u] = 0; k->pm[u] = 0; }           // the stream is empty again and may start a new signal, at another speed
+    else { k->N[u] = N1; k->pm[u] = pm; }
+    if (pm != 1000) k->parity[u] ^= 1;
+    return M1 - M0;
+}
+
+int ntts::speed_core_run(SpeedStreamCore* k, int n_jobs, const float* in_dev, long in_stride, hipStream_t st) {
+    ntts_codec* c = k->c;
+    if (n_jobs < 1) return NTTS_OK;
+    if (n_jobs > k->max_jobs) return cfail(c, NTTS_EINVAL, "speed stream: %d jobs exceed the %d it was created for", n_jobs, k->max_jobs);
+    // The rows are sized for the longest chunk at the slowest speed: checked, not assumed, before anything is written.  The plans have already moved
+    // the streams' counts, so a caller must not let this fire: ntts_speed_stream_push refuses an entry above max_chunk_samples before it plans, and
+    // a stream set's chunks are at most the out_stride the core was created for (chunk_out_max bounds what either can emit).
+    for (int j = 0; j < n_jobs; ++j) {
+        const SpeedStreamJob& q = k->jobs_host[j];
+        if (q.m1 - q.m0 > k->out_stride || q.n_new > in_stride || q.n_new < 0 || q.k1 - q.k0 > k->pos_stride || q.u < 0 || q.u >= k->n)
+            return cfail(c, NTTS_EINVAL, "speed stream: job %d (%d samples in, %ld out, %d frames) exceeds its rows", j, q.n_new, q.m1 - q.m0, q.k1 - q.k0);
+    }
+    CHIP(c, hipMemcpyAsync(k->jobs_dev, k->jobs_host, (size_t)n_jobs * sizeof(SpeedStreamJob), hipMemcpyHostToDevice, st));
+    SpeedStreamArgs a{};
+    a.jobs = k->jobs_dev; a.in = in_dev; a.in_stride = in_stride; a.hist = k->hist; a.state = k->state; a.n_streams = k->n; a.fade = k->fade;
+    a.out = k->out; a.out_stride = k->out_stride; a.pos = k->pos; a.pos_stride = k->pos_stride;
+    // a stream's two jobs of one round depend on each other through its history row and state record: two launches, phase 0 first
+    for (int phase = 0; phase < 2; ++phase) {
+        int lo = -1, hi = -1;
+        for (int j = 0; j < n_jobs; ++j)
+            if (k->jobs_host[j].phase == phase) {
+                if (lo < 0) lo = j;
+                hi = j;
+            }
+        if (lo < 0) continue;
+        NTTS_LAUNCH((wav_stretch_stream_kernel), dim3(hi - lo + 1), dim3(256), st, a, lo, phase);
+    }
+    return NTTS_OK;
+}
+
+// ---- ntts_speed_stream_*: the chunked stretch alone on host chunks, the output format behind it: the streaming twin of ntts_codec_stretch
+struct ntts_speed_stream {
+    ntts_codec* c = nullptr;
+    SpeedStreamCore* k = nullptr;
+    WavStreamCore* w = nullptr;          // the output stage behind the stretch; null for 24 kHz float32
+    int n = 0, max_chunk = 0;
+    float* in_dev = nullptr;             // [n][max_chunk]
+    std::vector<int> seen;               // per stream: the call that named it last (repeats within one call)
+    std::vector<int> k0, k1, pos_host;
+    int call = 0;
+    std::string err;
+};
+static std::string g_speed_stream_err;
+static int ssfail(ntts_speed_stream* ss, int code, const char* fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    if (ss) ss->err = buf; else g_speed_stream_err = buf;
+    return code;
+}
+extern "C" const char* ntts_speed_stream_last_error(const ntts_speed_stream* ss) { return ss ? ss->err.c_str() : g_speed_stream_err.c_str(); }
+
+extern "C" void ntts_speed_stream_destroy(ntts_speed_stream* ss) {
+    if (!ss) return;
+    if (ss->w) wav_core_destroy(ss->w);
+    if (ss->k) speed_core_destroy(ss->k);
+    if (ss->in_dev) hipFree(ss->in_dev);
+    delete ss;
+}
+
+extern "C" int ntts_speed_stream_create(ntts_codec* c, const ntts_wav_format* fmt, int32_t n_streams, int32_t max_chunk_samples, ntts_speed_stream** out) {
+    if (!c || !out) return ssfail(nullptr, NTTS_EINVAL, "null argument");
+    ntts_speed_stream* ss = new ntts_speed_stream();
+    ss->c = c; ss->n = n_streams; ss->max_chunk = max_chunk_samples;
+    // a stream names its speed with its first chunk: the rows are sized for the slowest one
+    int rc = speed_core_create(c, n_streams, max_chunk_samples, 500, n_streams, &ss->k);
+    if (rc == NTTS_OK) rc = wav_core_create(c, fmt, n_streams, (int)speed_core_out_stride(ss->k), n_streams, &ss->w);
+    if (rc != NTTS_OK) { rc = ssfail(nullptr, rc, "%s", c->err.c_str()); ntts_speed_stream_destroy(ss); return rc; }
+    if (wav_core_plain(ss->w)) { wav_core_destroy(ss->w); ss->w = nullptr; }
+    if (hipMalloc((void**)&ss->in_dev, (size_t)n_streams * max_chunk_samples * sizeof(float)) != hipSuccess) {
+        (void)hipGetLastError();
+        ntts_speed_stream_destroy(ss);
+        return ssfail(nullptr, NTTS_ENOMEM, "speed stream: no device memory for %d x %d samples", n_streams, max_chunk_samples);
+    }
+    ss->seen.assign(n_streams, 0);
+    ss->k0.assign(n_streams, 0); ss->k1.assign(n_streams, 0);
+    *out = ss;
+    return NTTS_OK;
+}
+
+extern "C" int ntts_speed_stream_count(int32_t speed_permille, int64_t n_in_total, int32_t last, int64_t* n_out_total) {
+    if (!n_out_total || n_in_total < 0) return ssfail(nullptr, NTTS_EINVAL, "ntts_speed_stream_count: null / negative argument");
+    if (speed_permille < 500 || speed_permille > 2000)
+        return ssfail(nullptr, NTTS_EINVAL, "ntts_speed_stream_count: speed %d per mille outside [500, 2000]", speed_permille);
+    *n_out_total = speed_stream_count_of(speed_permille, n_in_total, last != 0);
+    return NTTS_OK;
+}
+
+extern "C" int ntts_speed_stream_push(ntts_speed_stream* ss, int32_t n, const int32_t* stream, const int32_t* speed_permille, const float* wav,
+                                      int64_t in_stride, const int32_t* n_samples, const int32_t* last, void* out, int64_t out_stride, int32_t* out_lens,
+                                      int32_t* pos, int64_t pos_stride, int32_t* n_pos) {
+    if (!ss) return NTTS_EINVAL;
+    if (n < 1 || !stream || !speed_permille || !wav || !n_samples || !last || !out || !out_lens || in_stride < 0 || (pos && (!n_pos || pos_stride < 0)))
+        return ssfail(ss, NTTS_EINVAL, "null/empty argument");
+    // ---- every refusal first: nothing is run and no stream's state moves
+    ++ss->call;
+    int64_t Lmax = 0, Omax = 0, Kmax = 0;
+    bool any = false;
+    for (int i = 0; i < n; ++i) {
+        const int u = stream[i], pm = speed_permille[i];
+        if (u < 0 || u >= ss->n) return ssfail(ss, NTTS_EINVAL, "entry %d: stream %d outside [0, %d)", i, u, ss->n);
+        if (ss->seen[u] == ss->call) return ssfail(ss, NTTS_EINVAL, "entry %d: stream %d is named twice in one call", i, u);
+        ss->seen[u] = ss->call;
+        if (n_samples[i] < 0 || n_samples[i] > in_stride)
+            return ssfail(ss, NTTS_EINVAL, "entry %d: n_samples %d outside [0, in_stride %ld]", i, n_samples[i], (long)in_stride);
+        if (n_samples[i] > ss->max_chunk) return ssfail(ss, NTTS_EINVAL, "entry %d: n_samples %d above max_chunk_samples %d", i, n_samples[i], ss->max_chunk);
+        if (pm < 500 || pm > 2000) return ssfail(ss, NTTS_EINVAL, "entry %d: speed %d per mille outside [500, 2000]", i, pm);
+        if (speed_core_pm(ss->k, u) && speed_core_pm(ss->k, u) != pm)
+            return ssfail(ss, NTTS_EINVAL, "entry %d: speed %d per mille, but stream %d's signal began at %d: a stream keeps its speed until its last chunk", i,
+                          pm, u, speed_core_pm(ss->k, u));
+        if (speed_core_total(ss->k, u) + n_samples[i] >= (int64_t)1 << 30)
+            return ssfail(ss, NTTS_EINVAL, "entry %d: stream %d's signal exceeds 2^30 samples", i, u);
+        const int64_t s = speed_core_peek(ss->k, u, pm, n_samples[i], last[i] != 0);
+        any = any || pm != 1000;
+        Lmax = std::max<int64_t>(Lmax, n_samples[i]);
+        Omax = std::max(Omax, ss->w ? wav_core_peek(ss->w, u, (int)s, last[i] != 0) : s);
+        const int64_t f0 = pm == 1000 ? stretch_frames(speed_core_total(ss->k, u)) : speed_stream_count_of(pm, speed_core_total(ss->k, u), false) / kStretchHop;
+        Kmax = std::max(Kmax, stretch_frames(speed_stream_count_of(pm, speed_core_total(ss->k, u) + n_samples[i], last[i] != 0)) - f0);
+    }
+    if (out_stride < Omax) return ssfail(ss, NTTS_EINVAL, "out_stride %ld < %ld samples", (long)out_stride, (long)Omax);
+    if (pos && pos_stride < Kmax) return ssfail(ss, NTTS_EINVAL, "pos_stride %ld < %ld frames", (long)pos_stride, (long)Kmax);
+    for (int i = 0; i < n; ++i) {
+        const int64_t s = speed_core_plan(ss->k, i, stream[i], speed_permille[i], n_samples[i], last[i] != 0, 0, &ss->k0[i], &ss->k1[i]);
+        out_lens[i] = (int32_t)(ss->w ? wav_core_plan(ss->w, i, stream[i], (int)s, last[i] != 0, 0) : s);
+        if (n_pos) n_pos[i] = ss->k1[i] - ss->k0[i];
+    }
+    if (pos)                                // unit speed: position k * hop by definition
+        for (int i = 0; i < n; ++i)
+            for (int k = ss->k0[i]; k < ss->k1[i] && speed_permille[i] == 1000; ++k) pos[(size_t)i * pos_stride + (k - ss->k0[i])] = k * kStretchHop;
+    if (!any && !ss->w) {                   // every entry at 1000 in the native format: nothing to compute, nothing is launched
+        for (int i = 0; i < n; ++i) memcpy((float*)out + (size_t)i * out_stride, wav + (size_t)i * in_stride, (size_t)n_samples[i] * sizeof(float));
+        return NTTS_OK;
+    }
+    ntts_codec* c = ss->c;
+#define WHIP(call)                                                                                           \
+    do {                                                                                                     \
+        hipError_t _s = (call);                                                                              \
+        if (_s != hipSuccess) return ssfail(ss, NTTS_EHIP, "%s failed: %s", #call, hipGetErrorString(_s));    \
+    } while (0)
+    WHIP(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    if (Lmax > 0)
+        WHIP(hipMemcpy2DAsync(ss->in_dev, (size_t)ss->max_chunk * sizeof(float), wav, (size_t)in_stride * sizeof(float), (size_t)Lmax * sizeof(float), n,
+                              hipMemcpyHostToDevice, st));
+    const float* src = ss->in_dev;          // all at 1000: the stretch is not launched, the chunks go to the output stage as they are
+    long src_stride = ss->max_chunk;
+    if (any) {
+        const int rc = speed_core_run(ss->k, n, ss->in_dev, ss->max_chunk, st);     // (also with no output at all: histories and states move on)
+        if (rc != NTTS_OK) return ssfail(ss, rc, "%s", c->err.c_str());
+        src = speed_core_out(ss->k); src_stride = speed_core_out_stride(ss->k);
+    }
+    size_t esz = sizeof(float);
+    const void* res = src;
+    long res_stride = src_stride;
+    if (ss->w) {
+        const int rc = wav_core_run(ss->w, n, src, src_stride, st);
+        if (rc != NTTS_OK) return ssfail(ss, rc, "%s", c->err.c_str());
+        esz = wav_core_esz(ss->w); res = wav_core_out(ss->w); res_stride = wav_core_out_stride(ss->w);
+    }
+    if (Omax > 0)
+        WHIP(hipMemcpy2DAsync(out, (size_t)out_stride * esz, res, (size_t)res_stride * esz, (size_t)Omax * esz, n, hipMemcpyDeviceToHost, st));
+    const long ps = speed_core_pos_stride(ss->k);
+    if (pos && any) {
+        ss->pos_host.resize((size_t)n * ps);
+        WHIP(hipMemcpyAsync(ss->pos_host.data(), speed_core_pos(ss->k), (size_t)n * ps * sizeof(int), hipMemcpyDeviceToHost, st));
+    }
+    WHIP(hipStreamSynchronize(st));
+    WHIP(hipGetLastError());
+#undef WHIP
+    if (pos && any)
+        for (int i = 0; i < n; ++i)
+            if (speed_permille[i] != 1000)
+                for (int k = 0; k < ss->k1[i] - ss->k0[i]; ++k) pos[(size_t)i * pos_stride + k] = ss->pos_host[(size_t)i * ps + k];
+    return NTTS_OK;
+}
+
 extern "C" int ntts_codec_set_cu_mask(ntts_codec* c, const uint32_t* mask, int32_t n_words) {
     if (!c || n_words < 0 || (n_words > 0 && !mask)) return cfail(c, NTTS_EINVAL, "bad CU mask");
     CHIP(c, hipSetDevice(c->device));

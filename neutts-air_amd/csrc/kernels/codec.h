@@ -875,6 +875,46 @@ NTTS_D unsigned int stretch_sad(const unsigned short* a, const unsigned short* b
 }
 // (D, |c - t|, c) as two words that compare in tuple order: D, then dist << 9 | (c - c_lo)   (c - c_lo < 512, dist < 2^22)
 NTTS_D bool stretch_less(unsigned int d0, unsigned int k0, unsigned int d1, unsigned int k1) { return d0 < d1 || (d0 == d1 && k0 < k1); }
+// The search of one frame k >= 1 by the whole workgroup: the reference window at t, the candidates around a clamped to [0, pmax], the two images
+// in LDS, one v_sad_u16 chain per candidate, the workgroup's argmin of (D, |c - t|, c).  s16(idx) is the search signal at input sample idx.  Every
+// thread returns p_k; the barrier before the result also frees ref / img for the next frame.
+template <typename S16>
+NTTS_D long stretch_search_frame(const S16& s16, long t, long a, long pmax, unsigned short* ref, unsigned short (*img)[kStretchImg],
+                                 unsigned int (*red)[4]) {
+    long c_lo = a - kStretchDelta, c_hi = a + kStretchDelta;
+    c_lo = c_lo < 0 ? 0 : c_lo > pmax ? pmax : c_lo;
+    c_hi = c_hi < 0 ? 0 : c_hi > pmax ? pmax : c_hi;
+    const int n_cand = (int)(c_hi - c_lo) + 1;          // 1 .. kStretchCand
+    for (int i = threadIdx.x; i < kStretchHop; i += 256) ref[i] = s16(t + i);
+    for (int i = threadIdx.x; i < n_cand + kStretchHop; i += 256) {      // one sample more than the window: img[1]'s last
+        const unsigned short v = s16(c_lo + i);
+        if (i < n_cand + kStretchHop - 1) img[0][i] = v;
+        if (i > 0) img[1][i - 1] = v;
+    }
+    sync();
+    unsigned int bd = 0xffffffffu, bk = 0xffffffffu;
+    for (int j = threadIdx.x; j < n_cand; j += 256) {
+        const unsigned int d = stretch_sad(ref, (j & 1) ? &img[1][j - 1] : &img[0][j]);
+        const long dist = c_lo + j > t ? c_lo + j - t : t - (c_lo + j);
+        const unsigned int key = ((unsigned int)dist << 9) | (unsigned int)j;
+        if (stretch_less(d, key, bd, bk)) { bd = d; bk = key; }
+    }
+    for (int m = 32; m >= 1; m >>= 1) {
+        const unsigned int od = (unsigned int)shfl_xor((int)bd, m), ok = (unsigned int)shfl_xor((int)bk, m);
+        if (stretch_less(od, ok, bd, bk)) { bd = od; bk = ok; }
+    }
+    if (lane_id() == 0) { red[0][threadIdx.x >> 6] = bd; red[1][threadIdx.x >> 6] = bk; }
+    sync();                                             // (also: everybody is done with ref / img before the next frame overwrites them)
+    bd = red[0][0]; bk = red[1][0];
+    for (int w = 1; w < 4; ++w)
+        if (stretch_less(red[0][w], red[1][w], bd, bk)) { bd = red[0][w]; bk = red[1][w]; }
+    return c_lo + (long)(bk & 511u);
+}
+struct StretchRowS16 {     // the search signal of a whole row in memory
+    const float* x;
+    long n_in;
+    NTTS_D unsigned short operator()(long idx) const { return stretch_s16(x, n_in, idx); }
+};
 // grid (B): one workgroup walks its utterance's frames in order (p_k needs p_{k-1})
 NTTS_KERNEL(256) void wav_stretch_search_kernel(WavStretchArgs p) {
     NTTS_SHARED unsigned short ref[kStretchHop + 8];
@@ -889,41 +929,12 @@ NTTS_KERNEL(256) void wav_stretch_search_kernel(WavStretchArgs p) {
         for (int k = threadIdx.x; k < K; k += 256) pos[k] = k * kStretchHop;
         return;
     }
-    const float* x = p.in + (long)b * p.in_stride;
+    const StretchRowS16 s16{p.in + (long)b * p.in_stride, n_in};
     const long pmax = n_in > kStretchWin ? n_in - kStretchWin : 0;
     if (threadIdx.x == 0 && K > 0) pos[0] = 0;
     long prev = 0;
     for (int k = 1; k < K; ++k) {
-        const long t = prev + kStretchHop;
-        const long a = ((long)k * kStretchHop * pm + 500) / 1000;
-        long c_lo = a - kStretchDelta, c_hi = a + kStretchDelta;
-        c_lo = c_lo < 0 ? 0 : c_lo > pmax ? pmax : c_lo;
-        c_hi = c_hi < 0 ? 0 : c_hi > pmax ? pmax : c_hi;
-        const int n_cand = (int)(c_hi - c_lo) + 1;          // 1 .. kStretchCand
-        for (int i = threadIdx.x; i < kStretchHop; i += 256) ref[i] = stretch_s16(x, n_in, t + i);
-        for (int i = threadIdx.x; i < n_cand + kStretchHop; i += 256) {      // one sample more than the window: img[1]'s last
-            const unsigned short v = stretch_s16(x, n_in, c_lo + i);
-            if (i < n_cand + kStretchHop - 1) img[0][i] = v;
-            if (i > 0) img[1][i - 1] = v;
-        }
-        sync();
-        unsigned int bd = 0xffffffffu, bk = 0xffffffffu;
-        for (int j = threadIdx.x; j < n_cand; j += 256) {
-            const unsigned int d = stretch_sad(ref, (j & 1) ? &img[1][j - 1] : &img[0][j]);
-            const long dist = c_lo + j > t ? c_lo + j - t : t - (c_lo + j);
-            const unsigned int key = ((unsigned int)dist << 9) | (unsigned int)j;
-            if (stretch_less(d, key, bd, bk)) { bd = d; bk = key; }
-        }
-        for (int m = 32; m >= 1; m >>= 1) {
-            const unsigned int od = (unsigned int)shfl_xor((int)bd, m), ok = (unsigned int)shfl_xor((int)bk, m);
-            if (stretch_less(od, ok, bd, bk)) { bd = od; bk = ok; }
-        }
-        if (lane_id() == 0) { red[0][threadIdx.x >> 6] = bd; red[1][threadIdx.x >> 6] = bk; }
-        sync();                                             // (also: everybody is done with ref / img before the next frame overwrites them)
-        bd = red[0][0]; bk = red[1][0];
-        for (int w = 1; w < 4; ++w)
-            if (stretch_less(red[0][w], red[1][w], bd, bk)) { bd = red[0][w]; bk = red[1][w]; }
-        prev = c_lo + (long)(bk & 511u);
+        prev = stretch_search_frame(s16, prev + kStretchHop, ((long)k * kStretchHop * pm + 500) / 1000, pmax, ref, img, red);
         if (threadIdx.x == 0) pos[k] = (int)prev;
     }
 }
@@ -946,6 +957,114 @@ NTTS_KERNEL(256) void wav_stretch_render_kernel(WavStretchArgs p) {
         y = __builtin_fmaf(p.fade[i], xp - xt, xt);
     }
     p.out[(long)b * p.out_stride + m] = y;
+}
+
+// ---- the same stretch on a signal that arrives in chunks (ntts_speed_stream_*, ntts_streams_set_speed) ---------------------------------------------
+// A stream at pm has received N samples.  Frame k (frame 0 included) is decided and rendered once a_k + kStretchDelta + kStretchWin <= N: the clamp
+// to n_in - kStretchWin cannot bind then, the reference window and every candidate window have arrived, and the frame is a whole frame of the final
+// output -- position and samples are the one-shot rule's, whatever arrives later.  The last chunk knows n_in = N and runs the remaining frames as
+// the one-shot kernels do (clamp, zeros behind N, truncation to n_out).  Between chunks the stream keeps, on the device, its state record
+// (p_{k-1}, history length) and the inputs from h0 = max(0, min(t_k, a_k - kStretchDelta, N - kStretchWin)) on -- at most kSpeedHist -- in one of
+// two rows: a job reads `parity` and writes the other (as WavStreamArgs.hist).  The host plans a job from counts alone (frames_ready is arithmetic);
+// the positions never leave the device unless the caller asks for them.  pm = 1000 copies the chunk.  tests/stream_speed_spec.py is the contract.
+constexpr int kSpeedLag = kStretchDelta + kStretchWin;     // 960
+constexpr int kSpeedHist = 1560;                           // t_k >= a_k - 601, N <= a_k + 959
+struct SpeedStreamJob {
+    long n_before;         // input samples of the stream before this chunk
+    long m0, m1;           // output samples before / after it: the job writes m1 - m0 floats
+    int u;                 // the stream: its history rows and state record
+    int pm;                // speed per mille
+    int n_new;             // samples of this chunk
+    int k0, k1;            // the frames this job decides and renders: [k0, k1)
+    int parity;            // which of the two history rows the job reads
+    int last;              // the stream's final chunk: inputs behind it are zero, state and history start again
+    int phase;             // the launch this job belongs to (as WavStreamJob)
+};
+struct SpeedStreamState {  // per stream, written by its job, read by its next one (the frames done are host arithmetic: the job's k0)
+    int p_prev;            // p_{k-1}
+    int n_hist;            // samples in the history row: the inputs [N - n_hist, N)
+};
+struct SpeedStreamArgs {
+    const SpeedStreamJob* jobs;
+    const float* in;       // [jobs][in_stride]: every job's new samples
+    long in_stride;
+    float* hist;           // [2][n_streams][kSpeedHist]
+    SpeedStreamState* state;   // [n_streams]
+    int n_streams;
+    const float* fade;     // [kStretchHop] fp32
+    float* out;            // [jobs][out_stride] 24 kHz float32
+    long out_stride;
+    int* pos;              // [jobs][pos_stride]: p_{k0} .. p_{k1-1}
+    long pos_stride;
+};
+struct SpeedStreamInput {  // input sample idx of the job's stream: the chunk from n_before on, the history row below it, zero outside [0, N)
+    const float* pv;
+    const float* nx;
+    long n_before, N;
+    int n_hist;
+    NTTS_D float at(long idx) const {
+        if (idx < 0 || idx >= N) return 0.f;
+        if (idx >= n_before) return nx[idx - n_before];
+        const long h = idx - (n_before - n_hist);
+        return h >= 0 ? pv[h] : 0.f;      // (never below the row: the history starts at the lowest sample a later frame can read)
+    }
+    NTTS_D unsigned short operator()(long idx) const { return (unsigned short)(wav_pcm16(at(idx)) + 32768); }
+};
+// grid (jobs of the launch): one workgroup walks its job's frames in order; jobs job0 .. job0 + gridDim.x - 1, those of `phase`
+NTTS_KERNEL(256) void wav_stretch_stream_kernel(SpeedStreamArgs p, int job0, int phase) {
+    NTTS_SHARED unsigned short ref[kStretchHop + 8];
+    NTTS_SHARED unsigned short img[2][kStretchImg];
+    NTTS_SHARED unsigned int red[2][4];
+    const int jb = job0 + blockIdx.x;
+    const SpeedStreamJob j = p.jobs[jb];
+    if (j.phase != phase) return;                             // (block-uniform)
+    const float* nx = p.in + (long)jb * p.in_stride;
+    float* out = p.out + (long)jb * p.out_stride;
+    if (j.pm == 1000) {                                       // a copy: no lag, no history, no state
+        for (int i = threadIdx.x; i < j.n_new; i += 256) out[i] = nx[i];
+        return;
+    }
+    const SpeedStreamState st = p.state[j.u];
+    sync();                                                   // everybody has the record before thread 0 replaces it (a job may have no frame)
+    const int n_hist = st.n_hist < 0 ? 0 : st.n_hist > kSpeedHist ? kSpeedHist : st.n_hist;      // (never past the row, whatever the record says)
+    const float* pv = p.hist + ((long)j.parity * p.n_streams + j.u) * kSpeedHist;
+    float* nv = p.hist + ((long)(j.parity ^ 1) * p.n_streams + j.u) * kSpeedHist;
+    const long N = j.n_before + j.n_new;
+    const SpeedStreamInput x{pv, nx, j.n_before, N, n_hist};
+    // a chunk that is not the last decides only frames the clamp cannot reach: a_k + kStretchDelta <= N - kStretchWin
+    const long pmax = N > kStretchWin ? N - kStretchWin : 0;
+    int* pos = p.pos ? p.pos + (long)jb * p.pos_stride : nullptr;
+    long prev = st.p_prev;
+    for (int k = j.k0; k < j.k1; ++k) {
+        long t = 0, pk = 0;
+        if (k > 0) {
+            t = prev + kStretchHop;
+            pk = stretch_search_frame(x, t, ((long)k * kStretchHop * j.pm + 500) / 1000, pmax, ref, img, red);
+        }
+        for (int i = threadIdx.x; i < kStretchHop; i += 256) {       // the frame's samples, in the same pass
+            const long m = (long)k * kStretchHop + i;
+            if (m >= j.m0 && m < j.m1 && m - j.m0 < p.out_stride) {
+                const float xt = x.at(t + i), xp = x.at(pk + i);
+                out[m - j.m0] = __builtin_fmaf(p.fade[i], xp - xt, xt);
+            }
+        }
+        if (threadIdx.x == 0 && pos && k - j.k0 < p.pos_stride) pos[k - j.k0] = (int)pk;
+        prev = pk;
+    }
+    if (j.last) {                                             // the stream is empty again
+        if (threadIdx.x == 0) p.state[j.u] = SpeedStreamState{0, 0};
+        return;
+    }
+    // what the next frame k1 (and a last chunk's clamp) can still read of the inputs so far, into the other row
+    const long t_next = j.k1 > 0 ? prev + kStretchHop : 0;
+    const long a_next = ((long)j.k1 * kStretchHop * j.pm + 500) / 1000 - kStretchDelta;
+    long h0 = t_next < a_next ? t_next : a_next;
+    h0 = h0 < N - kStretchWin ? h0 : N - kStretchWin;
+    h0 = h0 > 0 ? h0 : 0;
+    long keep = N - h0;                                       // <= kSpeedHist
+    if (keep > kSpeedHist) { h0 = N - kSpeedHist; keep = kSpeedHist; }      // (never past the row)
+    for (int i = threadIdx.x; i < keep; i += 256) nv[i] = x.at(h0 + i);
+    if (threadIdx.x == 0) p.state[j.u] = SpeedStreamState{(int)prev, (int)keep};
 }
 
 }  // namespace ntts

@@ -51,7 +51,13 @@ struct ntts_streams {
     std::vector<int> n_dec, prev_len, frames, done;
     // output format of the chunks (ntts_streams_set_format): the chunked output stage behind the cross-fade; null = 24 kHz float32
     WavStreamCore* fmt = nullptr;
-    bool pumped = false;                            // a pump has begun: the format is fixed
+    ntts_wav_format fmt_desc{};                     // what set_format was given (the stage is rebuilt when the speeds change the length of its rows)
+    bool has_fmt = false;
+    // speed of the chunks (ntts_streams_set_speed): the chunked time stretch behind the cross-fade, ahead of the output stage; null = all at 1000
+    SpeedStreamCore* spd = nullptr;
+    std::vector<int> speed;                         // per mille, per stream; empty = all 1000
+    size_t out_host_bytes = 0;
+    bool pumped = false;                            // a pump has begun: format and speeds are fixed
     std::string err;
 };
 
@@ -79,6 +85,7 @@ extern "C" void ntts_streams_destroy(ntts_streams* s) {
     if (s->cst) hipStreamSynchronize(s->cst);
     if (s->est) hipStreamSynchronize(s->est);
     if (s->fmt) wav_core_destroy(s->fmt);
+    if (s->spd) speed_core_destroy(s->spd);
     for (void* b : {(void*)s->ibuf, (void*)s->win, (void*)s->wav_win, (void*)s->prev, (void*)s->out_dev, (void*)s->jobs_dev, (void*)s->parity_dev})
         if (b) hipFree(b);
     for (void* b : {(void*)s->snap_host, (void*)s->out_host, (void*)s->jobs_host, (void*)s->parity_host})
@@ -162,6 +169,7 @@ extern "C" int ntts_streams_create(ntts_backbone* e, ntts_codec* c, const ntts_s
     SCR(hipMalloc((void**)&s->parity_dev, (size_t)J * sizeof(int)));
     SCR(hipHostMalloc((void**)&s->snap_host, 2 * (size_t)n * sizeof(int), hipHostMallocDefault));
     SCR(hipHostMalloc((void**)&s->out_host, (size_t)J * s->out_stride * sizeof(float), hipHostMallocDefault));
+    s->out_host_bytes = (size_t)J * s->out_stride * sizeof(float);
     SCR(hipHostMalloc((void**)&s->jobs_host, (size_t)J * sizeof(StreamJob), hipHostMallocDefault));
     SCR(hipHostMalloc((void**)&s->parity_host, (size_t)J * sizeof(int), hipHostMallocDefault));
     SCR(hipEventCreateWithFlags(&s->ev_snap, hipEventDisableTiming));
@@ -204,32 +212,74 @@ extern "C" int ntts_streams_pump_wait(ntts_streams* s, int32_t* n_running) {
     return NTTS_OK;
 }
 
+// The stages behind the cross-fade, built from s->speed and s->fmt_desc: the chunked time stretch when a stream is not at 1000, then the chunked
+// output stage for a non-native format, on rows as long as the stage before it can emit; the page-locked buffer holds 2 n rows of the last one's.
+// On failure the set keeps the stages it had.
+static int build_stages(ntts_streams* s) {
+    SHIP(s, hipSetDevice(s->device));
+    SpeedStreamCore* spd = nullptr;
+    WavStreamCore* k = nullptr;
+    int pm_min = 1000;
+    bool any = false;
+    for (int pm : s->speed) { any = any || pm != 1000; pm_min = pm < pm_min ? pm : pm_min; }
+    if (any) {
+        const int rc = speed_core_create(s->c, s->n, (int)s->out_stride, pm_min, 2 * s->n, &spd);
+        if (rc != NTTS_OK) return sfail(s, rc, "%s", ntts_codec_last_error(s->c));
+    }
+    const long rows = spd ? speed_core_out_stride(spd) : s->out_stride;
+    const int rc = wav_core_create(s->c, s->has_fmt ? &s->fmt_desc : nullptr, s->n, (int)rows, 2 * s->n, &k);
+    if (rc != NTTS_OK) { speed_core_destroy(spd); return sfail(s, rc, "%s", ntts_codec_last_error(s->c)); }
+    if (wav_core_plain(k)) { wav_core_destroy(k); k = nullptr; }
+    // (48 kHz float32 is the largest format: twice its input row; half speed doubles the row before it)
+    const size_t need = 2 * (size_t)s->n * (k ? wav_core_out_stride(k) * wav_core_esz(k) : rows * sizeof(float));
+    if (need > s->out_host_bytes) {
+        float* nb = nullptr;
+        if (hipHostMalloc((void**)&nb, need, hipHostMallocDefault) != hipSuccess) {
+            (void)hipGetLastError();
+            wav_core_destroy(k);
+            speed_core_destroy(spd);
+            return sfail(s, NTTS_ENOMEM, "no page-locked memory for %zu bytes of chunks", need);
+        }
+        hipHostFree(s->out_host);
+        s->out_host = nb;
+        s->out_host_bytes = need;
+    }
+    if (s->fmt) wav_core_destroy(s->fmt);
+    if (s->spd) speed_core_destroy(s->spd);
+    s->fmt = k;
+    s->spd = spd;
+    return NTTS_OK;
+}
+
 // The output format of the set's chunks: legal until the first pump_begin.  A non-native format puts the chunked output stage (kernels/codec.h
 // wav_stream_kernel, one history row per stream) behind the cross-fade; the native one (zeroed or null) takes it away again.
 extern "C" int ntts_streams_set_format(ntts_streams* s, const ntts_wav_format* fmt) {
     if (!s) return NTTS_EINVAL;
     if (s->pumped) return sfail(s, NTTS_ESTATE, "the format of a stream set is fixed once a pump has begun");
-    SHIP(s, hipSetDevice(s->device));
-    WavStreamCore* k = nullptr;
-    const int rc = wav_core_create(s->c, fmt, s->n, (int)s->out_stride, 2 * s->n, &k);
-    if (rc != NTTS_OK) return sfail(s, rc, "%s", ntts_codec_last_error(s->c));
-    if (s->fmt) wav_core_destroy(s->fmt);
-    s->fmt = nullptr;
-    if (wav_core_plain(k)) { wav_core_destroy(k); return NTTS_OK; }
-    // the page-locked buffer holds 2 n rows of the format's elements (48 kHz float32 is the largest: twice the native row)
-    const size_t need = 2 * (size_t)s->n * wav_core_out_stride(k) * wav_core_esz(k), have = 2 * (size_t)s->n * s->out_stride * sizeof(float);
-    if (need > have) {
-        float* nb = nullptr;
-        if (hipHostMalloc((void**)&nb, need, hipHostMallocDefault) != hipSuccess) {
-            (void)hipGetLastError();
-            wav_core_destroy(k);
-            return sfail(s, NTTS_ENOMEM, "no page-locked memory for %zu bytes of chunks", need);
-        }
-        hipHostFree(s->out_host);
-        s->out_host = nb;
-    }
-    s->fmt = k;
-    return NTTS_OK;
+    const ntts_wav_format old = s->fmt_desc;
+    const bool had = s->has_fmt;
+    s->has_fmt = fmt != nullptr;
+    s->fmt_desc = fmt ? *fmt : ntts_wav_format{};
+    const int rc = build_stages(s);
+    if (rc != NTTS_OK) { s->fmt_desc = old; s->has_fmt = had; }
+    return rc;
+}
+
+// The speed of the set's chunks, per stream: legal until the first pump_begin.  A speed other than 1000 puts the chunked time stretch (kernels/codec.h
+// wav_stretch_stream_kernel: history rows and state records per stream) behind the cross-fade, ahead of the output stage; all 1000 (or null) takes it
+// away again.
+extern "C" int ntts_streams_set_speed(ntts_streams* s, const int32_t* speed_permille) {
+    if (!s) return NTTS_EINVAL;
+    if (s->pumped) return sfail(s, NTTS_ESTATE, "the speeds of a stream set are fixed once a pump has begun");
+    for (int u = 0; u < s->n && speed_permille; ++u)
+        if (speed_permille[u] < 500 || speed_permille[u] > 2000)
+            return sfail(s, NTTS_EINVAL, "stream %d: speed %d per mille outside [500, 2000]", u, speed_permille[u]);
+    std::vector<int> old;
+    old.swap(s->speed);
+    if (speed_permille) s->speed.assign(speed_permille, speed_permille + s->n);
+    const int rc = build_stages(s);
+    if (rc != NTTS_OK) s->speed.swap(old);
+    return rc;
 }
 
 // the round's J windows on the codec's stream: window codes -> codec pass(es) -> cross-fade into out_dev [J][out_stride]
@@ -289,7 +339,8 @@ static int pump_end_impl(ntts_streams* s, int32_t cap, int32_t* n_chunks, int32_
     // ---- which windows exist now (ref:neutts/neutts.py:401-415 / :443-459): per stream at most one regular window per round, and its
     //      final window once it has finished and no regular window is left
     int J = 0, pending = 0, running = 0;
-    std::vector<int> flush;                                 // formatted streams that end without a final window: their held-back outputs
+    std::vector<int> flush;                                 // streams with a stage behind them that end without a final window: their held-back outputs
+    auto pm_of = [&](int u) { return s->spd ? s->speed[u] : 1000; };
     auto add = [&](int u, int t0, int t1, int s0, int n1, bool last) {
         StreamJob& j = s->jobs_host[J];
         const bool hp = s->frames[u] > 0;
@@ -321,7 +372,7 @@ static int pump_end_impl(ntts_streams* s, int32_t cap, int32_t* n_chunks, int32_
                 if (s0 < 0) return sfail(s, NTTS_EINVAL, "stream %d: final window starts before its first frame", u);
                 add(u, t0, clen[u], s0, (clen[u] - t0) * hop - s0, true);
                 s->n_dec[u] = clen[u];
-            } else if (s->fmt && s->frames[u] > 0) {
+            } else if ((s->fmt || pm_of(u) != 1000) && s->frames[u] > 0) {
                 flush.push_back(u);                         // (the tokens ended on a window's edge: lookforward 0 only)
             }
             s->done[u] = 1;
@@ -331,13 +382,14 @@ static int pump_end_impl(ntts_streams* s, int32_t cap, int32_t* n_chunks, int32_
     const int Jw = J + (int)flush.size();
     *n_chunks = Jw;
     *chunks = s->out_host;
-    *row_stride = s->fmt ? wav_core_out_stride(s->fmt) : s->out_stride;
-    // with an output format every blended chunk is one job of the chunked output stage: its samples in that format are what the caller gets
-    for (int k = 0; k < J && s->fmt; ++k)
-        chunk_samples[k] = (int32_t)wav_core_plan(s->fmt, k, s->jobs_host[k].u, s->jobs_host[k].out_len, chunk_last[k] != 0, chunk_last[k] ? 1 : 0);
-    for (int k = J; k < Jw; ++k) {
-        chunk_stream[k] = flush[k - J]; chunk_last[k] = 1;
-        chunk_samples[k] = (int32_t)wav_core_plan(s->fmt, k, flush[k - J], 0, true, 1);
+    *row_stride = s->fmt ? wav_core_out_stride(s->fmt) : s->spd ? speed_core_out_stride(s->spd) : s->out_stride;
+    // with a speed or an output format every blended chunk is one job of each stage behind the cross-fade, a flush one without new samples: what
+    // the last stage emits for it is what the caller gets
+    for (int k = 0; k < Jw; ++k) {
+        if (k >= J) { chunk_stream[k] = flush[k - J]; chunk_last[k] = 1; chunk_samples[k] = 0; }
+        const int u = chunk_stream[k], phase = chunk_last[k] ? 1 : 0;
+        if (s->spd) chunk_samples[k] = (int32_t)speed_core_plan(s->spd, k, u, pm_of(u), chunk_samples[k], chunk_last[k] != 0, phase, nullptr, nullptr);
+        if (s->fmt) chunk_samples[k] = (int32_t)wav_core_plan(s->fmt, k, u, chunk_samples[k], chunk_last[k] != 0, phase);
     }
     if (n_running) *n_running = running;
     if (more) *more = pending > 0 ? 1 : 0;
@@ -355,12 +407,19 @@ static int pump_end_impl(ntts_streams* s, int32_t cap, int32_t* n_chunks, int32_
         const int rc = pump_windows(s, J, stride);
         if (rc != NTTS_OK) return rc;
     }
-    if (s->fmt) {      // behind the cross-fade, on the samples where they are; the copy is sized in the format's elements
-        const int rc = wav_core_run(s->fmt, Jw, s->out_dev, s->out_stride, s->cst);
+    const float* rows = s->out_dev;       // the stages behind the cross-fade, on the samples where they are
+    long rows_stride = s->out_stride;
+    if (s->spd) {
+        const int rc = speed_core_run(s->spd, Jw, rows, rows_stride, s->cst);
+        if (rc != NTTS_OK) return sfail(s, rc, "time stretch: %s", ntts_codec_last_error(s->c));
+        rows = speed_core_out(s->spd); rows_stride = speed_core_out_stride(s->spd);
+    }
+    if (s->fmt) {      // the copy is sized in the format's elements
+        const int rc = wav_core_run(s->fmt, Jw, rows, rows_stride, s->cst);
         if (rc != NTTS_OK) return sfail(s, rc, "output stage: %s", ntts_codec_last_error(s->c));
         SHIP(s, hipMemcpyAsync(s->out_host, wav_core_out(s->fmt), (size_t)Jw * wav_core_out_stride(s->fmt) * wav_core_esz(s->fmt), hipMemcpyDeviceToHost, s->cst));
     } else {
-        SHIP(s, hipMemcpyAsync(s->out_host, s->out_dev, (size_t)J * s->out_stride * sizeof(float), hipMemcpyDeviceToHost, s->cst));
+        SHIP(s, hipMemcpyAsync(s->out_host, rows, (size_t)Jw * rows_stride * sizeof(float), hipMemcpyDeviceToHost, s->cst));
     }
     SHIP(s, hipStreamSynchronize(s->cst));
     SHIP(s, hipGetLastError());

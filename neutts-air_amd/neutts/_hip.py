@@ -179,6 +179,13 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "ntts_wav_stream_last_error": (C.c_char_p, [p]),
         "ntts_wav_stream_push": (C.c_int, [p, i32, C.POINTER(i32), C.POINTER(f32), i64, C.POINTER(i32), C.POINTER(i32), p, i64, C.POINTER(i32)]),
         "ntts_wav_stream_count": (C.c_int, [C.POINTER(WavFormatC), i64, i32, C.POINTER(i64)]),
+        "ntts_speed_stream_create": (C.c_int, [p, C.POINTER(WavFormatC), i32, i32, C.POINTER(p)]),
+        "ntts_speed_stream_destroy": (None, [p]),
+        "ntts_speed_stream_last_error": (C.c_char_p, [p]),
+        "ntts_speed_stream_push": (C.c_int, [p, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(f32), i64, C.POINTER(i32), C.POINTER(i32), p, i64,
+                                             C.POINTER(i32), C.POINTER(i32), i64, C.POINTER(i32)]),
+        "ntts_speed_stream_count": (C.c_int, [i32, i64, i32, C.POINTER(i64)]),
+        "ntts_streams_set_speed": (C.c_int, [p, C.POINTER(i32)]),
         "ntts_streams_set_format": (C.c_int, [p, C.POINTER(WavFormatC)]),
         "ntts_streams_pump_end_fmt": (C.c_int, [p, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(p),
                                                 C.POINTER(i64), C.POINTER(i32), C.POINTER(i32)]),
@@ -1558,6 +1565,11 @@ class CodecEngine:
         out, out_lens = self.convert_array(buf, n_samples, sample_rate, encoding, filter_width)
         return [out[r, : int(out_lens[r])] for r in range(len(wavs))]
 
+    def stream_stretcher(self, n: int = 1, speed=1.0, sample_rate=None, encoding="f32", filter_width=None, max_chunk_samples: int = 16384) -> "SpeedStream":
+        """The time stretch, and the output stage behind it, for `n` signals that arrive in chunks (ntts_speed_stream_*): the streaming twin of
+        `stretch`.  speed: one value or one per stream, the default of `push`."""
+        return SpeedStream(self, n, speed, sample_rate, encoding, filter_width, max_chunk_samples)
+
     def stream_converter(self, n: int = 1, sample_rate=None, encoding="f32", filter_width=None, max_chunk_samples: int = 16384) -> "WavStream":
         """The output stage for `n` signals that arrive in chunks (ntts_wav_stream_*): the streaming twin of `convert`."""
         return WavStream(self, n, sample_rate, encoding, filter_width, max_chunk_samples)
@@ -1711,6 +1723,111 @@ class WavStream:
             pass
 
 
+class SpeedStream:
+    """The codec's time stretch on `n` independent 24 kHz float32 signals that arrive in chunks, the output stage behind it (ntts_speed_stream_*):
+    every stream keeps its last position and at most 1 560 input samples on the device, and its chunks, concatenated, are
+    CodecEngine.stretch of the concatenated signal bit for bit.  A stream has one speed per signal; at a speed other than 1 a chunk's output lags
+    its input by up to 960 samples (40 ms) and one frame, and may be empty; `last` flushes a stream, which is then empty and may start again at
+    another speed."""
+
+    def __init__(self, codec: "CodecEngine", n: int = 1, speed=1.0, sample_rate=None, encoding="f32", filter_width=None, max_chunk_samples: int = 16384):
+        self.lib = codec.lib
+        self.fmt, self.dtype, self.native = wav_format(sample_rate, encoding, filter_width)
+        self.n, self.max_chunk_samples = int(n), int(max_chunk_samples)
+        pm = speed_permille(speed, self.n)
+        self.permille = np.full(self.n, 1000, dtype=np.int32) if pm is None else pm
+        h = C.c_void_p()
+        rc = self.lib.ntts_speed_stream_create(codec.h, C.byref(self.fmt), self.n, self.max_chunk_samples, C.byref(h))
+        if rc != 0:
+            raise NeuTTSHipError(rc, (self.lib.ntts_speed_stream_last_error(None) or b"").decode())
+        self.h = h
+        self._keep = codec                                               # the stretcher borrows the engine
+        self._conv = WavStream.__new__(WavStream)                        # ntts_wav_stream_count of this format: host arithmetic, no handle
+        self._conv.lib, self._conv.fmt = self.lib, self.fmt
+        self._total = [0] * self.n                                       # input samples of every stream's current signal
+
+    def _chk(self, rc: int):
+        if rc != 0:
+            raise NeuTTSHipError(rc, (self.lib.ntts_speed_stream_last_error(self.h) or b"").decode())
+
+    def _emits(self, u: int, pm: int, v: int, last: bool):
+        """(stretched samples, elements of the format) stream u emits for v more samples: the two stages' counts, one behind the other."""
+        n0 = self._total[u]
+        s0, s1 = self.out_count(n0, pm), self.out_count(n0 + v, pm, last)
+        return s1 - s0, self._conv.out_count(s1, last) - self._conv.out_count(s0)
+
+    def out_count(self, n_in_total: int, permille: int = 1000, last: bool = False) -> int:
+        """24 kHz samples a stream at `permille` has emitted in all after n_in_total input samples (ntts_speed_stream_count)."""
+        m = C.c_int64()
+        rc = self.lib.ntts_speed_stream_count(int(permille), int(n_in_total), int(bool(last)), C.byref(m))
+        if rc != 0:
+            raise NeuTTSHipError(rc, (self.lib.ntts_speed_stream_last_error(None) or b"").decode())
+        return m.value
+
+    def push_array(self, streams, wav: np.ndarray, n_samples, last, permille=None, out_stride: Optional[int] = None, pos_stride: Optional[int] = None):
+        """One ntts_speed_stream_push: wav [k, in_stride] float32, row i = n_samples[i] new samples of stream streams[i] (its final chunk if
+        last[i]) at permille[i] (default: the stream's speed of the constructor) -> ([k, out_stride] array of the encoding's dtype, elements
+        per row, [k, pos_stride] int32 positions decided in this call, positions per row)."""
+        wav = np.ascontiguousarray(wav, dtype=np.float32)
+        k, in_stride = wav.shape
+        st = np.ascontiguousarray(streams, dtype=np.int32)
+        ns = np.ascontiguousarray(n_samples, dtype=np.int32)
+        la = np.ascontiguousarray(np.asarray(last).astype(np.int32))
+        if permille is None:
+            permille = [self.permille[int(u)] if 0 <= int(u) < self.n else 1000 for u in st]
+        pm = np.ascontiguousarray(permille, dtype=np.int32)
+        if not (len(st) == len(ns) == len(la) == len(pm) == k):
+            raise ValueError(f"streams / n_samples / last / permille: {len(st)} / {len(ns)} / {len(la)} / {len(pm)} values for {k} rows")
+        # what the longest chunk of this call emits through both stages, what they held back included
+        ok = [(int(u), int(m), int(v), bool(f)) for u, m, v, f in zip(st, pm, ns, la)
+              if 0 <= int(u) < self.n and int(v) >= 0 and SPEED_PERMILLE_MIN <= int(m) <= SPEED_PERMILLE_MAX]
+        emits = [self._emits(*e) for e in ok]
+        if out_stride is None:
+            out_stride = max([1] + [e[1] for e in emits])
+        if pos_stride is None:
+            pos_stride = max([1] + [e[0] // STRETCH_HOP + 2 for e in emits])
+        out_stride, pos_stride = int(out_stride), int(pos_stride)
+        buf = np.zeros(max(1, k * max(0, out_stride)), dtype=self.dtype)
+        pos = np.zeros(max(1, k * max(0, pos_stride)), dtype=np.int32)
+        out_lens, n_pos = np.zeros(k, dtype=np.int32), np.zeros(k, dtype=np.int32)
+        i32p = C.POINTER(C.c_int32)
+        self._chk(self.lib.ntts_speed_stream_push(self.h, k, st.ctypes.data_as(i32p), pm.ctypes.data_as(i32p), wav.ctypes.data_as(C.POINTER(C.c_float)),
+                                                  in_stride, ns.ctypes.data_as(i32p), la.ctypes.data_as(i32p), C.c_void_p(buf.ctypes.data), out_stride,
+                                                  out_lens.ctypes.data_as(i32p), pos.ctypes.data_as(i32p), pos_stride, n_pos.ctypes.data_as(i32p)))
+        for u, v, f in zip(st, ns, la):
+            self._total[int(u)] = 0 if f else self._total[int(u)] + int(v)
+        return buf[: k * out_stride].reshape(k, out_stride), out_lens, pos[: k * pos_stride].reshape(k, pos_stride), n_pos
+
+    def push(self, chunks: Sequence[np.ndarray], streams: Optional[Sequence[int]] = None, last=False, speed=None) -> List[np.ndarray]:
+        """chunks: one 1-D float32 array per entry, for streams `streams` (default 0, 1, ...); last: one flag or one per entry; speed: one value or
+        one per entry (default: the constructor's) -> the chunks at that speed in the output format."""
+        chunks = [np.asarray(c, dtype=np.float32).reshape(-1) for c in chunks]
+        if not chunks:
+            return []
+        streams = list(range(len(chunks))) if streams is None else list(streams)
+        last = [bool(last)] * len(chunks) if isinstance(last, (bool, np.bool_, int)) else [bool(f) for f in last]
+        pm = None
+        if speed is not None:
+            pm = speed_permille(speed, len(chunks))
+            pm = np.full(len(chunks), 1000, dtype=np.int32) if pm is None else pm
+        buf = np.zeros((len(chunks), max(1, max(len(c) for c in chunks))), dtype=np.float32)
+        for r, c in enumerate(chunks):
+            buf[r, : len(c)] = c
+        out, out_lens, _, _ = self.push_array(streams, buf, [len(c) for c in chunks], last, pm)
+        return [out[r, : int(out_lens[r])] for r in range(len(chunks))]
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.ntts_speed_stream_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class StreamSet:
     """Device-side streaming state of `n` concurrent infer_stream utterances (ntts_streams_*, ABI 6): token caches, window assembly,
     the 27-frame slice and the cross-fade with the previous chunk (ref:neutts/neutts.py:385-388, :401-465) run on the device; per burst
@@ -1718,8 +1835,9 @@ class StreamSet:
 
     def __init__(self, backbone: "BackboneEngine", codec: "CodecEngine", slots: Sequence[int], ref_codes: Sequence[Sequence[int]],
                  max_new_tokens: int, chunk: int, lookforward: int, lookback: int, overlap: int, hop_length: int, speech_base: int,
-                 n_codes: int, modulo: bool = False, fmt=None):
-        """fmt: None (24 kHz float32 chunks) or (sample_rate, encoding, filter_width): the chunked output stage behind the cross-fade."""
+                 n_codes: int, modulo: bool = False, fmt=None, speed=None):
+        """fmt: None (24 kHz float32 chunks) or (sample_rate, encoding, filter_width): the chunked output stage behind the cross-fade.
+        speed: None (all at 1.0), one value or one per stream: the chunked time stretch behind the cross-fade, ahead of the output stage."""
         self.lib = backbone.lib
         self.n = len(slots)
         prm = StreamParamsC(chunk, lookforward, lookback, overlap, hop_length, speech_base, n_codes, int(bool(modulo)))
@@ -1742,6 +1860,16 @@ class StreamSet:
             if not native:                                               # (the native format spelled out: the calls of a set without one)
                 self.set_format(fc)
                 self._fmt = (fc, dtype)
+        pm = speed_permille(speed, self.n)
+        if pm is not None:                                               # (all at 1.0: the calls of a set without the stage)
+            self.set_speed(pm)
+
+    def set_speed(self, permille):
+        """ntts_streams_set_speed as it is: int32 per mille per stream, or None for all 1000; legal until the first pump_begin."""
+        pm = None if permille is None else np.ascontiguousarray(permille, dtype=np.int32)
+        if pm is not None and len(pm) != self.n:
+            raise ValueError(f"set_speed: {len(pm)} values for {self.n} streams")
+        self._chk(self.lib.ntts_streams_set_speed(self.h, pm.ctypes.data_as(C.POINTER(C.c_int32)) if pm is not None else None))
 
     def set_format(self, fc: "WavFormatC"):
         """ntts_streams_set_format as it is: legal until the first pump_begin."""

@@ -231,6 +231,7 @@ class NeuTTS:
         stream_encoding: str = "f32",
         stream_filter_width: Optional[int] = None,
         speed: float = 1.0,
+        stream_speed: float = 1.0,
     ):
         # Consts (ref:neutts/neutts.py:84-91)
         self.sample_rate = 24_000            # the NATIVE rate (the codec's; what a watermarker sees), whatever the output format
@@ -254,9 +255,16 @@ class NeuTTS:
         # How fast the voice speaks, 0.5 .. 2.0 (a codec-token model has no duration input: the reference offers nothing, its users resample, which
         # moves the pitch).  A pitch-preserving time stretch (WSOLA) on the device between the codec pass and the output stage (include/neutts_hip.h
         # ntts_codec_decode_speed): an utterance takes ceil(samples / speed) samples at 24 kHz.  speed= per call overrides it, one value or one per
-        # utterance; the stream entry points take 1.0 only.
+        # utterance; the stream entry points take 1.0 only: their speed is stream_speed.
         _hip.speed_permille(speed, 1)
         self.speed = float(speed)
+        # Speed of the chunks of infer_stream / infer_stream_batch, apart from the one above as the stream format is: the same stretch on chunks, with
+        # each stream's state and at most 1 560 samples of history on the device (ntts_streams_set_speed / ntts_speed_stream_*), ahead of the chunks'
+        # output format.  A stream's chunks, concatenated, are the one-shot stage's output of its concatenated speed-1 chunks bit for bit; at a speed
+        # other than 1 they lag by up to 960 input samples (40 ms) and one frame -- the first audio comes that much later, only the last chunk is
+        # longer for it, and a chunk may be empty.  stream_speed= per call overrides it, one value or one per utterance.
+        _hip.speed_permille(stream_speed, 1, "stream_")
+        self.stream_speed = float(stream_speed)
         self.max_context = 2048
         self.hop_length = 480
         self.streaming_overlap_frames = 1
@@ -513,17 +521,19 @@ class NeuTTS:
         """Streaming synthesis with the reference's window / cross-fade semantics (ref:neutts/neutts.py:373-465).  Sampling overrides as `infer`
         (checked here, before the generator is handed out).  Chunks are 24 kHz float32 unless stream_sample_rate= / stream_encoding= /
         stream_filter_width= (or the instance's stream_* attributes) say otherwise; sample_rate= / encoding= / a non-native output_* attribute
-        stay a ValueError here."""
+        stay a ValueError here.  stream_speed= (or the instance's stream_speed) is the speed of this stream, 0.5 .. 2.0: the time stretch on its
+        chunks, ahead of their format; the chunks then lag by up to 40 ms and a frame and may be empty.  speed= other than 1 stays a ValueError."""
         self._refuse_stream_output(repetition.pop("sample_rate", None), repetition.pop("encoding", None), "infer_stream")
         self._refuse_stream_speed(repetition.pop("speed", None), "infer_stream")
         fmt = self._resolve_stream_output(repetition.pop("stream_sample_rate", None), repetition.pop("stream_encoding", None),
                                           repetition.pop("stream_filter_width", None))
+        spd = self._resolve_stream_speed(repetition.pop("stream_speed", None), 1)
         samp = self._resolve_sampling(1, temperature, top_k, top_p, min_p, repetition)
         prompt_ids = self._apply_chat_template(ref_codes, ref_text, text)
         ref = [int(c) for c in _to_list(ref_codes)]
         if self._stream_on_device([ref]):       # token cache, windows, codec pass and cross-fade on the device (csrc/stream.cpp): a set of one stream
-            return (chunk for _, chunk in self._infer_stream_batch_hip([prompt_ids], [ref], samp, fmt))
-        return self._infer_stream_hip(prompt_ids, ref, samp, fmt)   # host loop: a watermarker (a host library) sits between the codec and the slice
+            return (chunk for _, chunk in self._infer_stream_batch_hip([prompt_ids], [ref], samp, fmt, spd))
+        return self._infer_stream_hip(prompt_ids, ref, samp, fmt, spd)   # host loop: a watermarker (a host library) sits between the codec and the slice
 
     def infer_stream_batch(self, texts: Sequence[str], ref_codes, ref_texts, *, temperature=None, top_k=None, top_p=None, min_p=None, **repetition) -> Generator[tuple, None, None]:
         """Many utterances streamed at once (BASELINE config 5's shape: a decode batch with the codec on its own stream):
@@ -531,11 +541,13 @@ class NeuTTS:
         yields for it.  One decode burst serves every running utterance, and all windows that became decodable in a burst
         go through the codec in ONE batched call, enqueued behind the next burst (the two engines' streams overlap).
         At most `max_batch` utterances (the engine's decode slots) per call.  Sampling overrides as `infer_batch`.  Chunk format as
-        `infer_stream`: stream_sample_rate= / stream_encoding= / stream_filter_width=, one format per call."""
+        `infer_stream`: stream_sample_rate= / stream_encoding= / stream_filter_width=, one format per call; stream_speed= one value or one per
+        utterance."""
         self._refuse_stream_output(repetition.pop("sample_rate", None), repetition.pop("encoding", None), "infer_stream_batch")
         self._refuse_stream_speed(repetition.pop("speed", None), "infer_stream_batch")
         fmt = self._resolve_stream_output(repetition.pop("stream_sample_rate", None), repetition.pop("stream_encoding", None),
                                           repetition.pop("stream_filter_width", None))
+        spd = self._resolve_stream_speed(repetition.pop("stream_speed", None), len(texts))
         samp = self._resolve_sampling(len(texts), temperature, top_k, top_p, min_p, repetition)
         if not isinstance(ref_texts, (list, tuple)):
             ref_texts = [ref_texts] * len(texts)
@@ -544,7 +556,7 @@ class NeuTTS:
         if len(texts) > cap:
             raise ValueError(f"{len(texts)} utterances exceed the engine's {cap} decode slots")
         prompts = [self._apply_chat_template(rc, rt, t) for rc, rt, t in zip(ref_codes, ref_texts, texts)]
-        return self._infer_stream_batch_hip(prompts, [[int(c) for c in _to_list(rc)] for rc in ref_codes], samp, fmt)
+        return self._infer_stream_batch_hip(prompts, [[int(c) for c in _to_list(rc)] for rc in ref_codes], samp, fmt, spd)
 
     def score(self, text: str, codes, ref_codes, ref_text: str, include_eos: bool = True) -> Dict[str, object]:
         """Teacher-forced score of an EXISTING utterance: the model's log-probability of every speech token of `codes` (and, with include_eos, of
@@ -788,7 +800,16 @@ class NeuTTS:
         if self._resolve_speed(speed, 1) is not None:
             what = f"speed={speed!r}" if speed is not None else f"speed={self.speed!r} on the instance"
             raise ValueError(f"{who} speaks at speed 1.0 only (got {what}): the time stretch is a one-shot stage behind infer / infer_batch / "
-                             "decode_codes; a chunked stretch with history on the device does not exist yet")
+                             "decode_codes; a stream's own speed is set by stream_speed=, which keeps the stretch's history on the device")
+
+    def _resolve_stream_speed(self, speed, n: int):
+        """Per-call speed of the stream entry points: None = the instance's stream_speed.  -> None when every utterance runs at 1.0 (the calls of an
+        instance without the stage), else one checked value per utterance.  ValueError on a bad value, before a generator exists."""
+        given = speed is not None
+        speed = self.stream_speed if speed is None else speed
+        if _hip.speed_permille(speed, n, "stream_" if given else "instance stream_") is None:
+            return None
+        return [float(v) for v in speed] if isinstance(speed, (list, tuple, np.ndarray)) else [float(speed)] * n
 
     def _resolve_output(self, sample_rate=None, encoding=None):
         """Per-call output format: None = the instance attribute.  -> None for the native format (24 kHz float32: the calls of an instance without
@@ -835,10 +856,16 @@ class NeuTTS:
             k0 = k1
         return out
 
-    def _stream_converter(self, n: int, fmt):
-        """The chunked output stage for the host loops' blended chunks (a WavStream of n rows); the longest chunk is a final window's frame."""
+    def _stream_converter(self, n: int, fmt, spd=None):
+        """The stages behind the cross-fade for the host loops' blended chunks: the chunked output stage (a WavStream of n rows), or with speeds the
+        chunked time stretch with that stage behind it (a SpeedStream); None when there is neither.  The longest chunk is a final window's frame."""
+        if fmt is None and spd is None:
+            return None
         longest = (self.streaming_frames_per_chunk + self.streaming_lookforward + 2 * self.streaming_overlap_frames) * self.hop_length
-        return self.codec.engine.stream_converter(n, fmt[0], fmt[1], fmt[2], max_chunk_samples=longest)
+        if spd is None:
+            return self.codec.engine.stream_converter(n, fmt[0], fmt[1], fmt[2], max_chunk_samples=longest)
+        fmt = (None, "f32", None) if fmt is None else fmt
+        return self.codec.engine.stream_stretcher(n, spd, fmt[0], fmt[1], fmt[2], max_chunk_samples=longest)
 
     def _decode_formatted(self, codes: Sequence[Sequence[int]], out, speed=None) -> List[np.ndarray]:
         """One codec pass with the time stretch (speed: None, or one value per utterance) and the device output stage (out: None = native) behind it.
@@ -898,15 +925,16 @@ class NeuTTS:
 
     # ------------------------------------------------------------------------------------------ streaming
     def _infer_stream_hip(self, prompt_ids: List[int], ref_codes: List[int], samp: Optional[Sequence[tuple]] = None,
-                          fmt=_INSTANCE_FORMAT) -> Generator[np.ndarray, None, None]:
+                          fmt=_INSTANCE_FORMAT, spd=None) -> Generator[np.ndarray, None, None]:
         """Window / cross-fade semantics of ref:neutts/neutts.py:401-465 (Appendix C of SURVEY.md), token by token.
         The backbone and the codec are separate engines on separate HIP streams: the next `chunk` decode steps are
         enqueued (asynchronously) BEFORE the codec pass of the chunk that just became decodable, so the codec runs
         beside the backbone instead of between its bursts; the host only blocks in `read()`.  With a chunk format (`fmt`) every blended chunk
-        goes through the chunked output stage (a WavStream of one row) behind the cross-fade; a watermarker still sees 24 kHz float32 windows."""
+        goes through the chunked output stage (a WavStream of one row) behind the cross-fade, with a speed (`spd`: None or [speed]) through the chunked
+        time stretch ahead of it (a SpeedStream); a watermarker still sees 24 kHz float32 windows at speed 1."""
         if fmt is _INSTANCE_FORMAT:
             fmt = self._resolve_stream_output()
-        conv = self._stream_converter(1, fmt) if fmt is not None else None
+        conv = self._stream_converter(1, fmt, spd)
         emit = (lambda x, last=False: x) if conv is None else (lambda x, last=False: conv.push([x], last=last)[0])
         eng = self.backbone
         self._seed += 1
@@ -977,7 +1005,7 @@ class NeuTTS:
             return False                   # (ntts_streams_create refuses these; the host loop slices like the reference does)
         return min(len(rc) for rc in ref_codes) >= self.streaming_overlap_frames
 
-    def _stream_batch_device(self, slots, ref_codes, fmt=None):
+    def _stream_batch_device(self, slots, ref_codes, fmt=None, spd=None):
         """The loop of _infer_stream_batch_hip with the token caches, the window assembly, the 27-frame slice and the cross-fade on the
         device (ntts_streams_*): per burst the host waits for a snapshot of 2 n integers, enqueues the next burst, and receives each
         stream's new samples.  Same windows, same arithmetic (kernels/stream.h restates numpy's operations one by one): the chunks are
@@ -986,7 +1014,8 @@ class NeuTTS:
         chunk, look_f = self.streaming_frames_per_chunk, self.streaming_lookforward
         mod = int(getattr(self, "_stream_modulo", 0))
         ss = _hip.StreamSet(eng, self.codec.engine, slots, ref_codes, int(eng.cfg["max_context"]), chunk, look_f, self.streaming_lookback,
-                            self.streaming_overlap_frames, self.hop_length, 0 if mod else int(self._speech_base), mod or 65536, bool(mod), fmt=fmt)
+                            self.streaming_overlap_frames, self.hop_length, 0 if mod else int(self._speech_base), mod or 65536, bool(mod), fmt=fmt,
+                            speed=spd)
         try:
             # the first window is complete once chunk + lookforward tokens exist (ref :401-404) and the prompt pass produced one of them
             steps = chunk + look_f - 1
@@ -1028,7 +1057,8 @@ class NeuTTS:
             self._gang_codec0_lent = True
         return self._gang_codecs
 
-    def _infer_stream_batch_gang(self, prompts: List[List[int]], ref_codes: List[List[int]], samp: Optional[Sequence[tuple]] = None, fmt=None):
+    def _infer_stream_batch_gang(self, prompts: List[List[int]], ref_codes: List[List[int]], samp: Optional[Sequence[tuple]] = None, fmt=None,
+                                 spd=None):
         """infer_stream_batch over an ENGINE GANG (BASELINE configs[4]'s literal shape: ref:neutts/neutts.py:373-465
         for many utterances at once).  The utterances are dealt out in admission groups over the gang's engines; every group is a
         device-side stream set (ntts_streams_*) on its engine, the engine's codec engine on the same lane.  Per turn of an engine:
@@ -1106,7 +1136,8 @@ class NeuTTS:
                             i0 = i1
                         item[0] = _hip.StreamSet(eng, codecs[k], slots, [ref_codes[i] for i in idx], int(eng.cfg["max_context"]), chunk, look_f,
                                                  self.streaming_lookback, self.streaming_overlap_frames, self.hop_length,
-                                                 0 if mod else int(self._speech_base), mod or 65536, bool(mod), fmt=fmt)
+                                                 0 if mod else int(self._speech_base), mod or 65536, bool(mod), fmt=fmt,
+                                                 speed=None if spd is None else [spd[i] for i in idx])
                         admitted = True
                         running += len(idx)
                     if running:
@@ -1139,8 +1170,9 @@ class NeuTTS:
                                 pass
 
     def _infer_stream_batch_hip(self, prompts: List[List[int]], ref_codes: List[List[int]], samp: Optional[Sequence[tuple]] = None,
-                                fmt=_INSTANCE_FORMAT):
+                                fmt=_INSTANCE_FORMAT, spd=None):
         # fmt: the chunks' format -- None = 24 kHz float32, (sample_rate, encoding, filter_width), or (the default) the instance's stream_* attributes
+        # spd: the chunks' speeds -- None = all at 1.0, or one value per utterance
         if fmt is _INSTANCE_FORMAT:
             fmt = self._resolve_stream_output()
         # (stream_on_gang: off unless the caller sets it -- it pays for one of the two models measured.  512 streams of the fp8 Nano-sized model
@@ -1148,7 +1180,7 @@ class NeuTTS:
         #  182 ms on ONE 512-slot engine; NeuTTS-Air bf16: 256 streams over 4 x 64 slots 80.3 k against 100.5 k on one engine, 512 streams over
         #  4 x 128 111.9 k against 114.9 k -- four chains stream Air's larger weights four times; profiles/r05o_sweep_stream_gang*.txt)
         if (self.gang is not None and len(prompts) > 1 and getattr(self, "stream_on_gang", False) and self._stream_on_device(ref_codes)):
-            yield from self._infer_stream_batch_gang(prompts, ref_codes, samp, fmt)
+            yield from self._infer_stream_batch_gang(prompts, ref_codes, samp, fmt, spd)
             return
         eng = self.backbone
         n = len(prompts)
@@ -1176,7 +1208,7 @@ class NeuTTS:
                                       self.streaming_lookback, self.streaming_overlap_frames)
         if self._stream_on_device(ref_codes):
             try:
-                yield from self._stream_batch_device(slots, ref_codes, fmt)
+                yield from self._stream_batch_device(slots, ref_codes, fmt, spd)
             finally:
                 eng.sync()
                 for s in slots:
@@ -1197,8 +1229,9 @@ class NeuTTS:
         need = chunk + look_f                             # undecoded tokens that make a window decodable (ref :401-404)
         conv = None
         try:
-            if fmt is not None:                           # the chunked output stage behind the cross-fade: one row per utterance
-                conv = self._stream_converter(n, fmt)
+            conv = self._stream_converter(n, fmt, spd)    # the stages behind the cross-fade (time stretch, output format): one row per utterance
+            pm = _hip.speed_permille(spd, n)
+            held = [fmt is not None or (pm is not None and pm[i] != 1000) for i in range(n)]        # utterances whose stage holds samples back
             while not all(done):
                 ids_all, n_new_all, fin_all = eng.read_all_array()    # blocks until the bursts enqueued so far are done
                 ids, n_new, fin = ids_all[slots], n_new_all[slots], fin_all[slots]     # row i = utterance i
@@ -1230,7 +1263,7 @@ class NeuTTS:
                             t0 = max(int(clen[i]) - (look_b + ovl + remaining), 0)
                             s0 = (int(clen[i]) - t0 - remaining - ovl) * hop
                             jobs.append((i, cache[i, t0:clen[i]], s0, None, True))
-                        elif conv is not None and (blend[i].prev is not None or any(j[0] == i for j in jobs)):
+                        elif conv is not None and held[i] and (blend[i].prev is not None or any(j[0] == i for j in jobs)):
                             flush.append(i)               # (the tokens ended on a window's edge: lookforward 0 only)
                         done[i] = True
                 if jobs:
