@@ -564,6 +564,52 @@ int ntts_codec_decode_dev_speed(ntts_codec* c, int32_t n, const int32_t* codes_d
                                 const ntts_wav_format* fmt, int32_t* out_lens);
 int ntts_codec_last_stretch_timing(ntts_codec* c, float* search_ms, float* render_ms);
 
+/* Loudness: ITU-R BS.1770-4 loudness normalisation on the device, between the time stretch and the output stage.  NEW SYMBOLS ONLY: NTTS_ABI_VERSION
+ * stays 11.
+ *
+ * The reference has no such knob: a cloned voice comes out as loud as its reference clip was, and its users run a loudness normaliser on the 24 kHz
+ * float waveform on the host.  Here the row is measured and scaled where it lies, at the native 24 kHz, behind the time stretch (if any) and ahead of
+ * resampling and encoding.  K-weighting: two biquads designed for 24 kHz by the bilinear construction that gives the standard's 48 kHz table at
+ * 48 kHz (coefficients built on the host in double).  Sub-blocks of S = 2400 samples (100 ms), J = n / S of them; a trailing partial one is not
+ * measured.  For sub-block j both biquads start from zero state at sample max(0, (j - 1) * S); z_j = the mean square of the filter output over the
+ * sub-block's own samples (against filtering the whole row this moves L by about 2e-12 LU).  Gating block i = sub-blocks i .. i + 3, i in [0, J - 3):
+ * P_i = mean(z_i .. z_{i+3}), l_i = -0.691 + 10 log10 P_i; the absolute gate keeps l_i > -70, Gamma = -0.691 + 10 log10(mean P_i of those) - 10, the
+ * relative gate keeps those with l_i > Gamma as well, L = -0.691 + 10 log10(mean P_i of those).  Filters, sums and gates run in fp64.
+ * A row without a block (n < 9600), without a block past the absolute gate, or with a non-finite sample is UNMEASURABLE: L = NaN, gain 1.
+ * peak = max |x| over the row: the SAMPLE peak, not the true (inter-sample) peak (+inf for a row with a non-finite sample).
+ * g = min(10^((target_lufs - L) / 20), 10^(max_gain_db / 20), 10^(peak_dbfs / 20) / peak) (the last term only where peak > 0), in double, rounded
+ * once to float32; out[i] = x[i] * g in fp32.  A row whose g is exactly 1, and every row with enable == 0, is the input bit for bit.  Resampling behind
+ * the gain can overshoot the ceiling slightly.  tests/loudness_spec.py states all of this in numpy and is the authority.
+ *
+ * ntts_wav_loudness, one per row: enable (0 = the row is left alone, the other fields are not looked at); target_lufs in [-70, 0]; peak_dbfs in
+ * [-20, 0] (-1 is the usual ceiling); max_gain_db in [0, 60] (20 keeps a near-silent utterance from being lifted into its noise).
+ * measured (may be NULL): [n][3] doubles, row i = (L_i, peak_i, g_i).
+ * ntts_codec_normalize: the stage alone (and the output stage behind it) on HOST float32 waveforms, the twin of ntts_codec_stretch / ntts_codec_convert
+ * -- for a host library between the codec and the output, and for the tests; out_lens[i] = the samples of row i in `fmt`.  Blocking.
+ * ntts_codec_measure_loudness: the measurement alone, nothing scaled (g = 1 in `measured`).  Blocking.
+ * ntts_codec_decode_loud / ntts_codec_decode_dev_loud: ntts_codec_decode_speed / ntts_codec_decode_dev_speed with loudness[n]; NULL, or every enable
+ * 0, makes the very same calls as those entry points, bit for bit.
+ * Refused with NTTS_EINVAL and a message that names the row and the value, nothing run, the engine stays usable: a parameter of an enabled row
+ * outside its range or NaN, and what ntts_codec_stretch / ntts_codec_decode_speed refuse.  Batches larger than the workspace are split as the
+ * stretch splits them.
+ * ntts_codec_last_loudness_timing: GPU milliseconds of the measure and the apply kernel of the most recent loudness stage (NTTS_ESTATE before the
+ * first). */
+typedef struct ntts_wav_loudness {
+    int32_t enable;
+    float target_lufs;
+    float peak_dbfs;
+    float max_gain_db;
+} ntts_wav_loudness;
+int ntts_codec_normalize(ntts_codec* c, int32_t n, const float* wav, int64_t in_stride, const int32_t* n_samples, const ntts_wav_loudness* loudness,
+                         const ntts_wav_format* fmt, void* out, int64_t out_stride, int32_t* out_lens, double* measured);
+int ntts_codec_measure_loudness(ntts_codec* c, int32_t n, const float* wav, int64_t in_stride, const int32_t* n_samples, double* measured);
+int ntts_codec_decode_loud(ntts_codec* c, int32_t n, const int32_t* codes, const int32_t* lens, const int32_t* speed_permille,
+                           const ntts_wav_loudness* loudness, const ntts_wav_format* fmt, void* out, int64_t out_stride, int32_t* out_lens);
+int ntts_codec_decode_dev_loud(ntts_codec* c, int32_t n, const int32_t* codes_dev, int32_t codes_stride, const int32_t* lens,
+                               const int32_t* speed_permille, const ntts_wav_loudness* loudness, void* out, int64_t out_stride,
+                               int32_t out_on_device, void* producer_stream, const ntts_wav_format* fmt, int32_t* out_lens);
+int ntts_codec_last_loudness_timing(ntts_codec* c, float* measure_ms, float* apply_ms);
+
 /* The output stage on a signal that arrives in CHUNKS (a stream).  NEW SYMBOLS ONLY: NTTS_ABI_VERSION stays 11.
  *
  * After N input samples in all a stream has emitted M(N) output samples: M = N at 24 kHz; otherwise M = ((N - width) / orig) * new once

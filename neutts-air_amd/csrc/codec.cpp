@@ -85,6 +85,17 @@ struct ntts_codec {
     float* sfade = nullptr;
     hipEvent_t ev_s[3]{};
     bool have_stretch_time = false;
+    // loudness (ntts_codec_normalize / _decode_loud): sub-block powers, the measure kernel's partial peaks and (L, peak, g) per row, allocated with
+    // the first call that needs them; the K-weighting coefficients; events around the measure and the apply kernel
+    double* lz = nullptr;
+    size_t lz_cap = 0;           // doubles
+    float* lpk = nullptr;
+    size_t lpk_cap = 0;          // floats
+    double* lres = nullptr;
+    size_t lres_cap = 0;         // doubles
+    double kw[7]{};
+    hipEvent_t ev_l[4]{};
+    bool have_loud_time = false;
 };
 
 static int cfail(ntts_codec* c, int code, const char* fmt, ...) {
@@ -122,7 +133,12 @@ extern "C" void ntts_codec_destroy(ntts_codec* c) {
     if (c->fbuf) hipFree(c->fbuf);
     if (c->sbuf) hipFree(c->sbuf);
     if (c->spos) hipFree(c->spos);
+    if (c->lz) hipFree(c->lz);
+    if (c->lpk) hipFree(c->lpk);
+    if (c->lres) hipFree(c->lres);
     for (auto& e : c->ev_s)
+        if (e) hipEventDestroy(e);
+    for (auto& e : c->ev_l)
         if (e) hipEventDestroy(e);
     for (auto& e : c->ev)
         if (e) hipEventDestroy(e);
@@ -601,6 +617,87 @@ static int wav_stretch_launch(ntts_codec* c, const float* in, long in_stride, co
     return NTTS_OK;
 }
 
+// ---- loudness normalisation between the time stretch and the output stage (kernels/codec.h wav_loud_*; tests/loudness_spec.py is the contract)
+// one biquad of the K-weighting at the native rate: the bilinear construction that gives the standard's 48 kHz table at 48 kHz
+static void loud_biquad(double f0, double Q, double Vh, double Vb, bool shelf, double* b, double* a) {
+    const double K = tan(M_PI * f0 / 24000.0), a0 = 1.0 + K / Q + K * K;
+    if (shelf) { b[0] = (Vh + Vb * K / Q + K * K) / a0; b[1] = 2.0 * (K * K - Vh) / a0; b[2] = (Vh - Vb * K / Q + K * K) / a0; }
+    a[0] = 2.0 * (K * K - 1.0) / a0; a[1] = (1.0 - K / Q + K * K) / a0;
+}
+// the parameters of every row with the option on inside their ranges (a NaN is outside); *any = one row has it on
+static int loud_check(ntts_codec* c, const ntts_wav_loudness* loud, int n, bool* any) {
+    *any = false;
+    for (int i = 0; i < n; ++i) {
+        if (!loud[i].enable) continue;
+        *any = true;
+        if (!(loud[i].target_lufs >= -70.f && loud[i].target_lufs <= 0.f))
+            return cfail(c, NTTS_EINVAL, "utterance %d: loudness target_lufs %g outside [-70, 0]", i, (double)loud[i].target_lufs);
+        if (!(loud[i].peak_dbfs >= -20.f && loud[i].peak_dbfs <= 0.f))
+            return cfail(c, NTTS_EINVAL, "utterance %d: loudness peak_dbfs %g outside [-20, 0]", i, (double)loud[i].peak_dbfs);
+        if (!(loud[i].max_gain_db >= 0.f && loud[i].max_gain_db <= 60.f))
+            return cfail(c, NTTS_EINVAL, "utterance %d: loudness max_gain_db %g outside [0, 60]", i, (double)loud[i].max_gain_db);
+    }
+    return NTTS_OK;
+}
+// [enable, target_lufs, peak_dbfs, max_gain_db] of n rows as floats, the layout the gate kernel reads (through the int meta block)
+static void loud_pack(int* dst, const ntts_wav_loudness* loud, int n) {
+    for (int i = 0; i < n; ++i) {
+        const float v[4] = {loud[i].enable ? 1.f : 0.f, loud[i].target_lufs, loud[i].peak_dbfs, loud[i].max_gain_db};
+        memcpy(dst + 4 * (size_t)i, v, sizeof v);
+    }
+}
+
+// io [n][stride] (utterance b: lens_dev[b] * len_mul samples, the longest n_max): measure every row, gate, and -- with par_dev, [n][4] floats as
+// loud_pack wrote them -- scale the rows in place; without it nothing is changed.  c->lres [n][3] receives (L, peak, g).
+static int wav_loud_launch(ntts_codec* c, float* io, long stride, const int* lens_dev, int len_mul, const int* par_dev, int n, int64_t n_max,
+                           hipStream_t st) {
+    const int64_t j_max = n_max / kLoudSub;
+    const int64_t z_stride = std::max<int64_t>(j_max, 1), gy = std::max<int64_t>((j_max + kLoudLanes - 1) / kLoudLanes, 1);
+    const size_t need_z = (size_t)n * z_stride, need_pk = (size_t)n * gy, need_res = 3 * (size_t)n;
+    if (c->lz_cap < need_z || c->lpk_cap < need_pk || c->lres_cap < need_res) {
+        CHIP(c, hipStreamSynchronize(st));
+        if (!c->ev_l[0]) {
+            double b[3];
+            loud_biquad(1681.974450955533, 0.7071752369554196, pow(10.0, 3.999843853973347 / 20.0),
+                        pow(pow(10.0, 3.999843853973347 / 20.0), 0.4996667741545416), true, b, c->kw + 3);
+            c->kw[0] = b[0]; c->kw[1] = b[1]; c->kw[2] = b[2];
+            loud_biquad(38.13547087602444, 0.5003270373238773, 0.0, 0.0, false, nullptr, c->kw + 5);
+            for (auto& e : c->ev_l) CHIP(c, hipEventCreate(&e));
+        }
+        if (c->lz_cap < need_z) {              // room for the whole waveform workspace (as many sub-blocks as it holds, one per row at least)
+            const size_t whole = 2 * c->wav_cap / kLoudSub + (size_t)c->max_rows;
+            if (c->lz) { hipFree(c->lz); c->lz = nullptr; c->lz_cap = 0; }
+            CHIP(c, hipMalloc((void**)&c->lz, std::max(need_z, whole) * sizeof(double)));
+            c->lz_cap = std::max(need_z, whole);
+        }
+        if (c->lpk_cap < need_pk) {
+            const size_t whole = 2 * c->wav_cap / ((size_t)kLoudSub * kLoudLanes) + (size_t)c->max_rows;
+            if (c->lpk) { hipFree(c->lpk); c->lpk = nullptr; c->lpk_cap = 0; }
+            CHIP(c, hipMalloc((void**)&c->lpk, std::max(need_pk, whole) * sizeof(float)));
+            c->lpk_cap = std::max(need_pk, whole);
+        }
+        if (c->lres_cap < need_res) {
+            const size_t whole = 3 * (size_t)c->max_rows;
+            if (c->lres) { hipFree(c->lres); c->lres = nullptr; c->lres_cap = 0; }
+            CHIP(c, hipMalloc((void**)&c->lres, std::max(need_res, whole) * sizeof(double)));
+            c->lres_cap = std::max(need_res, whole);
+        }
+    }
+    WavLoudArgs a{};
+    a.io = io; a.stride = stride; a.lens = lens_dev; a.len_mul = len_mul; a.par = (const float*)par_dev;
+    memcpy(a.kw, c->kw, sizeof a.kw);
+    a.z = c->lz; a.z_stride = (long)z_stride; a.pk = c->lpk; a.pk_stride = (int)gy; a.res = c->lres;
+    CHIP(c, hipEventRecord(c->ev_l[0], st));
+    NTTS_LAUNCH((wav_loud_measure_kernel), dim3(n, (unsigned)gy), dim3(kLoudLanes), st, a);
+    CHIP(c, hipEventRecord(c->ev_l[1], st));
+    NTTS_LAUNCH((wav_loud_gate_kernel), dim3(n), dim3(kLoudLanes), st, a);
+    CHIP(c, hipEventRecord(c->ev_l[2], st));
+    if (par_dev && n_max > 0) NTTS_LAUNCH((wav_loud_apply_kernel), dim3(n, (unsigned)((n_max + 1023) / 1024)), dim3(256), st, a);
+    CHIP(c, hipEventRecord(c->ev_l[3], st));
+    c->have_loud_time = true;
+    return NTTS_OK;
+}
+
 // codes: HOST packed codes (codes_dev == null), or DEVICE codes, utterance i at codes_dev + i * codes_stride (already in range:
 // they come from ntts_backbone_export_codes).  out_kind: 0 = host destination, blocking (the classic entry point);
 // 1 = host destination (pinned), asynchronous; 2 = device destination, asynchronous.  producer: a HIP stream whose work so far
@@ -609,7 +706,8 @@ static int wav_stretch_launch(ntts_codec* c, const float* in, long in_stride, co
 // receives every utterance's samples.
 static int codec_decode_impl(ntts_codec* c, int32_t n, const int32_t* codes, const int32_t* codes_dev, int32_t codes_stride,
                              const int32_t* lens, void* wav_out, int64_t wav_stride, int out_kind, hipStream_t producer,
-                             const WavFmt* wf = nullptr, int32_t* out_lens = nullptr, const int32_t* speed = nullptr) {
+                             const WavFmt* wf = nullptr, int32_t* out_lens = nullptr, const int32_t* speed = nullptr,
+                             const ntts_wav_loudness* loud = nullptr) {
     if (!c || n < 1 || (!codes && !codes_dev) || !lens || !wav_out) return cfail(c, NTTS_EINVAL, "null/empty argument");
     if (!c->finalized) return cfail(c, NTTS_ESTATE, "weights not finalised");
     if (wf && wf->plain()) wf = nullptr;
@@ -618,6 +716,12 @@ static int codec_decode_impl(ntts_codec* c, int32_t n, const int32_t* codes, con
         const int rc = stretch_check(c, speed, n, &any);
         if (rc != NTTS_OK) return rc;
         if (!any) speed = nullptr;
+    }
+    if (loud) {                            // loudness: no row with the option on (or null) is the pass without the stage, call for call
+        bool any;
+        const int rc = loud_check(c, loud, n, &any);
+        if (rc != NTTS_OK) return rc;
+        if (!any) loud = nullptr;
     }
     CHIP(c, hipSetDevice(c->device));
     const int H = c->H, hop = c->cfg.hop_length;
@@ -659,8 +763,9 @@ static int codec_decode_impl(ntts_codec* c, int32_t n, const int32_t* codes, con
     if (!(c->attn_resident && npages <= kAttnResPages) && (long)n * npages * kPage > c->max_rows + (c->max_rows / (1 + 2 * kPadRows) + 1) * kPage)
         return cfail(c, NTTS_EINVAL, "%d utterances x %d pages exceed the V^T workspace: decode fewer utterances per call", n, npages);
     // ---- meta: [lens n][code_off n][row_off n + 1][codes total], built in a page-locked ring slot: the copy is asynchronous, no stream-wide wait
-    // (with a speed: [speed n][stretched samples n] behind them)
-    const size_t m_size = 3 * (size_t)n + 1 + (codes ? (size_t)total : 0) + (speed ? 2 * (size_t)n : 0);
+    // (with a speed: [speed n][stretched samples n] behind them; with a loudness: [enable, target, peak, max gain] x n as floats behind those)
+    const size_t sp_off = 3 * (size_t)n + 1 + (codes ? (size_t)total : 0), ld_off = sp_off + (speed ? 2 * (size_t)n : 0);
+    const size_t m_size = ld_off + (loud ? 4 * (size_t)n : 0);
     if (m_size > c->meta_cap) return cfail(c, NTTS_EINVAL, "meta block too large");
     hipStream_t st = c->stream;
     {
@@ -680,6 +785,7 @@ static int codec_decode_impl(ntts_codec* c, int32_t n, const int32_t* codes, con
             memcpy(m + at, speed, (size_t)n * sizeof(int)); at += n;
             for (int i = 0; i < n; ++i) m[at++] = (int)stretch_len((int64_t)hop * lens[i], speed[i]);
         }
+        if (loud) { loud_pack(m + at, loud, n); at += 4 * (size_t)n; }
         CHIP(c, hipMemcpyAsync(c->meta, m, at * sizeof(int), hipMemcpyHostToDevice, st));
         c->meta_used[k] = true;
         CHIP(c, hipEventRecord(c->meta_ev[k], st));
@@ -766,10 +872,14 @@ static int codec_decode_impl(ntts_codec* c, int32_t n, const int32_t* codes, con
     const int* fin_lens = R.lens;
     int fin_mul = hop;
     if (speed) {                           // the time stretch: the stretched buffer becomes the copy's source, or the output stage's input
-        const int* sp = c->meta + (m_size - 2 * (size_t)n);
+        const int* sp = c->meta + sp_off;
         const int rc = wav_stretch_launch(c, c->wav, (long)hop * Tmax, R.lens, hop, sp, sp + n, n, s_max, st);
         if (rc != NTTS_OK) return rc;
         src = fin = c->sbuf; fin_stride = (long)s_max; fin_lens = sp + n; fin_mul = 1;
+    }
+    if (loud) {                            // the loudness: every row scaled where it stands (c->wav / c->sbuf are this pass's own, nobody reads them later)
+        const int rc = wav_loud_launch(c, const_cast<float*>(fin), fin_stride, fin_lens, fin_mul, c->meta + ld_off, n, s_max, st);
+        if (rc != NTTS_OK) return rc;
     }
     if (wf) {                              // the output stage: the formatted buffer becomes the copy's source
         const int rc = wav_format_launch(c, *wf, fin, fin_stride, fin_lens, fin_mul, n, row_len, st);
@@ -997,6 +1107,135 @@ extern "C" int ntts_codec_last_stretch_timing(ntts_codec* c, float* search_ms, f
     CHIP(c, hipEventSynchronize(c->ev_s[2]));
     CHIP(c, hipEventElapsedTime(search_ms, c->ev_s[0], c->ev_s[1]));
     CHIP(c, hipEventElapsedTime(render_ms, c->ev_s[1], c->ev_s[2]));
+    return NTTS_OK;
+}
+
+// ntts_codec_decode_speed / ntts_codec_decode_dev_speed with a loudness per utterance (null, or every enable 0: the very same calls)
+extern "C" int ntts_codec_decode_loud(ntts_codec* c, int32_t n, const int32_t* codes, const int32_t* lens, const int32_t* speed_permille,
+                                      const ntts_wav_loudness* loudness, const ntts_wav_format* fmt, void* out, int64_t out_stride,
+                                      int32_t* out_lens) {
+    if (!c) return NTTS_EINVAL;
+    if (!codes || !out_lens) return cfail(c, NTTS_EINVAL, "null/empty argument");
+    WavFmt w;
+    const int rc = wav_fmt_check(c, fmt, &w);
+    if (rc != NTTS_OK) return rc;
+    return codec_decode_impl(c, n, codes, nullptr, 0, lens, out, out_stride, 0, nullptr, &w, out_lens, speed_permille, loudness);
+}
+
+extern "C" int ntts_codec_decode_dev_loud(ntts_codec* c, int32_t n, const int32_t* codes_dev, int32_t codes_stride, const int32_t* lens,
+                                          const int32_t* speed_permille, const ntts_wav_loudness* loudness, void* out, int64_t out_stride,
+                                          int32_t out_on_device, void* producer_stream, const ntts_wav_format* fmt, int32_t* out_lens) {
+    if (!c) return NTTS_EINVAL;
+    if (!codes_dev || !out_lens) return cfail(c, NTTS_EINVAL, "null/empty argument");
+    WavFmt w;
+    const int rc = wav_fmt_check(c, fmt, &w);
+    if (rc != NTTS_OK) return rc;
+    return codec_decode_impl(c, n, nullptr, codes_dev, codes_stride, lens, out, out_stride, out_on_device ? 2 : 1, (hipStream_t)producer_stream, &w,
+                             out_lens, speed_permille, loudness);
+}
+
+// The loudness stage (and the output stage behind it) alone on the caller's 24 kHz float32 waveforms, in ntts_codec_stretch's rounds.
+// loud == null: measure only (out / w unused).  measured (may be null): (L, peak, g) per row.
+static int loud_rounds(ntts_codec* c, int32_t n, const float* wav, int64_t in_stride, const int32_t* n_samples, const ntts_wav_loudness* loud,
+                       const WavFmt* w, void* out, int64_t out_stride, int64_t Lmax, double* measured) {
+    if (Lmax == 0) {                       // nothing but empty rows: unmeasurable, nothing to launch
+        if (measured)
+            for (int i = 0; i < n; ++i) { measured[3 * i] = NAN; measured[3 * i + 1] = 0.0; measured[3 * i + 2] = 1.0; }
+        return NTTS_OK;
+    }
+    CHIP(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    const bool plain = !w || w->plain();
+    const size_t esz = plain ? sizeof(float) : w->esz;
+    const int64_t row_len = w ? w->out_len(Lmax) : Lmax;
+    const size_t row_bytes = (size_t)row_len * esz;
+    const int per_round = (int)std::min<int64_t>(std::min<int64_t>((int64_t)c->wav_cap / Lmax, c->max_rows), (int64_t)c->meta_cap / 5);
+    for (int i0 = 0; i0 < n; i0 += per_round) {
+        const int nb = std::min(per_round, n - i0);
+        const int k = c->meta_next;            // [samples nb][enable, target, peak, max gain x nb] through the page-locked meta ring
+        c->meta_next = (k + 1) % ntts_codec::kMetaStages;
+        if (c->meta_used[k]) CHIP(c, hipEventSynchronize(c->meta_ev[k]));
+        int* m = c->meta_host[k];
+        memcpy(m, n_samples + i0, (size_t)nb * sizeof(int));
+        if (loud) loud_pack(m + nb, loud + i0, nb);
+        CHIP(c, hipMemcpyAsync(c->meta, m, (loud ? 5 : 1) * (size_t)nb * sizeof(int), hipMemcpyHostToDevice, st));
+        c->meta_used[k] = true;
+        CHIP(c, hipEventRecord(c->meta_ev[k], st));
+        CHIP(c, hipMemcpy2DAsync(c->wav, (size_t)Lmax * sizeof(float), wav + (size_t)i0 * in_stride, (size_t)in_stride * sizeof(float),
+                                 (size_t)Lmax * sizeof(float), nb, hipMemcpyHostToDevice, st));
+        CHIP(c, hipEventRecord(c->ev[0], st));
+        int rc = wav_loud_launch(c, c->wav, (long)Lmax, c->meta, 1, loud ? c->meta + nb : nullptr, nb, Lmax, st);
+        if (rc != NTTS_OK) return rc;
+        const void* src = c->wav;
+        if (out && !plain) {
+            rc = wav_format_launch(c, *w, c->wav, (long)Lmax, c->meta, 1, nb, row_len, st);
+            if (rc != NTTS_OK) return rc;
+            src = c->fbuf;
+        }
+        CHIP(c, hipEventRecord(c->ev[1], st));
+        c->have_time = true;
+        if (out)
+            CHIP(c, hipMemcpy2DAsync((char*)out + (size_t)i0 * out_stride * esz, (size_t)out_stride * esz, src, row_bytes, row_bytes, nb,
+                                     hipMemcpyDeviceToHost, st));
+        if (measured) CHIP(c, hipMemcpyAsync(measured + 3 * (size_t)i0, c->lres, 3 * (size_t)nb * sizeof(double), hipMemcpyDeviceToHost, st));
+        CHIP(c, hipStreamSynchronize(st));
+        CHIP(c, hipGetLastError());
+    }
+    return NTTS_OK;
+}
+// what ntts_codec_stretch checks of its rows: every n_samples inside [0, in_stride] and the engine's longest utterance; *Lmax = the longest
+static int loud_rows_check(ntts_codec* c, int32_t n, int64_t in_stride, const int32_t* n_samples, int64_t* Lmax) {
+    const int64_t cap = (int64_t)c->cfg.max_frames * c->cfg.hop_length;
+    *Lmax = 0;
+    for (int i = 0; i < n; ++i) {
+        if (n_samples[i] < 0 || n_samples[i] > in_stride)
+            return cfail(c, NTTS_EINVAL, "utterance %d: n_samples %d outside [0, in_stride %ld]", i, n_samples[i], (long)in_stride);
+        if (n_samples[i] > cap) return cfail(c, NTTS_EINVAL, "utterance %d: %d samples exceed the engine's %ld (max_frames x hop)", i, n_samples[i], (long)cap);
+        *Lmax = std::max<int64_t>(*Lmax, n_samples[i]);
+    }
+    return NTTS_OK;
+}
+
+extern "C" int ntts_codec_normalize(ntts_codec* c, int32_t n, const float* wav, int64_t in_stride, const int32_t* n_samples,
+                                    const ntts_wav_loudness* loudness, const ntts_wav_format* fmt, void* out, int64_t out_stride, int32_t* out_lens,
+                                    double* measured) {
+    if (!c) return NTTS_EINVAL;
+    if (n < 1 || !wav || !n_samples || !loudness || !out || !out_lens || in_stride < 0) return cfail(c, NTTS_EINVAL, "null/empty argument");
+    WavFmt w;
+    int rc = wav_fmt_check(c, fmt, &w);
+    if (rc != NTTS_OK) return rc;
+    bool any;
+    rc = loud_check(c, loudness, n, &any);
+    if (rc != NTTS_OK) return rc;
+    int64_t Lmax;
+    rc = loud_rows_check(c, n, in_stride, n_samples, &Lmax);
+    if (rc != NTTS_OK) return rc;
+    const int64_t row_len = w.out_len(Lmax);
+    if (out_stride < row_len) return cfail(c, NTTS_EINVAL, "out_stride %ld < %ld samples", (long)out_stride, (long)row_len);
+    if (!any && !measured)                 // no row has the option on and nobody asks for the figures: the output stage alone
+        return ntts_codec_convert(c, n, wav, in_stride, n_samples, fmt, out, out_stride, out_lens);
+    for (int i = 0; i < n; ++i) out_lens[i] = (int32_t)w.out_len(n_samples[i]);
+    return loud_rounds(c, n, wav, in_stride, n_samples, loudness, &w, out, out_stride, Lmax, measured);
+}
+
+extern "C" int ntts_codec_measure_loudness(ntts_codec* c, int32_t n, const float* wav, int64_t in_stride, const int32_t* n_samples,
+                                           double* measured) {
+    if (!c) return NTTS_EINVAL;
+    if (n < 1 || !wav || !n_samples || !measured || in_stride < 0) return cfail(c, NTTS_EINVAL, "null/empty argument");
+    int64_t Lmax;
+    const int rc = loud_rows_check(c, n, in_stride, n_samples, &Lmax);
+    if (rc != NTTS_OK) return rc;
+    return loud_rounds(c, n, wav, in_stride, n_samples, nullptr, nullptr, nullptr, 0, Lmax, measured);
+}
+
+// GPU milliseconds of the measure and the apply kernel of the most recent loudness stage
+extern "C" int ntts_codec_last_loudness_timing(ntts_codec* c, float* measure_ms, float* apply_ms) {
+    if (!c || !measure_ms || !apply_ms) return NTTS_EINVAL;
+    if (!c->have_loud_time) return cfail(c, NTTS_ESTATE, "no loudness stage has run on this engine");
+    CHIP(c, hipSetDevice(c->device));
+    CHIP(c, hipEventSynchronize(c->ev_l[3]));
+    CHIP(c, hipEventElapsedTime(measure_ms, c->ev_l[0], c->ev_l[1]));
+    CHIP(c, hipEventElapsedTime(apply_ms, c->ev_l[2], c->ev_l[3]));
     return NTTS_OK;
 }
 

@@ -1067,4 +1067,161 @@ NTTS_KERNEL(256) void wav_stretch_stream_kernel(SpeedStreamArgs p, int job0, int
     if (threadIdx.x == 0) p.state[j.u] = SpeedStreamState{(int)prev, (int)keep};
 }
 
+// ---- loudness normalisation between the time stretch and the output stage: ITU-R BS.1770-4 integrated loudness, one gain per utterance -------------
+// The reference has no such stage (ref:neutts/neutts.py:288-291 hands out the level the reference clip had); its users run a loudness normaliser on
+// the 24 kHz float waveform on the host.  Here: K-weighting (two biquads, coefficients built on the host in double), z_j = the mean square of the
+// filter output over the 100 ms sub-block j, both biquads started from zero state at sample max(0, (j - 1) * kLoudSub) -- every z_j a function of
+// 4800 input samples, so all sub-blocks run side by side; gating blocks of four sub-blocks, the absolute gate at -70 and the relative gate 10 LU
+// under the mean of what passed it; g = min(10^((target - L) / 20), 10^(max_gain_db / 20), 10^(peak_dbfs / 20) / peak) in double, rounded once to
+// float32; out = x * g in fp32 (g == 1: the row is not touched).  Filters, sums and the gate run in fp64.  tests/loudness_spec.py is the contract.
+constexpr int kLoudSub = 2400;                        // samples of a sub-block
+constexpr int kLoudLanes = 64;                        // sub-blocks per workgroup: one per lane of its single wave
+constexpr int kLoudChunk = 32;                        // samples staged per lane and round; kLoudSub = 75 rounds
+constexpr int kLoudRow = kLoudChunk + 1;              // LDS row of a lane, padded: lane l reads bank (l + m) % 32, the staging writes bank (seg + o) % 32
+constexpr int kLoudRounds = 2 * kLoudSub / kLoudChunk;
+static_assert(kLoudSub % kLoudChunk == 0, "the sub-block's own part starts on a round");
+struct WavLoudArgs {
+    float* io;             // [B][stride] 24 kHz float32, scaled in place by the apply kernel
+    long stride;
+    const int* lens;       // [B]; utterance b holds lens[b] * len_mul samples (as WavFormatArgs)
+    int len_mul;
+    const float* par;      // [B][4]: enable (0 / 1), target_lufs, peak_dbfs, max_gain_db; null: measure only, every gain 1
+    double kw[7];          // shelf b0 b1 b2 a1 a2, high-pass a1 a2 (its b is 1 -2 1)
+    double* z;             // [B][z_stride] sub-block powers
+    long z_stride;
+    float* pk;             // [B][pk_stride] max |x| per workgroup of the measure kernel (+inf: a non-finite sample)
+    int pk_stride;
+    double* res;           // [B][3]: L (NaN = unmeasurable), peak, g
+};
+// this thread's share of round k: element o = t & 31 of the segments 2 i + (t >> 5) -- 64 consecutive lanes read 2 x 32 consecutive floats
+NTTS_D void loud_fetch(float (&r)[kLoudChunk], const float* x, long n, long base, int jn, int k) {
+    const int o = threadIdx.x & 31, half = threadIdx.x >> 5;
+#pragma unroll
+    for (int i = 0; i < kLoudChunk; ++i) {
+        const int seg = 2 * i + half;
+        const long idx = base + (long)seg * kLoudSub + (long)k * kLoudChunk + o;
+        r[i] = (seg < jn && idx >= 0 && idx < n) ? x[idx] : 0.f;          // (ahead of sub-block 0: zeros, which leave the zero state as it is)
+    }
+}
+// grid (B, max(1, ceil(most sub-blocks / kLoudLanes))), one wave: lane l runs sub-block j0 + l through 4800 samples, staged through LDS 32 per lane at
+// a time with the next round's loads in flight; the workgroup that holds a row's last sub-block also takes the peak of the unmeasured tail
+NTTS_KERNEL(64) void wav_loud_measure_kernel(WavLoudArgs p) {
+    NTTS_SHARED float stage[kLoudLanes * kLoudRow];
+    const int b = blockIdx.x, t = threadIdx.x;
+    const long n = (long)p.lens[b] * p.len_mul;
+    const long J = n / kLoudSub;
+    const long j0 = (long)blockIdx.y * kLoudLanes;
+    const float* x = p.io + (long)b * p.stride;
+    float pk = 0.f;
+    bool bad = false;
+    if (j0 < J) {                                           // (block-uniform)
+        const int jn = (int)(J - j0 < kLoudLanes ? J - j0 : kLoudLanes);
+        const long base = (j0 - 1) * kLoudSub;
+        const double b0 = p.kw[0], b1 = p.kw[1], b2 = p.kw[2], a1 = p.kw[3], a2 = p.kw[4], c1 = p.kw[5], c2 = p.kw[6];
+        double s1 = 0.0, s2 = 0.0, t1 = 0.0, t2 = 0.0, acc = 0.0;
+        float r[kLoudChunk];
+        loud_fetch(r, x, n, base, jn, 0);
+        const float* mine = stage + t * kLoudRow;
+        for (int k = 0; k < kLoudRounds; ++k) {
+            lds_barrier();                                  // everybody has read round k - 1
+#pragma unroll
+            for (int i = 0; i < kLoudChunk; ++i) stage[(2 * i + (t >> 5)) * kLoudRow + (t & 31)] = r[i];
+            lds_barrier();
+            if (k + 1 < kLoudRounds) loud_fetch(r, x, n, base, jn, k + 1);
+            const bool own = k >= kLoudRounds / 2;          // the sub-block's own samples: summed, and part of the peak
+#pragma unroll 8
+            for (int m = 0; m < kLoudChunk; ++m) {
+                const float xf = mine[m];
+                const double v = (double)xf;
+                const double y = b0 * v + s1;               // the shelf, transposed direct form II
+                s1 = b1 * v - a1 * y + s2;
+                s2 = b2 * v - a2 * y;
+                const double w = y + t1;                    // the high-pass
+                t1 = -2.0 * y - c1 * w + t2;
+                t2 = y - c2 * w;
+                if (own) {
+                    acc += w * w;
+                    const float a = __builtin_fabsf(xf);
+                    bad |= !(a <= 3.402823466e38f);
+                    pk = fmaxf(pk, a);
+                }
+            }
+        }
+        if (t < jn) p.z[(long)b * p.z_stride + j0 + t] = acc / (double)kLoudSub;
+    }
+    const long y_tail = J > 0 ? (J - 1) / kLoudLanes : 0;
+    if (blockIdx.y == y_tail)
+        for (long i = J * kLoudSub + t; i < n; i += kLoudLanes) {
+            const float a = __builtin_fabsf(x[i]);
+            bad |= !(a <= 3.402823466e38f);
+            pk = fmaxf(pk, a);
+        }
+    if (bad) pk = INFINITY;
+    for (int m = 32; m >= 1; m >>= 1) pk = fmaxf(pk, shfl_xor(pk, m));
+    if (t == 0) p.pk[(long)b * p.pk_stride + blockIdx.y] = pk;
+}
+// the sum of the 64 partial sums and counts, by thread 0, in lane order
+NTTS_D void loud_total(const double* red, const int* cnt, double* s, int* c) {
+    *s = 0.0; *c = 0;
+    for (int i = 0; i < kLoudLanes; ++i) { *s += red[i]; *c += cnt[i]; }
+}
+// grid (B), one wave: the two gates over the row's blocks, then L, the peak and the gain
+NTTS_KERNEL(64) void wav_loud_gate_kernel(WavLoudArgs p) {
+    NTTS_SHARED double red[kLoudLanes];
+    NTTS_SHARED int cnt[kLoudLanes];
+    NTTS_SHARED double gam[1];
+    const int b = blockIdx.x, t = threadIdx.x;
+    const long n = (long)p.lens[b] * p.len_mul;
+    const long J = n / kLoudSub, nb = J >= 4 ? J - 3 : 0;
+    const double* z = p.z + (long)b * p.z_stride;
+    float pk = 0.f;
+    for (int y = t; y < p.pk_stride; y += kLoudLanes) pk = fmaxf(pk, p.pk[(long)b * p.pk_stride + y]);
+    for (int m = 32; m >= 1; m >>= 1) pk = fmaxf(pk, shfl_xor(pk, m));
+    double s = 0.0;
+    int c = 0;
+    for (long i = t; i < nb; i += kLoudLanes) {             // the absolute gate
+        const double P = (z[i] + z[i + 1] + z[i + 2] + z[i + 3]) * 0.25;
+        if (-0.691 + 10.0 * log10(P) > -70.0) { s += P; ++c; }
+    }
+    red[t] = s; cnt[t] = c;
+    sync();
+    if (t == 0) {
+        loud_total(red, cnt, &s, &c);
+        gam[0] = c > 0 ? -0.691 + 10.0 * log10(s / c) - 10.0 : (double)NAN;
+    }
+    sync();
+    const double gamma = gam[0];
+    s = 0.0; c = 0;
+    for (long i = t; i < nb; i += kLoudLanes) {             // the relative gate (nothing passes a NaN threshold)
+        const double P = (z[i] + z[i + 1] + z[i + 2] + z[i + 3]) * 0.25;
+        const double l = -0.691 + 10.0 * log10(P);
+        if (l > -70.0 && l > gamma) { s += P; ++c; }
+    }
+    red[t] = s; cnt[t] = c;
+    sync();
+    if (t != 0) return;
+    loud_total(red, cnt, &s, &c);
+    const double L = (c > 0 && pk <= 3.402823466e38f) ? -0.691 + 10.0 * log10(s / c) : (double)NAN;
+    float g = 1.0f;
+    const float* par = p.par ? p.par + 4L * b : nullptr;
+    if (par && par[0] != 0.f && L == L) {
+        double gd = fmin(pow(10.0, ((double)par[1] - L) / 20.0), pow(10.0, (double)par[3] / 20.0));
+        if (pk > 0.f) gd = fmin(gd, pow(10.0, (double)par[2] / 20.0) / (double)pk);
+        g = (float)gd;
+    }
+    p.res[3L * b] = L; p.res[3L * b + 1] = (double)pk; p.res[3L * b + 2] = (double)g;
+}
+// grid (B, ceil(longest row / 1024)): x *= g in place; a row whose gain is 1 is not touched
+NTTS_KERNEL(256) void wav_loud_apply_kernel(WavLoudArgs p) {
+    const int b = blockIdx.x;
+    const float g = (float)p.res[3L * b + 2];
+    if (g == 1.0f) return;
+    const long n = (long)p.lens[b] * p.len_mul;
+    float* x = p.io + (long)b * p.stride;
+    for (int k = 0; k < 4; ++k) {
+        const long i = (long)blockIdx.y * 1024 + k * 256 + threadIdx.x;
+        if (i < n) x[i] = x[i] * g;
+    }
+}
+
 }  // namespace ntts

@@ -50,6 +50,10 @@ class WavFormatC(C.Structure):
     _fields_ = [("sample_rate", C.c_int32), ("encoding", C.c_int32), ("filter_width", C.c_int32)]
 
 
+class WavLoudnessC(C.Structure):
+    _fields_ = [("enable", C.c_int32), ("target_lufs", C.c_float), ("peak_dbfs", C.c_float), ("max_gain_db", C.c_float)]
+
+
 class EncoderConfigC(C.Structure):
     _fields_ = [("sem_hidden", C.c_int32), ("sem_layers", C.c_int32), ("sem_heads", C.c_int32), ("sem_ffn", C.c_int32),
                 ("sem_conv_kernel", C.c_int32), ("sem_left", C.c_int32), ("sem_right", C.c_int32), ("sem_ln_eps", C.c_float),
@@ -174,6 +178,14 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "ntts_codec_decode_dev_speed": (C.c_int, [p, i32, p, i32, C.POINTER(i32), C.POINTER(i32), p, i64, i32, p, C.POINTER(WavFormatC),
                                                   C.POINTER(i32)]),
         "ntts_codec_last_stretch_timing": (C.c_int, [p, C.POINTER(f32), C.POINTER(f32)]),
+        "ntts_codec_normalize": (C.c_int, [p, i32, C.POINTER(f32), i64, C.POINTER(i32), C.POINTER(WavLoudnessC), C.POINTER(WavFormatC), p, i64,
+                                           C.POINTER(i32), C.POINTER(C.c_double)]),
+        "ntts_codec_measure_loudness": (C.c_int, [p, i32, C.POINTER(f32), i64, C.POINTER(i32), C.POINTER(C.c_double)]),
+        "ntts_codec_decode_loud": (C.c_int, [p, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(WavLoudnessC), C.POINTER(WavFormatC), p,
+                                             i64, C.POINTER(i32)]),
+        "ntts_codec_decode_dev_loud": (C.c_int, [p, i32, p, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(WavLoudnessC), p, i64, i32, p,
+                                                 C.POINTER(WavFormatC), C.POINTER(i32)]),
+        "ntts_codec_last_loudness_timing": (C.c_int, [p, C.POINTER(f32), C.POINTER(f32)]),
         "ntts_wav_stream_create": (C.c_int, [p, C.POINTER(WavFormatC), i32, i32, C.POINTER(p)]),
         "ntts_wav_stream_destroy": (None, [p]),
         "ntts_wav_stream_last_error": (C.c_char_p, [p]),
@@ -308,6 +320,48 @@ def speed_permille(speed, n: int, who: str = "") -> Optional[np.ndarray]:
 def wav_stretch_len(n_in: int, permille: int) -> int:
     """Samples of n_in samples at a speed per mille: ceil(n_in * 1000 / permille) (ntts_wav_stretch_len's arithmetic)."""
     return -(-int(n_in) * 1000 // int(permille))
+
+
+# ---- loudness: BS.1770 loudness normalisation between the time stretch and the output stage (include/neutts_hip.h ntts_codec_normalize)
+LOUDNESS_TARGET_RANGE, LOUDNESS_PEAK_RANGE, LOUDNESS_MAX_GAIN_RANGE = (-70.0, 0.0), (-20.0, 0.0), (0.0, 60.0)
+LOUDNESS_PEAK_DEFAULT, LOUDNESS_MAX_GAIN_DEFAULT = -1.0, 20.0
+
+
+def _loudness_number(v, lo: float, hi: float, what: str, unit: str) -> float:
+    ok = not isinstance(v, (bool, np.bool_)) and isinstance(v, (int, float, np.integer, np.floating)) and np.isfinite(v)
+    if not ok or not lo <= float(v) <= hi:
+        raise ValueError(f"{what} must be a number in [{lo:g}, {hi:g}] {unit} (got {v!r})")
+    return float(v)
+
+
+def loudness_params(loudness, peak=LOUDNESS_PEAK_DEFAULT, max_gain=LOUDNESS_MAX_GAIN_DEFAULT, n: int = 1, who: str = ""):
+    """Checked loudness settings of n utterances as the engine's ntts_wav_loudness array, or None when no utterance has the option on.  loudness:
+    the target in LUFS, one value or one per utterance; None (or a None entry) = off.  peak (the sample-peak ceiling in dBFS) and max_gain (dB) are
+    one value for the call.  ValueError names the bad value."""
+    if loudness is None:
+        return None
+    vals = list(loudness) if isinstance(loudness, (list, tuple, np.ndarray)) else [loudness] * n
+    if len(vals) != n:
+        raise ValueError(f"{who}loudness: {len(vals)} values for {n} utterances")
+    if all(v is None for v in vals):
+        return None
+    peak = _loudness_number(peak, *LOUDNESS_PEAK_RANGE, f"{who}loudness_peak", "dBFS")
+    max_gain = _loudness_number(max_gain, *LOUDNESS_MAX_GAIN_RANGE, f"{who}loudness_max_gain", "dB")
+    arr = (WavLoudnessC * n)()
+    for i, v in enumerate(vals):
+        if v is None:
+            arr[i] = WavLoudnessC(0, 0.0, 0.0, 0.0)
+        else:
+            arr[i] = WavLoudnessC(1, _loudness_number(v, *LOUDNESS_TARGET_RANGE, f"{who}loudness", "LUFS"), peak, max_gain)
+    return arr
+
+
+def _loudness_rows(arr, rows):
+    """The entries `rows` of an ntts_wav_loudness array, as a new array."""
+    sub = (WavLoudnessC * len(rows))()
+    for k, j in enumerate(rows):
+        sub[k] = arr[j]
+    return sub
 
 
 @dataclass
@@ -1412,9 +1466,10 @@ class CodecEngine:
             self._pin_ptr, self._pin_cap = ptr, nbytes
         return np.frombuffer((C.c_char * nbytes).from_address(self._pin_ptr.value), dtype=dtype, count=n)
 
-    def _decode_call(self, n: int, flat: np.ndarray, lens: np.ndarray, tmax: int, fmt, reuse_output: bool, pm: Optional[np.ndarray] = None):
-        """One ntts_codec_decode / ntts_codec_decode_fmt / ntts_codec_decode_speed call -> ([n, stride] array of the format's dtype, samples per
-        utterance).  pm: speeds per mille (int32 [n]) or None."""
+    def _decode_call(self, n: int, flat: np.ndarray, lens: np.ndarray, tmax: int, fmt, reuse_output: bool, pm: Optional[np.ndarray] = None,
+                     loud=None):
+        """One ntts_codec_decode / ntts_codec_decode_fmt / ntts_codec_decode_speed / ntts_codec_decode_loud call -> ([n, stride] array of the
+        format's dtype, samples per utterance).  pm: speeds per mille (int32 [n]) or None; loud: an ntts_wav_loudness array [n] or None."""
         fc, dtype, native = fmt
         i32p = C.POINTER(C.c_int32)
         if pm is None:
@@ -1423,12 +1478,16 @@ class CodecEngine:
             pm = np.ascontiguousarray(pm, dtype=np.int32)
             stride = wav_out_len(max(wav_stretch_len(self.hop_length * int(t), int(s)) for t, s in zip(lens, pm)), fc.sample_rate)
         wav = (self._pinned(n * stride, dtype) if reuse_output else np.empty(n * stride, dtype=dtype)).reshape(n, stride)
-        if native and pm is None:        # the plain entry point: the calls and the bits of an engine without the output stage
+        if native and pm is None and loud is None:        # the plain entry point: the calls and the bits of an engine without the output stage
             self._chk(self.lib.ntts_codec_decode(self.h, n, flat.ctypes.data_as(i32p), lens.ctypes.data_as(i32p),
                                                  wav.ctypes.data_as(C.POINTER(C.c_float)), stride))
             return wav, self.hop_length * lens.astype(np.int64)
         out_lens = np.zeros(n, dtype=np.int32)
-        if pm is None:
+        if loud is not None:
+            self._chk(self.lib.ntts_codec_decode_loud(self.h, n, flat.ctypes.data_as(i32p), lens.ctypes.data_as(i32p),
+                                                      None if pm is None else pm.ctypes.data_as(i32p), loud, C.byref(fc),
+                                                      C.c_void_p(wav.ctypes.data), stride, out_lens.ctypes.data_as(i32p)))
+        elif pm is None:
             self._chk(self.lib.ntts_codec_decode_fmt(self.h, n, flat.ctypes.data_as(i32p), lens.ctypes.data_as(i32p), C.byref(fc),
                                                      C.c_void_p(wav.ctypes.data), stride, out_lens.ctypes.data_as(i32p)))
         else:
@@ -1437,16 +1496,21 @@ class CodecEngine:
         return wav, out_lens
 
     def decode(self, codes: Sequence[Sequence[int]], reuse_output: bool = False, sample_rate=None, encoding="f32",
-               filter_width=None, speed=None) -> List[np.ndarray]:
+               filter_width=None, speed=None, loudness=None, loudness_peak=LOUDNESS_PEAK_DEFAULT,
+               loudness_max_gain=LOUDNESS_MAX_GAIN_DEFAULT) -> List[np.ndarray]:
         """codes: one int sequence per utterance -> list of waveforms: float32 at 24 kHz, hop_length * len samples each, by default;
         sample_rate (one of WAV_RATES) / encoding ("f32", "pcm16" -> int16, "mulaw" -> uint8) / filter_width (the resampler's
         lowpass_filter_width, 1..64, default 6) put the device output stage behind the pass: ceil(hop_length * len * rate / 24000) samples.
         speed (0.5 .. 2.0, one value or one per utterance; None = 1.0) puts the time stretch between the pass and the output stage: the pitch stays,
         the utterance takes ceil(hop_length * len / speed) samples at 24 kHz (ntts_codec_decode_speed).
+        loudness (a target in LUFS, -70 .. 0, one value or one per utterance; None or a None entry = off) puts the BS.1770 loudness normalisation
+        between the stretch and the output stage: one gain per utterance, held by loudness_max_gain (dB) and by the sample-peak ceiling
+        loudness_peak (dBFS) (ntts_codec_decode_loud).
         reuse_output=True returns views into an engine-owned pinned buffer (fast D2H, no copy): they are only valid
         until the next decode() call on this engine."""
         fmt = wav_format(sample_rate, encoding, filter_width)
         pm = speed_permille(speed, len(codes))
+        loud = loudness_params(loudness, loudness_peak, loudness_max_gain, len(codes))
         out: List[Optional[np.ndarray]] = [None] * len(codes)
         order = sorted(range(len(codes)), key=lambda i: -len(codes[i]))   # batch similar lengths together
         i = 0
@@ -1458,7 +1522,7 @@ class CodecEngine:
             flat = np.ascontiguousarray(np.concatenate([np.asarray(codes[j], dtype=np.int32) for j in grp]))
             # (pinned fast path when a single call covers the batch)
             wav, out_lens = self._decode_call(len(grp), flat, lens, tmax, fmt, reuse_output and i == 0 and nb == len(order),
-                                              None if pm is None else pm[grp])
+                                              None if pm is None else pm[grp], None if loud is None else _loudness_rows(loud, grp))
             for r, j in enumerate(grp):
                 out[j] = wav[r, : int(out_lens[r])]     # view into this call's buffer: no second copy
             i += nb
@@ -1532,6 +1596,57 @@ class CodecEngine:
         self._chk(self.lib.ntts_codec_last_stretch_timing(self.h, C.byref(a), C.byref(b)))
         return a.value, b.value
 
+    @staticmethod
+    def _rows_of(wavs):
+        """1-D waveforms -> ([n, longest] float32 with zeros behind each row, samples per row)."""
+        n_samples = np.array([len(w) for w in wavs], dtype=np.int32)
+        buf = np.zeros((len(wavs), max(1, int(n_samples.max()))), dtype=np.float32)
+        for r, w in enumerate(wavs):
+            buf[r, : len(w)] = w
+        return buf, n_samples
+
+    def normalize(self, wavs: Sequence[np.ndarray], loudness, loudness_peak=LOUDNESS_PEAK_DEFAULT, loudness_max_gain=LOUDNESS_MAX_GAIN_DEFAULT,
+                  sample_rate=None, encoding="f32", filter_width=None, return_measured: bool = False):
+        """24 kHz float waveforms (one 1-D array each; e.g. what a watermarker handed back) -> the same at the loudness `decode` with these arguments
+        would have given them, in the output format (ntts_codec_normalize).  return_measured=True: (waveforms, float64 [n, 3]) with row i =
+        (integrated loudness in LUFS, NaN where the row is unmeasurable; sample peak; the gain applied)."""
+        wavs = [np.asarray(w, dtype=np.float32).reshape(-1) for w in wavs]
+        fc, dtype, _ = wav_format(sample_rate, encoding, filter_width)
+        loud = loudness_params(loudness, loudness_peak, loudness_max_gain, len(wavs))
+        if not wavs:
+            return ([], np.zeros((0, 3))) if return_measured else []
+        if loud is None:
+            loud = (WavLoudnessC * len(wavs))()
+        buf, n_samples = self._rows_of(wavs)
+        out_stride = wav_out_len(int(n_samples.max()), fc.sample_rate)
+        out = np.zeros((len(wavs), max(1, out_stride)), dtype=dtype)
+        out_lens = np.zeros(len(wavs), dtype=np.int32)
+        measured = np.zeros((len(wavs), 3), dtype=np.float64)
+        i32p = C.POINTER(C.c_int32)
+        self._chk(self.lib.ntts_codec_normalize(self.h, len(wavs), buf.ctypes.data_as(C.POINTER(C.c_float)), buf.shape[1], n_samples.ctypes.data_as(i32p),
+                                                loud, C.byref(fc), C.c_void_p(out.ctypes.data), out.shape[1], out_lens.ctypes.data_as(i32p),
+                                                measured.ctypes.data_as(C.POINTER(C.c_double)) if return_measured else None))
+        res = [out[r, : int(out_lens[r])] for r in range(len(wavs))]
+        return (res, measured) if return_measured else res
+
+    def measure_loudness(self, wavs: Sequence[np.ndarray]) -> np.ndarray:
+        """24 kHz float waveforms -> float64 [n, 3]: row i = (BS.1770-4 integrated loudness in LUFS, NaN where unmeasurable; sample peak max|x|; 1.0).
+        Nothing is scaled (ntts_codec_measure_loudness)."""
+        wavs = [np.asarray(w, dtype=np.float32).reshape(-1) for w in wavs]
+        measured = np.zeros((len(wavs), 3), dtype=np.float64)
+        if not wavs:
+            return measured
+        buf, n_samples = self._rows_of(wavs)
+        self._chk(self.lib.ntts_codec_measure_loudness(self.h, len(wavs), buf.ctypes.data_as(C.POINTER(C.c_float)), buf.shape[1],
+                                                       n_samples.ctypes.data_as(C.POINTER(C.c_int32)), measured.ctypes.data_as(C.POINTER(C.c_double))))
+        return measured
+
+    def last_loudness_timing(self):
+        """GPU milliseconds (measure kernel, apply kernel) of the most recent loudness stage on this engine."""
+        a, b = C.c_float(), C.c_float()
+        self._chk(self.lib.ntts_codec_last_loudness_timing(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
     def convert_array(self, wav: np.ndarray, n_samples, sample_rate=None, encoding="f32", filter_width=None, out_stride: Optional[int] = None):
         """The output stage alone (ntts_codec_convert): wav [n, in_stride] float32 at 24 kHz, row i valid up to n_samples[i] (what follows is
         never read as signal) -> ([n, out_stride] array of the encoding's dtype, samples per row)."""
@@ -1594,16 +1709,19 @@ class CodecEngine:
 
     def decode_device(self, codes_dev_ptr: int, codes_stride: int, lens: np.ndarray, producer_stream: int = 0,
                       wav_dev_ptr: Optional[int] = None, wav_stride: Optional[int] = None, reuse_output: bool = True,
-                      sample_rate=None, encoding="f32", filter_width=None, speed=None):
+                      sample_rate=None, encoding="f32", filter_width=None, speed=None, loudness=None, loudness_peak=LOUDNESS_PEAK_DEFAULT,
+                      loudness_max_gain=LOUDNESS_MAX_GAIN_DEFAULT):
         """Codes already on the device (BackboneEngine.export_codes) -> waveforms, asynchronously: returns the [n, stride]
         destination (a view of the engine's pinned host buffer, or None when `wav_dev_ptr` names a device buffer);
         call sync() before reading it.  float32 at 24 kHz by default; with an output format (as `decode`) elements of the encoding's dtype,
         stride = wav_out_len(hop_length * max(lens), sample_rate) unless given, row i valid up to wav_out_len(hop_length * lens[i], sample_rate).
-        With speed (as `decode`; ntts_codec_decode_dev_speed) the lengths are those of the stretched utterances."""
+        With speed (as `decode`; ntts_codec_decode_dev_speed) the lengths are those of the stretched utterances; loudness / loudness_peak /
+        loudness_max_gain as `decode` (ntts_codec_decode_dev_loud)."""
         fc, dtype, native = wav_format(sample_rate, encoding, filter_width)
         lens = np.ascontiguousarray(lens, dtype=np.int32)
         n = len(lens)
         pm = speed_permille(speed, n)
+        loud = loudness_params(loudness, loudness_peak, loudness_max_gain, n)
         if pm is None:
             longest = self.hop_length * int(lens.max())
         else:
@@ -1616,7 +1734,12 @@ class CodecEngine:
         else:
             dst, on_dev = wav_dev_ptr, 1
         i32p = C.POINTER(C.c_int32)
-        if native and pm is None:
+        if loud is not None:
+            out_lens = np.zeros(n, dtype=np.int32)
+            self._chk(self.lib.ntts_codec_decode_dev_loud(self.h, n, C.c_void_p(codes_dev_ptr), codes_stride, lens.ctypes.data_as(i32p),
+                                                          None if pm is None else pm.ctypes.data_as(i32p), loud, C.c_void_p(dst), stride, on_dev,
+                                                          C.c_void_p(producer_stream or None), C.byref(fc), out_lens.ctypes.data_as(i32p)))
+        elif native and pm is None:
             self._chk(self.lib.ntts_codec_decode_dev(self.h, n, C.c_void_p(codes_dev_ptr), codes_stride, lens.ctypes.data_as(i32p),
                                                      C.c_void_p(dst), stride, on_dev, C.c_void_p(producer_stream or None)))
         elif pm is None:

@@ -192,6 +192,7 @@ def _check_output(sample_rate, encoding, filter_width, who: str = "") -> None:
 
 
 _INSTANCE_FORMAT = object()      # "the instance's stream_* attributes" as a default argument (None is the native format)
+_INSTANCE = object()             # "the instance's loudness" as a default argument (None switches the option off)
 
 
 def sequence_score(logprobs) -> float:
@@ -232,6 +233,9 @@ class NeuTTS:
         stream_filter_width: Optional[int] = None,
         speed: float = 1.0,
         stream_speed: float = 1.0,
+        loudness: Optional[float] = None,
+        loudness_peak: float = -1.0,
+        loudness_max_gain: float = 20.0,
     ):
         # Consts (ref:neutts/neutts.py:84-91)
         self.sample_rate = 24_000            # the NATIVE rate (the codec's; what a watermarker sees), whatever the output format
@@ -265,6 +269,16 @@ class NeuTTS:
         # longer for it, and a chunk may be empty.  stream_speed= per call overrides it, one value or one per utterance.
         _hip.speed_permille(stream_speed, 1, "stream_")
         self.stream_speed = float(stream_speed)
+        # How loud an utterance comes out: a target in LUFS (-70 .. 0; None = as the codec gives it, which is about as loud as the reference clip
+        # was -- the reference offers nothing, its users normalise on the host).  ITU-R BS.1770-4 integrated loudness (K-weighting, gating) measured
+        # on the device at 24 kHz behind the time stretch and ahead of the output stage, then one gain per utterance (include/neutts_hip.h
+        # ntts_codec_decode_loud): never more than loudness_max_gain dB, and never lifting the SAMPLE peak (not the true, inter-sample peak) above
+        # loudness_peak dBFS.  loudness= per call overrides the target, one value or one per utterance (None = off).  A stream's gain is not known
+        # before its end: the stream entry points refuse the option.
+        _hip.loudness_params(-23.0 if loudness is None else loudness, loudness_peak, loudness_max_gain, 1, "instance ")
+        self.loudness = None if loudness is None else float(loudness)
+        self.loudness_peak = float(loudness_peak)
+        self.loudness_max_gain = float(loudness_max_gain)
         self.max_context = 2048
         self.hop_length = 480
         self.streaming_overlap_frames = 1
@@ -473,14 +487,15 @@ class NeuTTS:
         point takes behind them: repetition_penalty= and repetition_ignore_prompt= (anything else is a TypeError).
         best_of=N: N sampled candidates, the one with the highest mean log-probability is synthesised; return_scores=True: (wav, score).
         sample_rate= / encoding= (two more keywords of the catch-all) override output_sample_rate / output_encoding for this call, speed= (0.5 .. 2.0)
-        the instance's speed."""
+        the instance's speed, loudness= (a target in LUFS; None = off) the instance's loudness."""
         out = self._resolve_output(repetition.pop("sample_rate", None), repetition.pop("encoding", None))
         speed = self._resolve_speed(repetition.pop("speed", None), 1)
+        loud = self._resolve_loudness(repetition.pop("loudness", _INSTANCE), 1)
         best_of, want = self._pop_scoring(1, repetition, "return_scores")
         samp = self._resolve_sampling(1, temperature, top_k, top_p, min_p, repetition)
         prompt_ids = self._apply_chat_template(ref_codes, ref_text, text)
         ids, lps = self._generate_scored([prompt_ids], samp, best_of, want)
-        if out is None and speed is None:
+        if out is None and speed is None and loud is None:
             wav = self._decode_ids(ids[0])
             if self.watermarker is not None:
                 wav = self.watermarker.apply_watermark(wav, sample_rate=24_000)
@@ -488,7 +503,7 @@ class NeuTTS:
             speech_ids = self._ids_to_codes(ids[0])
             if len(speech_ids) == 0:
                 raise ValueError("No valid speech tokens found in the output.")
-            wav = self._decode_formatted([speech_ids], out, speed)[0]
+            wav = self._decode_formatted([speech_ids], out, speed, loud)[0]
         return (wav, sequence_score(lps[0])) if want else wav
 
     def infer_batch(self, texts: Sequence[str], ref_codes, ref_texts, *, temperature=None, top_k=None, top_p=None, min_p=None, **repetition) -> List[np.ndarray]:
@@ -496,9 +511,11 @@ class NeuTTS:
         one codec pass.  The sampling overrides take one value for the call or one per utterance, and so does best_of= (candidates per
         utterance; only the winners go through the codec); return_scores=True: (wavs, scores), score = mean log-probability of the ids.
         sample_rate= / encoding= (two more keywords of the catch-all) override output_sample_rate / output_encoding for this call (one format per call),
-        speed= the instance's speed: one value, or one per utterance."""
+        speed= the instance's speed: one value, or one per utterance; loudness= the instance's loudness target in the same way (None, or a None
+        entry, = off)."""
         out = self._resolve_output(repetition.pop("sample_rate", None), repetition.pop("encoding", None))
         speed = self._resolve_speed(repetition.pop("speed", None), len(texts))
+        loud = self._resolve_loudness(repetition.pop("loudness", _INSTANCE), len(texts))
         best_of, want = self._pop_scoring(len(texts), repetition, "return_scores")
         samp = self._resolve_sampling(len(texts), temperature, top_k, top_p, min_p, repetition)
         if not isinstance(ref_texts, (list, tuple)):
@@ -509,12 +526,12 @@ class NeuTTS:
         codes = [self._ids_to_codes(x) for x in ids]
         if any(len(c) == 0 for c in codes):
             raise ValueError("No valid speech tokens found in the output.")
-        if out is None and speed is None:
+        if out is None and speed is None and loud is None:
             wavs = self.codec.engine.decode(codes)
             if self.watermarker is not None:
                 wavs = [self.watermarker.apply_watermark(w, sample_rate=24_000) for w in wavs]
         else:
-            wavs = self._decode_formatted(codes, out, speed)
+            wavs = self._decode_formatted(codes, out, speed, loud)
         return (wavs, [sequence_score(lp) for lp in lps]) if want else wavs
 
     def infer_stream(self, text: str, ref_codes, ref_text: str, *, temperature=None, top_k=None, top_p=None, min_p=None, **repetition) -> Generator[np.ndarray, None, None]:
@@ -522,9 +539,11 @@ class NeuTTS:
         (checked here, before the generator is handed out).  Chunks are 24 kHz float32 unless stream_sample_rate= / stream_encoding= /
         stream_filter_width= (or the instance's stream_* attributes) say otherwise; sample_rate= / encoding= / a non-native output_* attribute
         stay a ValueError here.  stream_speed= (or the instance's stream_speed) is the speed of this stream, 0.5 .. 2.0: the time stretch on its
-        chunks, ahead of their format; the chunks then lag by up to 40 ms and a frame and may be empty.  speed= other than 1 stays a ValueError."""
+        chunks, ahead of their format; the chunks then lag by up to 40 ms and a frame and may be empty.  speed= other than 1 stays a ValueError, and so
+        does loudness= (or an instance whose loudness is set): an utterance's gain is known only at its end."""
         self._refuse_stream_output(repetition.pop("sample_rate", None), repetition.pop("encoding", None), "infer_stream")
         self._refuse_stream_speed(repetition.pop("speed", None), "infer_stream")
+        self._refuse_stream_loudness(repetition.pop("loudness", _INSTANCE), "infer_stream")
         fmt = self._resolve_stream_output(repetition.pop("stream_sample_rate", None), repetition.pop("stream_encoding", None),
                                           repetition.pop("stream_filter_width", None))
         spd = self._resolve_stream_speed(repetition.pop("stream_speed", None), 1)
@@ -545,6 +564,7 @@ class NeuTTS:
         utterance."""
         self._refuse_stream_output(repetition.pop("sample_rate", None), repetition.pop("encoding", None), "infer_stream_batch")
         self._refuse_stream_speed(repetition.pop("speed", None), "infer_stream_batch")
+        self._refuse_stream_loudness(repetition.pop("loudness", _INSTANCE), "infer_stream_batch")
         fmt = self._resolve_stream_output(repetition.pop("stream_sample_rate", None), repetition.pop("stream_encoding", None),
                                           repetition.pop("stream_filter_width", None))
         spd = self._resolve_stream_speed(repetition.pop("stream_speed", None), len(texts))
@@ -776,16 +796,36 @@ class NeuTTS:
             return x[(x >= 0) & (x < 65536)].astype(np.int32)
         return np.asarray(self._ids_to_codes(np.asarray(ids).tolist()), dtype=np.int32)
 
-    def decode_codes(self, codes: Sequence[Sequence[int]], sample_rate=None, encoding=None, speed=None) -> List[np.ndarray]:
-        """Codec codes -> waveforms in the instance's output format and at the instance's speed (sample_rate= / encoding= / speed= override them for
-        this call; speed one value or one per utterance); no watermark, as before."""
+    def decode_codes(self, codes: Sequence[Sequence[int]], sample_rate=None, encoding=None, speed=None, loudness=_INSTANCE) -> List[np.ndarray]:
+        """Codec codes -> waveforms in the instance's output format, at the instance's speed and loudness (sample_rate= / encoding= / speed= /
+        loudness= override them for this call; speed and loudness one value or one per utterance, loudness=None = off); no watermark, as before."""
         out = self._resolve_output(sample_rate, encoding)
         speed = self._resolve_speed(speed, len(codes))
-        if out is None and speed is None:
+        loud = self._resolve_loudness(loudness, len(codes))
+        if out is None and speed is None and loud is None:
             return self.codec.engine.decode(codes)
-        if out is None:
-            return self.codec.engine.decode(codes, speed=speed)
-        return self.codec.engine.decode(codes, sample_rate=out[0], encoding=out[1], filter_width=out[2], speed=speed)
+        fmt = {} if out is None else dict(sample_rate=out[0], encoding=out[1], filter_width=out[2])
+        if loud is None:
+            return self.codec.engine.decode(codes, speed=speed, **fmt)
+        return self.codec.engine.decode(codes, speed=speed, **loud, **fmt)
+
+    def _resolve_loudness(self, loudness, n: int):
+        """Per-call loudness: not given = the instance attribute; None = off.  -> None when no utterance has the option on (the calls of an instance
+        without the stage), else CodecEngine.decode's three keywords with one checked target (or None) per utterance.  ValueError on a bad value,
+        before the engine is touched."""
+        given = loudness is not _INSTANCE
+        loudness = loudness if given else self.loudness
+        if _hip.loudness_params(loudness, self.loudness_peak, self.loudness_max_gain, n, "" if given else "instance ") is None:
+            return None
+        vals = list(loudness) if isinstance(loudness, (list, tuple, np.ndarray)) else [loudness] * n
+        return dict(loudness=[None if v is None else float(v) for v in vals], loudness_peak=self.loudness_peak,
+                    loudness_max_gain=self.loudness_max_gain)
+
+    def _refuse_stream_loudness(self, loudness, who: str) -> None:
+        if self._resolve_loudness(loudness, 1) is not None:
+            what = f"loudness={loudness!r}" if loudness is not _INSTANCE else f"loudness={self.loudness!r} on the instance"
+            raise ValueError(f"{who} has no loudness normalisation (got {what}): the gain of an utterance is known only at its end, after every chunk "
+                             "but the last has left; loudness is a one-shot stage behind infer / infer_batch / decode_codes")
 
     def _resolve_speed(self, speed, n: int):
         """Per-call speed: None = the instance attribute.  -> None when every utterance runs at 1.0 (the calls of an instance without the stage), else
@@ -867,15 +907,17 @@ class NeuTTS:
         fmt = (None, "f32", None) if fmt is None else fmt
         return self.codec.engine.stream_stretcher(n, spd, fmt[0], fmt[1], fmt[2], max_chunk_samples=longest)
 
-    def _decode_formatted(self, codes: Sequence[Sequence[int]], out, speed=None) -> List[np.ndarray]:
-        """One codec pass with the time stretch (speed: None, or one value per utterance) and the device output stage (out: None = native) behind it.
-        A watermarker is a host library that works on the 24 kHz float waveform: with one present the order is decode with the speed in the native
-        format, watermark on the host, then the output stage alone (CodecEngine.convert)."""
+    def _decode_formatted(self, codes: Sequence[Sequence[int]], out, speed=None, loud=None) -> List[np.ndarray]:
+        """One codec pass with the time stretch (speed: None, or one value per utterance), the loudness normalisation (loud: None, or
+        _resolve_loudness's keywords) and the device output stage (out: None = native) behind it, in that order.
+        A watermarker is a host library that works on the 24 kHz float waveform: with one present the order is decode with the speed and the loudness
+        in the native format, watermark on the host, then the output stage alone (CodecEngine.convert)."""
         eng = self.codec.engine
         fmt = {} if out is None else dict(sample_rate=out[0], encoding=out[1], filter_width=out[2])
+        loud = loud or {}
         if self.watermarker is None:
-            return eng.decode(codes, speed=speed, **fmt)
-        wavs = [self.watermarker.apply_watermark(w, sample_rate=24_000) for w in eng.decode(codes, speed=speed)]
+            return eng.decode(codes, speed=speed, **loud, **fmt)
+        wavs = [self.watermarker.apply_watermark(w, sample_rate=24_000) for w in eng.decode(codes, speed=speed, **loud)]
         return wavs if out is None else eng.convert(wavs, **fmt)
 
     def _decode_ids(self, ids: Sequence[int]) -> np.ndarray:
