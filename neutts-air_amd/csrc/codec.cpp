@@ -74,25 +74,22 @@ struct ntts_codec {
     // is allocated with the first call that needs it, for the engine's whole workspace at that call's rate and element size
     struct WavTable { float* coef; int orig, nw, width, taps; };
     std::map<std::pair<int, int>, WavTable> wav_tables;
-    void* fbuf = nullptr;
-    size_t fbuf_cap = 0;         // bytes
+    // a device buffer of the stages behind overlap-add: allocated by the first call that needs it, grown by a later one (grow), freed with the engine
+    template <typename T>
+    struct Grown { T* p = nullptr; size_t cap = 0; };      // cap counts elements of T
+    Grown<char> fbuf;
     // time stretch (ntts_codec_stretch / _decode_speed): the stretched 24 kHz waveforms and their frame positions, allocated with the first call
     // that needs them for twice the waveform workspace (speed 0.5 doubles a row); the fade table; events around the two kernels
-    float* sbuf = nullptr;
-    size_t sbuf_cap = 0;         // floats
-    int* spos = nullptr;
-    size_t spos_cap = 0;         // ints
+    Grown<float> sbuf;
+    Grown<int> spos;
     float* sfade = nullptr;
     hipEvent_t ev_s[3]{};
     bool have_stretch_time = false;
     // loudness (ntts_codec_normalize / _decode_loud): sub-block powers, the measure kernel's partial peaks and (L, peak, g) per row, allocated with
     // the first call that needs them; the K-weighting coefficients; events around the measure and the apply kernel
-    double* lz = nullptr;
-    size_t lz_cap = 0;           // doubles
-    float* lpk = nullptr;
-    size_t lpk_cap = 0;          // floats
-    double* lres = nullptr;
-    size_t lres_cap = 0;         // doubles
+    Grown<double> lz;
+    Grown<float> lpk;
+    Grown<double> lres;
     double kw[7]{};
     hipEvent_t ev_l[4]{};
     bool have_loud_time = false;
@@ -130,12 +127,8 @@ extern "C" void ntts_codec_destroy(ntts_codec* c) {
     hipDeviceSynchronize();
     for (void* p : c->allocs) hipFree(p);
     if (c->tap) hipFree(c->tap);
-    if (c->fbuf) hipFree(c->fbuf);
-    if (c->sbuf) hipFree(c->sbuf);
-    if (c->spos) hipFree(c->spos);
-    if (c->lz) hipFree(c->lz);
-    if (c->lpk) hipFree(c->lpk);
-    if (c->lres) hipFree(c->lres);
+    for (void* p : {(void*)c->fbuf.p, (void*)c->sbuf.p, (void*)c->spos.p, (void*)c->lz.p, (void*)c->lpk.p, (void*)c->lres.p})
+        if (p) hipFree(p);
     for (auto& e : c->ev_s)
         if (e) hipEventDestroy(e);
     for (auto& e : c->ev_l)
@@ -530,23 +523,30 @@ static int wav_table(ntts_codec* c, const WavFmt& w, ntts_codec::WavTable* out) 
     return NTTS_OK;
 }
 
+// Room for `need` elements in a stage's buffer.  The first call that needs it (or a larger one) allocates max(need, whole), `whole` being what the
+// engine's whole waveform workspace can ask of this buffer; the stream is drained first: a kernel queued on it may still read the old one.
+template <typename T>
+static int grow(ntts_codec* c, ntts_codec::Grown<T>& b, size_t need, size_t whole, hipStream_t st) {
+    if (b.cap >= need) return NTTS_OK;
+    CHIP(c, hipStreamSynchronize(st));
+    if (b.p) { hipFree(b.p); b.p = nullptr; b.cap = 0; }
+    CHIP(c, hipMalloc((void**)&b.p, std::max(need, whole) * sizeof(T)));
+    b.cap = std::max(need, whole);
+    return NTTS_OK;
+}
+
 // in [n][in_stride] (utterance b: lens_dev[b] * len_mul samples; the rest of a row is scratch) -> c->fbuf [n][out_len_max] in the format's element type
 static int wav_format_launch(ntts_codec* c, const WavFmt& w, const float* in, long in_stride, const int* lens_dev, int len_mul, int n,
                              int64_t out_len_max, hipStream_t st) {
-    const size_t need = (size_t)n * out_len_max * w.esz;
-    if (c->fbuf_cap < need) {      // first use (or a wider format): room for the engine's whole waveform workspace in this format
-        const size_t whole = ((size_t)w.out_len((int64_t)c->wav_cap) + (size_t)c->max_rows) * w.esz;
-        CHIP(c, hipStreamSynchronize(st));
-        if (c->fbuf) { hipFree(c->fbuf); c->fbuf = nullptr; c->fbuf_cap = 0; }
-        CHIP(c, hipMalloc(&c->fbuf, std::max(need, whole)));
-        c->fbuf_cap = std::max(need, whole);
-    }
+    // (a wider format grows it: room for the engine's whole waveform workspace in this format)
+    int rc = grow(c, c->fbuf, (size_t)n * out_len_max * w.esz, ((size_t)w.out_len((int64_t)c->wav_cap) + (size_t)c->max_rows) * w.esz, st);
+    if (rc != NTTS_OK) return rc;
     WavFormatArgs a{};
-    a.in = in; a.in_stride = in_stride; a.lens = lens_dev; a.len_mul = len_mul; a.out = c->fbuf; a.out_stride = out_len_max; a.enc = w.enc;
+    a.in = in; a.in_stride = in_stride; a.lens = lens_dev; a.len_mul = len_mul; a.out = c->fbuf.p; a.out_stride = out_len_max; a.enc = w.enc;
     a.orig = 1; a.nw = 1;
     if (w.rate != 24000) {
         ntts_codec::WavTable tb;
-        const int rc = wav_table(c, w, &tb);
+        rc = wav_table(c, w, &tb);
         if (rc != NTTS_OK) return rc;
         a.coef = tb.coef; a.orig = tb.orig; a.nw = tb.nw; a.width = tb.width; a.taps = tb.taps;
     }
@@ -581,33 +581,21 @@ extern "C" int ntts_wav_stretch_len(int32_t speed_permille, int64_t n_in, int64_
 static int wav_stretch_launch(ntts_codec* c, const float* in, long in_stride, const int* lens_dev, int len_mul, const int* pm_dev, const int* nout_dev,
                               int n, int64_t n_out_max, hipStream_t st) {
     const int64_t k_max = stretch_frames(n_out_max);
-    const size_t need = (size_t)n * n_out_max, need_pos = (size_t)n * k_max;
-    if (c->sbuf_cap < need || c->spos_cap < need_pos || !c->sfade) {
+    if (!c->sfade) {                       // the stage's first launch on this engine: the fade table and the events
         CHIP(c, hipStreamSynchronize(st));
-        if (!c->sfade) {
-            std::vector<float> f(kStretchHop);
-            for (int i = 0; i < kStretchHop; ++i) f[i] = (float)(0.5 - 0.5 * cos(M_PI * (i + 0.5) / kStretchHop));
-            const int rc = dalloc(c, &c->sfade, f.size());
-            if (rc != NTTS_OK) return rc;
-            CHIP(c, hipMemcpy(c->sfade, f.data(), f.size() * sizeof(float), hipMemcpyHostToDevice));
-            for (auto& e : c->ev_s) CHIP(c, hipEventCreate(&e));
-        }
-        if (c->sbuf_cap < need) {
-            const size_t whole = 2 * c->wav_cap + (size_t)c->max_rows;
-            if (c->sbuf) { hipFree(c->sbuf); c->sbuf = nullptr; c->sbuf_cap = 0; }
-            CHIP(c, hipMalloc((void**)&c->sbuf, std::max(need, whole) * sizeof(float)));
-            c->sbuf_cap = std::max(need, whole);
-        }
-        if (c->spos_cap < need_pos) {
-            const size_t whole = 2 * c->wav_cap / kStretchHop + 2 * (size_t)c->max_rows;
-            if (c->spos) { hipFree(c->spos); c->spos = nullptr; c->spos_cap = 0; }
-            CHIP(c, hipMalloc((void**)&c->spos, std::max(need_pos, whole) * sizeof(int)));
-            c->spos_cap = std::max(need_pos, whole);
-        }
+        std::vector<float> f(kStretchHop);
+        for (int i = 0; i < kStretchHop; ++i) f[i] = (float)(0.5 - 0.5 * cos(M_PI * (i + 0.5) / kStretchHop));
+        const int rc = dalloc(c, &c->sfade, f.size());
+        if (rc != NTTS_OK) return rc;
+        CHIP(c, hipMemcpy(c->sfade, f.data(), f.size() * sizeof(float), hipMemcpyHostToDevice));
+        for (auto& e : c->ev_s) CHIP(c, hipEventCreate(&e));
     }
+    int rc = grow(c, c->sbuf, (size_t)n * n_out_max, 2 * c->wav_cap + (size_t)c->max_rows, st);
+    if (rc == NTTS_OK) rc = grow(c, c->spos, (size_t)n * k_max, 2 * c->wav_cap / kStretchHop + 2 * (size_t)c->max_rows, st);
+    if (rc != NTTS_OK) return rc;
     WavStretchArgs a{};
     a.in = in; a.in_stride = in_stride; a.lens = lens_dev; a.len_mul = len_mul; a.pm = pm_dev; a.n_out = nout_dev;
-    a.pos = c->spos; a.pos_stride = k_max; a.fade = c->sfade; a.out = c->sbuf; a.out_stride = n_out_max;
+    a.pos = c->spos.p; a.pos_stride = k_max; a.fade = c->sfade; a.out = c->sbuf.p; a.out_stride = n_out_max;
     CHIP(c, hipEventRecord(c->ev_s[0], st));
     NTTS_LAUNCH((wav_stretch_search_kernel), dim3(n), dim3(256), st, a);
     CHIP(c, hipEventRecord(c->ev_s[1], st));
@@ -653,40 +641,23 @@ static int wav_loud_launch(ntts_codec* c, float* io, long stride, const int* len
                            hipStream_t st) {
     const int64_t j_max = n_max / kLoudSub;
     const int64_t z_stride = std::max<int64_t>(j_max, 1), gy = std::max<int64_t>((j_max + kLoudLanes - 1) / kLoudLanes, 1);
-    const size_t need_z = (size_t)n * z_stride, need_pk = (size_t)n * gy, need_res = 3 * (size_t)n;
-    if (c->lz_cap < need_z || c->lpk_cap < need_pk || c->lres_cap < need_res) {
-        CHIP(c, hipStreamSynchronize(st));
-        if (!c->ev_l[0]) {
-            double b[3];
-            loud_biquad(1681.974450955533, 0.7071752369554196, pow(10.0, 3.999843853973347 / 20.0),
-                        pow(pow(10.0, 3.999843853973347 / 20.0), 0.4996667741545416), true, b, c->kw + 3);
-            c->kw[0] = b[0]; c->kw[1] = b[1]; c->kw[2] = b[2];
-            loud_biquad(38.13547087602444, 0.5003270373238773, 0.0, 0.0, false, nullptr, c->kw + 5);
-            for (auto& e : c->ev_l) CHIP(c, hipEventCreate(&e));
-        }
-        if (c->lz_cap < need_z) {              // room for the whole waveform workspace (as many sub-blocks as it holds, one per row at least)
-            const size_t whole = 2 * c->wav_cap / kLoudSub + (size_t)c->max_rows;
-            if (c->lz) { hipFree(c->lz); c->lz = nullptr; c->lz_cap = 0; }
-            CHIP(c, hipMalloc((void**)&c->lz, std::max(need_z, whole) * sizeof(double)));
-            c->lz_cap = std::max(need_z, whole);
-        }
-        if (c->lpk_cap < need_pk) {
-            const size_t whole = 2 * c->wav_cap / ((size_t)kLoudSub * kLoudLanes) + (size_t)c->max_rows;
-            if (c->lpk) { hipFree(c->lpk); c->lpk = nullptr; c->lpk_cap = 0; }
-            CHIP(c, hipMalloc((void**)&c->lpk, std::max(need_pk, whole) * sizeof(float)));
-            c->lpk_cap = std::max(need_pk, whole);
-        }
-        if (c->lres_cap < need_res) {
-            const size_t whole = 3 * (size_t)c->max_rows;
-            if (c->lres) { hipFree(c->lres); c->lres = nullptr; c->lres_cap = 0; }
-            CHIP(c, hipMalloc((void**)&c->lres, std::max(need_res, whole) * sizeof(double)));
-            c->lres_cap = std::max(need_res, whole);
-        }
+    if (!c->ev_l[0]) {                     // the stage's first launch on this engine: the K-weighting coefficients and the events
+        double b[3];
+        loud_biquad(1681.974450955533, 0.7071752369554196, pow(10.0, 3.999843853973347 / 20.0),
+                    pow(pow(10.0, 3.999843853973347 / 20.0), 0.4996667741545416), true, b, c->kw + 3);
+        c->kw[0] = b[0]; c->kw[1] = b[1]; c->kw[2] = b[2];
+        loud_biquad(38.13547087602444, 0.5003270373238773, 0.0, 0.0, false, nullptr, c->kw + 5);
+        for (auto& e : c->ev_l) CHIP(c, hipEventCreate(&e));
     }
+    // room for the whole waveform workspace: as many sub-blocks (and partial peaks of kLoudLanes of them) as it holds, one per row at least
+    int rc = grow(c, c->lz, (size_t)n * z_stride, 2 * c->wav_cap / kLoudSub + (size_t)c->max_rows, st);
+    if (rc == NTTS_OK) rc = grow(c, c->lpk, (size_t)n * gy, 2 * c->wav_cap / ((size_t)kLoudSub * kLoudLanes) + (size_t)c->max_rows, st);
+    if (rc == NTTS_OK) rc = grow(c, c->lres, 3 * (size_t)n, 3 * (size_t)c->max_rows, st);
+    if (rc != NTTS_OK) return rc;
     WavLoudArgs a{};
     a.io = io; a.stride = stride; a.lens = lens_dev; a.len_mul = len_mul; a.par = (const float*)par_dev;
     memcpy(a.kw, c->kw, sizeof a.kw);
-    a.z = c->lz; a.z_stride = (long)z_stride; a.pk = c->lpk; a.pk_stride = (int)gy; a.res = c->lres;
+    a.z = c->lz.p; a.z_stride = (long)z_stride; a.pk = c->lpk.p; a.pk_stride = (int)gy; a.res = c->lres.p;
     CHIP(c, hipEventRecord(c->ev_l[0], st));
     NTTS_LAUNCH((wav_loud_measure_kernel), dim3(n, (unsigned)gy), dim3(kLoudLanes), st, a);
     CHIP(c, hipEventRecord(c->ev_l[1], st));
@@ -698,31 +669,107 @@ static int wav_loud_launch(ntts_codec* c, float* io, long stride, const int* len
     return NTTS_OK;
 }
 
+// ---- the stages of one call behind overlap-add, in the order they run: time stretch, loudness, output format (DESIGN.md "Output path").
+// A stage that has nothing to do is off, and a call with every stage off launches nothing behind the waveform.
+struct WavPost {
+    WavFmt w;                                  // the checked format; its kernel runs unless it is the native one
+    const int32_t* speed = nullptr;            // per mille per row; null: every row at 1000
+    const ntts_wav_loudness* loud = nullptr;   // per row; null: no row has the option on
+    bool measure = false;                      // the loudness kernels without a parameter block: the figures alone, nothing scaled
+    bool loud_on() const { return loud || measure; }
+    bool idle() const { return !speed && !loud_on() && w.plain(); }
+    WavPost from_row(int i0) const {           // the same stages for the rows i0.. of the call
+        WavPost q = *this;
+        if (speed) q.speed += i0;
+        if (loud) q.loud += i0;
+        return q;
+    }
+};
+// The caller's (fmt, speed_permille, loudness) of n rows in two steps, because a decode call's own argument checks stand between the format's check
+// and the stages': wav_post_format starts the description from the checked format, wav_post_stages checks speeds and loudness and switches each
+// on only where something is asked of it.  The only place where a stage is switched off.
+static int wav_post_format(ntts_codec* c, const ntts_wav_format* fmt, WavPost* p) {
+    *p = WavPost{};
+    return wav_fmt_check(c, fmt, &p->w);
+}
+static int wav_post_stages(ntts_codec* c, const int32_t* speed, const ntts_wav_loudness* loud, int n, WavPost* p) {
+    int rc = NTTS_OK;
+    bool any = false;
+    if (speed) rc = stretch_check(c, speed, n, &any);
+    if (rc == NTTS_OK && any) p->speed = speed;
+    any = false;
+    if (rc == NTTS_OK && loud) rc = loud_check(c, loud, n, &any);
+    if (rc == NTTS_OK && any) p->loud = loud;
+    return rc;
+}
+
+// The meta tail of n rows of lens[i] * mul samples: [speed n][stretched samples n] with a speed, then [enable, target, peak, max gain] x n as floats
+// with a loudness.  Returns its ints and, where asked, writes it (tail), every row's samples in the output format (out_lens) and the longest row
+// behind the stretch at 24 kHz (s_max).
+static size_t wav_post_tail(const WavPost& p, int n, const int32_t* lens, int mul, int* tail, int32_t* out_lens, int64_t* s_max) {
+    int64_t longest = 0;
+    for (int i = 0; i < n; ++i) {
+        const int64_t s = p.speed ? stretch_len((int64_t)mul * lens[i], p.speed[i]) : (int64_t)mul * lens[i];
+        longest = std::max(longest, s);
+        if (out_lens) out_lens[i] = (int32_t)p.w.out_len(s);
+        if (tail && p.speed) { tail[i] = p.speed[i]; tail[n + i] = (int)s; }
+    }
+    if (s_max) *s_max = longest;
+    const size_t ld_off = p.speed ? 2 * (size_t)n : 0;
+    if (tail && p.loud) loud_pack(tail + ld_off, p.loud, n);
+    return ld_off + (p.loud ? 4 * (size_t)n : 0);
+}
+
+// what a call hands over: [n][stride] elements of esz bytes at src
+struct WavOut { const void* src; long stride; size_t esz; };
+// The chain on n rows on the device -- in [n][stride], row b of lens_dev[b] * len_mul samples, s_max the longest behind the stretch -- with the
+// call's meta tail at tail_dev (wav_post_tail).  A stretch moves the rows to c->sbuf, the loudness scales them where they stand (`in` and c->sbuf
+// are this call's own), a format moves them to c->fbuf.
+static int wav_post_launch(ntts_codec* c, const WavPost& p, float* in, long stride, const int* lens_dev, int len_mul, int n, int64_t s_max,
+                           const int* tail_dev, hipStream_t st, WavOut* o) {
+    if (p.speed) {
+        const int rc = wav_stretch_launch(c, in, stride, lens_dev, len_mul, tail_dev, tail_dev + n, n, s_max, st);
+        if (rc != NTTS_OK) return rc;
+        in = c->sbuf.p; stride = (long)s_max; lens_dev = tail_dev + n; len_mul = 1;
+        tail_dev += 2 * (size_t)n;
+    }
+    if (p.loud_on()) {
+        const int rc = wav_loud_launch(c, in, stride, lens_dev, len_mul, p.loud ? tail_dev : nullptr, n, s_max, st);
+        if (rc != NTTS_OK) return rc;
+    }
+    *o = WavOut{in, stride, sizeof(float)};
+    if (!p.w.plain()) {
+        const int64_t row_len = p.w.out_len(s_max);
+        const int rc = wav_format_launch(c, p.w, in, stride, lens_dev, len_mul, n, row_len, st);
+        if (rc != NTTS_OK) return rc;
+        *o = WavOut{c->fbuf.p, (long)row_len, p.w.esz};
+    }
+    return NTTS_OK;
+}
+
+// One meta block through the page-locked ring: pack(slot) fills the next slot and returns its ints, the copy to c->meta is asynchronous (the slot is
+// free again once the copy out of it, two blocks ago, has completed: no stream-wide wait)
+template <typename Pack>
+static int meta_send(ntts_codec* c, hipStream_t st, Pack pack) {
+    const int k = c->meta_next;
+    c->meta_next = (k + 1) % ntts_codec::kMetaStages;
+    if (c->meta_used[k]) CHIP(c, hipEventSynchronize(c->meta_ev[k]));
+    const size_t n_ints = pack(c->meta_host[k]);
+    CHIP(c, hipMemcpyAsync(c->meta, c->meta_host[k], n_ints * sizeof(int), hipMemcpyHostToDevice, st));
+    c->meta_used[k] = true;
+    CHIP(c, hipEventRecord(c->meta_ev[k], st));
+    return NTTS_OK;
+}
+
 // codes: HOST packed codes (codes_dev == null), or DEVICE codes, utterance i at codes_dev + i * codes_stride (already in range:
 // they come from ntts_backbone_export_codes).  out_kind: 0 = host destination, blocking (the classic entry point);
 // 1 = host destination (pinned), asynchronous; 2 = device destination, asynchronous.  producer: a HIP stream whose work so far
-// must complete before the codes are read (the backbone's stream), or null.  wf: the output format (null = the native 24 kHz float32: the
-// waveform buffer is the copy's source and nothing more is launched); wav_stride counts elements of that format, out_lens (may be null)
-// receives every utterance's samples.
+// must complete before the codes are read (the backbone's stream), or null.  post: the stages behind overlap-add (with none of them on the
+// waveform buffer is the copy's source and nothing more is launched); wav_stride counts elements of its format, out_lens (may be null)
+// receives every utterance's samples.  The arguments are codec_decode's: checked there.
 static int codec_decode_impl(ntts_codec* c, int32_t n, const int32_t* codes, const int32_t* codes_dev, int32_t codes_stride,
                              const int32_t* lens, void* wav_out, int64_t wav_stride, int out_kind, hipStream_t producer,
-                             const WavFmt* wf = nullptr, int32_t* out_lens = nullptr, const int32_t* speed = nullptr,
-                             const ntts_wav_loudness* loud = nullptr) {
-    if (!c || n < 1 || (!codes && !codes_dev) || !lens || !wav_out) return cfail(c, NTTS_EINVAL, "null/empty argument");
-    if (!c->finalized) return cfail(c, NTTS_ESTATE, "weights not finalised");
-    if (wf && wf->plain()) wf = nullptr;
-    if (speed) {                           // speed_permille: all 1000 (or null) is the pass without the stage, call for call
-        bool any;
-        const int rc = stretch_check(c, speed, n, &any);
-        if (rc != NTTS_OK) return rc;
-        if (!any) speed = nullptr;
-    }
-    if (loud) {                            // loudness: no row with the option on (or null) is the pass without the stage, call for call
-        bool any;
-        const int rc = loud_check(c, loud, n, &any);
-        if (rc != NTTS_OK) return rc;
-        if (!any) loud = nullptr;
-    }
+                             const WavPost& post, int32_t* out_lens) {
     CHIP(c, hipSetDevice(c->device));
     const int H = c->H, hop = c->cfg.hop_length;
     int Tmax = 0;
@@ -740,19 +787,11 @@ static int codec_decode_impl(ntts_codec* c, int32_t n, const int32_t* codes, con
     if (codes_dev && codes_stride < Tmax) return cfail(c, NTTS_EINVAL, "codes_stride %d < longest utterance %d", codes_stride, Tmax);
     // samples per row of the hand-over (the longest utterance's, in the output format) and bytes per sample
     // (with a speed: of the longest STRETCHED utterance)
-    int64_t s_max = (int64_t)hop * Tmax;
-    if (speed) {
-        s_max = 0;
-        for (int i = 0; i < n; ++i) s_max = std::max(s_max, stretch_len((int64_t)hop * lens[i], speed[i]));
-    }
-    const int64_t row_len = wf ? wf->out_len(s_max) : s_max;
-    const size_t esz = wf ? wf->esz : sizeof(float);
+    int64_t s_max;
+    const size_t tail_ints = wav_post_tail(post, n, lens, hop, nullptr, nullptr, &s_max);
+    const int64_t row_len = post.w.out_len(s_max);
     if (wav_stride < row_len) return cfail(c, NTTS_EINVAL, "wav_stride %ld < %ld samples", (long)wav_stride, (long)row_len);
-    if (out_lens)
-        for (int i = 0; i < n; ++i) {
-            const int64_t s_i = speed ? stretch_len((int64_t)hop * lens[i], speed[i]) : (int64_t)hop * lens[i];
-            out_lens[i] = (int32_t)(wf ? wf->out_len(s_i) : s_i);
-        }
+    if (out_lens) wav_post_tail(post, n, lens, hop, nullptr, out_lens, nullptr);
     const int Tp = Tmax + 2 * kPadRows;
     const long rows = total + 2L * kPadRows * n;          // packed: every utterance brings its own frames + pad rows (codec.h)
     if (rows > c->max_rows) return cfail(c, NTTS_EINVAL, "%ld rows exceed max_rows %ld: decode fewer utterances per call", rows, c->max_rows);
@@ -763,32 +802,23 @@ static int codec_decode_impl(ntts_codec* c, int32_t n, const int32_t* codes, con
     if (!(c->attn_resident && npages <= kAttnResPages) && (long)n * npages * kPage > c->max_rows + (c->max_rows / (1 + 2 * kPadRows) + 1) * kPage)
         return cfail(c, NTTS_EINVAL, "%d utterances x %d pages exceed the V^T workspace: decode fewer utterances per call", n, npages);
     // ---- meta: [lens n][code_off n][row_off n + 1][codes total], built in a page-locked ring slot: the copy is asynchronous, no stream-wide wait
-    // (with a speed: [speed n][stretched samples n] behind them; with a loudness: [enable, target, peak, max gain] x n as floats behind those)
-    const size_t sp_off = 3 * (size_t)n + 1 + (codes ? (size_t)total : 0), ld_off = sp_off + (speed ? 2 * (size_t)n : 0);
-    const size_t m_size = ld_off + (loud ? 4 * (size_t)n : 0);
-    if (m_size > c->meta_cap) return cfail(c, NTTS_EINVAL, "meta block too large");
+    // and the stages' tail (wav_post_tail) behind them
+    const size_t tail_off = 3 * (size_t)n + 1 + (codes ? (size_t)total : 0);
+    if (tail_off + tail_ints > c->meta_cap) return cfail(c, NTTS_EINVAL, "meta block too large");
     hipStream_t st = c->stream;
     {
-        const int k = c->meta_next;
-        c->meta_next = (k + 1) % ntts_codec::kMetaStages;
-        if (c->meta_used[k]) CHIP(c, hipEventSynchronize(c->meta_ev[k]));     // (the copy out of this slot two passes ago)
-        int* m = c->meta_host[k];
-        size_t at = 0;
-        memcpy(m, lens, (size_t)n * sizeof(int)); at = n;
-        long off = 0;
-        for (int i = 0; i < n; ++i) { m[at++] = codes ? (int)off : i * codes_stride; off += lens[i]; }
-        long roff = 0;
-        for (int i = 0; i < n; ++i) { m[at++] = (int)roff; roff += lens[i] + 2 * kPadRows; }
-        m[at++] = (int)roff;
-        if (codes) { memcpy(m + at, codes, (size_t)total * sizeof(int)); at += total; }
-        if (speed) {
-            memcpy(m + at, speed, (size_t)n * sizeof(int)); at += n;
-            for (int i = 0; i < n; ++i) m[at++] = (int)stretch_len((int64_t)hop * lens[i], speed[i]);
-        }
-        if (loud) { loud_pack(m + at, loud, n); at += 4 * (size_t)n; }
-        CHIP(c, hipMemcpyAsync(c->meta, m, at * sizeof(int), hipMemcpyHostToDevice, st));
-        c->meta_used[k] = true;
-        CHIP(c, hipEventRecord(c->meta_ev[k], st));
+        const int rc = meta_send(c, st, [&](int* m) {
+            size_t at = 0;
+            memcpy(m, lens, (size_t)n * sizeof(int)); at = n;
+            long off = 0;
+            for (int i = 0; i < n; ++i) { m[at++] = codes ? (int)off : i * codes_stride; off += lens[i]; }
+            long roff = 0;
+            for (int i = 0; i < n; ++i) { m[at++] = (int)roff; roff += lens[i] + 2 * kPadRows; }
+            m[at++] = (int)roff;
+            if (codes) { memcpy(m + at, codes, (size_t)total * sizeof(int)); at += total; }
+            return at + wav_post_tail(post, n, lens, hop, m + at, nullptr, nullptr);
+        });
+        if (rc != NTTS_OK) return rc;
     }
     if (producer) {                        // the codes are being written on another stream: order this pass behind it
         CHIP(c, hipEventRecord(c->ev_in, producer));
@@ -866,237 +896,186 @@ static int codec_decode_impl(ntts_codec* c, int32_t n, const int32_t* codes, con
     oa.frames = c->frames; oa.win2 = c->win2; oa.wav = c->wav; oa.wav_stride = (long)hop * Tmax; oa.R = R; oa.hop = hop; oa.n_fft = c->n_fft;
     oa.scale = c->fmt == kOpF16 ? 1.0f / kDftScale : 1.0f;
     NTTS_LAUNCH((ola_kernel), dim3(n, (unsigned)(((long)hop * Tmax + 255) / 256)), dim3(256), st, oa);
-    const void* src = c->wav;
-    const float* fin = c->wav;             // what the output stage reads: [n][fin_stride], utterance b of fin_lens[b] * fin_mul samples
-    long fin_stride = (long)hop * Tmax;
-    const int* fin_lens = R.lens;
-    int fin_mul = hop;
-    if (speed) {                           // the time stretch: the stretched buffer becomes the copy's source, or the output stage's input
-        const int* sp = c->meta + sp_off;
-        const int rc = wav_stretch_launch(c, c->wav, (long)hop * Tmax, R.lens, hop, sp, sp + n, n, s_max, st);
+    WavOut o;
+    {
+        const int rc = wav_post_launch(c, post, c->wav, (long)hop * Tmax, R.lens, hop, n, s_max, c->meta + tail_off, st, &o);
         if (rc != NTTS_OK) return rc;
-        src = fin = c->sbuf; fin_stride = (long)s_max; fin_lens = sp + n; fin_mul = 1;
-    }
-    if (loud) {                            // the loudness: every row scaled where it stands (c->wav / c->sbuf are this pass's own, nobody reads them later)
-        const int rc = wav_loud_launch(c, const_cast<float*>(fin), fin_stride, fin_lens, fin_mul, c->meta + ld_off, n, s_max, st);
-        if (rc != NTTS_OK) return rc;
-    }
-    if (wf) {                              // the output stage: the formatted buffer becomes the copy's source
-        const int rc = wav_format_launch(c, *wf, fin, fin_stride, fin_lens, fin_mul, n, row_len, st);
-        if (rc != NTTS_OK) return rc;
-        src = c->fbuf;
     }
     CHIP(c, hipEventRecord(c->ev[1], st));
     c->have_time = true;
     const hipMemcpyKind kind = out_kind == 2 ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    const size_t row_bytes = (size_t)row_len * esz;
+    const void* src = o.src;
+    const size_t esz = o.esz, row_bytes = (size_t)row_len * esz, src_pitch = (size_t)o.stride * esz;
+    const bool dense = wav_stride == row_len && o.stride == row_len;      // source and destination rows back to back: one linear copy
     if (out_kind == 0) {
         CHIP(c, hipStreamSynchronize(st));
         CHIP(c, hipGetLastError());
         // one strided device-to-host copy for the whole batch (rows shorter than Tmax carry don't-care tails)
-        if (wav_stride == row_len)   // dense destination: one linear copy (DMA engine at PCIe speed into pinned memory)
+        if (dense)                   // (DMA engine at PCIe speed into pinned memory)
             CHIP(c, hipMemcpy(wav_out, src, (size_t)n * row_bytes, kind));
         else
-            CHIP(c, hipMemcpy2D(wav_out, (size_t)wav_stride * esz, src, row_bytes, row_bytes, n, kind));
+            CHIP(c, hipMemcpy2D(wav_out, (size_t)wav_stride * esz, src, src_pitch, row_bytes, n, kind));
         return NTTS_OK;
     }
     // asynchronous hand-over, stream-ordered behind the pass (ntts_codec_sync waits for it)
-    if (wav_stride == row_len)
+    if (dense)
         CHIP(c, hipMemcpyAsync(wav_out, src, (size_t)n * row_bytes, kind, st));
     else
-        CHIP(c, hipMemcpy2DAsync(wav_out, (size_t)wav_stride * esz, src, row_bytes, row_bytes, n, kind, st));
+        CHIP(c, hipMemcpy2DAsync(wav_out, (size_t)wav_stride * esz, src, src_pitch, row_bytes, n, kind, st));
     if (c->ev_done && hipEventRecord(c->ev_done, st) == hipSuccess) c->have_done = true;
     else { (void)hipGetLastError(); c->have_done = false; }
     return NTTS_OK;
 }
 
+// Every decode entry point.  codes: on the host (out_kind 0) or on the device.  classic: ntts_codec_decode / _dev, which hand out no lengths and
+// report a null engine through the global error string; the others return NTTS_EINVAL for it.  A null format, speed or loudness is that stage off.
+static int codec_decode(ntts_codec* c, bool classic, int32_t n, const int32_t* codes, int32_t codes_stride, const int32_t* lens,
+                        const int32_t* speed_permille, const ntts_wav_loudness* loudness, const ntts_wav_format* fmt, void* out, int64_t out_stride,
+                        int out_kind, void* producer_stream, int32_t* out_lens) {
+    if (!c && !classic) return NTTS_EINVAL;
+    if (!codes || (!out_lens && !classic)) return cfail(c, NTTS_EINVAL, "null/empty argument");
+    WavPost post;
+    int rc = wav_post_format(c, fmt, &post);
+    if (rc != NTTS_OK) return rc;
+    if (!c || n < 1 || !lens || !out) return cfail(c, NTTS_EINVAL, "null/empty argument");
+    if (!c->finalized) return cfail(c, NTTS_ESTATE, "weights not finalised");
+    rc = wav_post_stages(c, speed_permille, loudness, n, &post);
+    if (rc != NTTS_OK) return rc;
+    return codec_decode_impl(c, n, out_kind ? nullptr : codes, out_kind ? codes : nullptr, codes_stride, lens, out, out_stride, out_kind,
+                             (hipStream_t)producer_stream, post, out_lens);
+}
+
 extern "C" int ntts_codec_decode(ntts_codec* c, int32_t n, const int32_t* codes, const int32_t* lens, float* wav_out,
                                  int64_t wav_stride) {
-    if (!codes) return cfail(c, NTTS_EINVAL, "null/empty argument");
-    return codec_decode_impl(c, n, codes, nullptr, 0, lens, wav_out, wav_stride, 0, nullptr);
+    return codec_decode(c, true, n, codes, 0, lens, nullptr, nullptr, nullptr, wav_out, wav_stride, 0, nullptr, nullptr);
 }
-
 extern "C" int ntts_codec_decode_dev(ntts_codec* c, int32_t n, const int32_t* codes_dev, int32_t codes_stride, const int32_t* lens,
                                      float* wav_out, int64_t wav_stride, int32_t wav_on_device, void* producer_stream) {
-    if (!codes_dev) return cfail(c, NTTS_EINVAL, "null/empty argument");
-    return codec_decode_impl(c, n, nullptr, codes_dev, codes_stride, lens, wav_out, wav_stride, wav_on_device ? 2 : 1, (hipStream_t)producer_stream);
+    return codec_decode(c, true, n, codes_dev, codes_stride, lens, nullptr, nullptr, nullptr, wav_out, wav_stride, wav_on_device ? 2 : 1, producer_stream, nullptr);
 }
-
 // The same two passes with the output stage behind overlap-add (ntts_wav_format); a zeroed or null format is the plain pass, bit for bit.
 extern "C" int ntts_codec_decode_fmt(ntts_codec* c, int32_t n, const int32_t* codes, const int32_t* lens, const ntts_wav_format* fmt,
                                      void* out, int64_t out_stride, int32_t* out_lens) {
-    if (!c) return NTTS_EINVAL;
-    if (!codes || !out_lens) return cfail(c, NTTS_EINVAL, "null/empty argument");
-    WavFmt w;
-    const int rc = wav_fmt_check(c, fmt, &w);
-    if (rc != NTTS_OK) return rc;
-    return codec_decode_impl(c, n, codes, nullptr, 0, lens, out, out_stride, 0, nullptr, &w, out_lens);
+    return codec_decode(c, false, n, codes, 0, lens, nullptr, nullptr, fmt, out, out_stride, 0, nullptr, out_lens);
 }
-
 extern "C" int ntts_codec_decode_dev_fmt(ntts_codec* c, int32_t n, const int32_t* codes_dev, int32_t codes_stride, const int32_t* lens,
                                          void* out, int64_t out_stride, int32_t out_on_device, void* producer_stream,
                                          const ntts_wav_format* fmt, int32_t* out_lens) {
-    if (!c) return NTTS_EINVAL;
-    if (!codes_dev || !out_lens) return cfail(c, NTTS_EINVAL, "null/empty argument");
-    WavFmt w;
-    const int rc = wav_fmt_check(c, fmt, &w);
-    if (rc != NTTS_OK) return rc;
-    return codec_decode_impl(c, n, nullptr, codes_dev, codes_stride, lens, out, out_stride, out_on_device ? 2 : 1, (hipStream_t)producer_stream, &w, out_lens);
+    return codec_decode(c, false, n, codes_dev, codes_stride, lens, nullptr, nullptr, fmt, out, out_stride, out_on_device ? 2 : 1, producer_stream, out_lens);
+}
+// ... with a speed per utterance (per mille; null = all 1000: the very same calls)
+extern "C" int ntts_codec_decode_speed(ntts_codec* c, int32_t n, const int32_t* codes, const int32_t* lens, const int32_t* speed_permille,
+                                       const ntts_wav_format* fmt, void* out, int64_t out_stride, int32_t* out_lens) {
+    return codec_decode(c, false, n, codes, 0, lens, speed_permille, nullptr, fmt, out, out_stride, 0, nullptr, out_lens);
+}
+extern "C" int ntts_codec_decode_dev_speed(ntts_codec* c, int32_t n, const int32_t* codes_dev, int32_t codes_stride, const int32_t* lens,
+                                           const int32_t* speed_permille, void* out, int64_t out_stride, int32_t out_on_device,
+                                           void* producer_stream, const ntts_wav_format* fmt, int32_t* out_lens) {
+    return codec_decode(c, false, n, codes_dev, codes_stride, lens, speed_permille, nullptr, fmt, out, out_stride, out_on_device ? 2 : 1, producer_stream, out_lens);
+}
+// ... and with a loudness per utterance (null, or every enable 0: the very same calls)
+extern "C" int ntts_codec_decode_loud(ntts_codec* c, int32_t n, const int32_t* codes, const int32_t* lens, const int32_t* speed_permille,
+                                      const ntts_wav_loudness* loudness, const ntts_wav_format* fmt, void* out, int64_t out_stride,
+                                      int32_t* out_lens) {
+    return codec_decode(c, false, n, codes, 0, lens, speed_permille, loudness, fmt, out, out_stride, 0, nullptr, out_lens);
+}
+extern "C" int ntts_codec_decode_dev_loud(ntts_codec* c, int32_t n, const int32_t* codes_dev, int32_t codes_stride, const int32_t* lens,
+                                          const int32_t* speed_permille, const ntts_wav_loudness* loudness, void* out, int64_t out_stride,
+                                          int32_t out_on_device, void* producer_stream, const ntts_wav_format* fmt, int32_t* out_lens) {
+    return codec_decode(c, false, n, codes_dev, codes_stride, lens, speed_permille, loudness, fmt, out, out_stride, out_on_device ? 2 : 1, producer_stream, out_lens);
 }
 
-// The output stage alone on the caller's 24 kHz float32 waveforms (a watermarker, a host library, sits between the codec and the output):
-// H2D into the engine's waveform workspace, the kernel, D2H, as many rows per round as the workspace holds.  Blocking.
-extern "C" int ntts_codec_convert(ntts_codec* c, int32_t n, const float* wav, int64_t in_stride, const int32_t* n_samples,
-                                  const ntts_wav_format* fmt, void* out, int64_t out_stride, int32_t* out_lens) {
-    if (!c) return NTTS_EINVAL;
-    if (n < 1 || !wav || !n_samples || !out || !out_lens || in_stride < 0) return cfail(c, NTTS_EINVAL, "null/empty argument");
-    WavFmt w;
-    int rc = wav_fmt_check(c, fmt, &w);
-    if (rc != NTTS_OK) return rc;
+// The chain alone on the caller's 24 kHz float32 waveforms -- HOST [n][in_stride], row i of n_samples[i] -- in rounds of as many rows as the
+// waveform workspace and the meta block hold: H2D, the stages, D2H.  Blocking.  out [n][out_stride] elements of the format and out_lens (both null:
+// nothing is handed out), positions [n][pos_stride] (may be null; row i receives its own K_i, nothing behind them), measured [n][3] doubles (may be
+// null; needs the loudness kernels on).
+static int wav_rounds(ntts_codec* c, int32_t n, const float* wav, int64_t in_stride, const int32_t* n_samples, const WavPost& post, void* out,
+                      int64_t out_stride, int32_t* out_lens, int32_t* positions, int64_t pos_stride, double* measured) {
     const int64_t cap = (int64_t)c->cfg.max_frames * c->cfg.hop_length;
-    int64_t Lmax = 0;
+    int64_t Lmax = 0, s_max;
     for (int i = 0; i < n; ++i) {
         if (n_samples[i] < 0 || n_samples[i] > in_stride)
             return cfail(c, NTTS_EINVAL, "utterance %d: n_samples %d outside [0, in_stride %ld]", i, n_samples[i], (long)in_stride);
         if (n_samples[i] > cap) return cfail(c, NTTS_EINVAL, "utterance %d: %d samples exceed the engine's %ld (max_frames x hop)", i, n_samples[i], (long)cap);
         Lmax = std::max<int64_t>(Lmax, n_samples[i]);
     }
-    const int64_t row_len = w.out_len(Lmax);
-    if (out_stride < row_len) return cfail(c, NTTS_EINVAL, "out_stride %ld < %ld samples", (long)out_stride, (long)row_len);
-    for (int i = 0; i < n; ++i) out_lens[i] = (int32_t)w.out_len(n_samples[i]);
-    if (Lmax == 0) return NTTS_OK;
-    if (w.plain()) {                       // the native format: nothing to compute, nothing is launched
-        for (int i = 0; i < n; ++i) memcpy((float*)out + (size_t)i * out_stride, wav + (size_t)i * in_stride, (size_t)n_samples[i] * sizeof(float));
+    wav_post_tail(post, n, n_samples, 1, nullptr, nullptr, &s_max);
+    const int64_t row_len = post.w.out_len(s_max), k_max = stretch_frames(s_max);
+    if (out && out_stride < row_len) return cfail(c, NTTS_EINVAL, "out_stride %ld < %ld samples", (long)out_stride, (long)row_len);
+    if (positions && pos_stride < k_max) return cfail(c, NTTS_EINVAL, "pos_stride %ld < %ld frames", (long)pos_stride, (long)k_max);
+    if (out_lens) wav_post_tail(post, n, n_samples, 1, nullptr, out_lens, nullptr);
+    if (Lmax == 0) {                       // nothing but empty rows: unmeasurable, nothing to launch
+        if (measured)
+            for (int i = 0; i < n; ++i) { measured[3 * i] = NAN; measured[3 * i + 1] = 0.0; measured[3 * i + 2] = 1.0; }
         return NTTS_OK;
     }
+    if (post.idle())                       // every stage off: nothing to compute, nothing is launched
+        for (int i = 0; i < n; ++i) memcpy((float*)out + (size_t)i * out_stride, wav + (size_t)i * in_stride, (size_t)n_samples[i] * sizeof(float));
+    if (positions && !post.speed)          // unit speed: frame k was taken from k * hop, by definition
+        for (int i = 0; i < n; ++i)
+            for (int64_t k = 0; k < stretch_frames(n_samples[i]); ++k) positions[(size_t)i * pos_stride + k] = (int32_t)(k * kStretchHop);
+    if (post.idle()) return NTTS_OK;
     CHIP(c, hipSetDevice(c->device));
     hipStream_t st = c->stream;
-    const size_t row_bytes = (size_t)row_len * w.esz;
-    const int per_round = (int)std::min<int64_t>(std::min<int64_t>((int64_t)c->wav_cap / Lmax, c->max_rows), (int64_t)c->meta_cap);
+    const int per_round = (int)std::min<int64_t>(std::min<int64_t>((int64_t)c->wav_cap / Lmax, c->max_rows),
+                                                 (int64_t)c->meta_cap / (1 + (post.speed ? 2 : 0) + (post.loud_on() ? 4 : 0)));
+    std::vector<int32_t> pos_host;
     for (int i0 = 0; i0 < n; i0 += per_round) {
         const int nb = std::min(per_round, n - i0);
-        const int k = c->meta_next;            // the lengths go through the page-locked meta ring, as a decode pass's do
-        c->meta_next = (k + 1) % ntts_codec::kMetaStages;
-        if (c->meta_used[k]) CHIP(c, hipEventSynchronize(c->meta_ev[k]));
-        memcpy(c->meta_host[k], n_samples + i0, (size_t)nb * sizeof(int));
-        CHIP(c, hipMemcpyAsync(c->meta, c->meta_host[k], (size_t)nb * sizeof(int), hipMemcpyHostToDevice, st));
-        c->meta_used[k] = true;
-        CHIP(c, hipEventRecord(c->meta_ev[k], st));
+        const WavPost rows = post.from_row(i0);
+        int rc = meta_send(c, st, [&](int* m) {           // [samples nb], then the stages' tail
+            memcpy(m, n_samples + i0, (size_t)nb * sizeof(int));
+            return nb + wav_post_tail(rows, nb, n_samples + i0, 1, m + nb, nullptr, nullptr);
+        });
+        if (rc != NTTS_OK) return rc;
         CHIP(c, hipMemcpy2DAsync(c->wav, (size_t)Lmax * sizeof(float), wav + (size_t)i0 * in_stride, (size_t)in_stride * sizeof(float),
                                  (size_t)Lmax * sizeof(float), nb, hipMemcpyHostToDevice, st));
         CHIP(c, hipEventRecord(c->ev[0], st));
-        rc = wav_format_launch(c, w, c->wav, (long)Lmax, c->meta, 1, nb, row_len, st);
+        WavOut o;
+        rc = wav_post_launch(c, rows, c->wav, (long)Lmax, c->meta, 1, nb, s_max, c->meta + nb, st, &o);
         if (rc != NTTS_OK) return rc;
         CHIP(c, hipEventRecord(c->ev[1], st));
         c->have_time = true;
-        CHIP(c, hipMemcpy2DAsync((char*)out + (size_t)i0 * out_stride * w.esz, (size_t)out_stride * w.esz, c->fbuf, row_bytes, row_bytes, nb,
-                                 hipMemcpyDeviceToHost, st));
+        if (out)
+            CHIP(c, hipMemcpy2DAsync((char*)out + (size_t)i0 * out_stride * o.esz, (size_t)out_stride * o.esz, o.src, (size_t)o.stride * o.esz,
+                                     (size_t)row_len * o.esz, nb, hipMemcpyDeviceToHost, st));
+        if (positions && post.speed) {
+            pos_host.resize((size_t)nb * k_max);
+            CHIP(c, hipMemcpyAsync(pos_host.data(), c->spos.p, pos_host.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        }
+        if (measured) CHIP(c, hipMemcpyAsync(measured + 3 * (size_t)i0, c->lres.p, 3 * (size_t)nb * sizeof(double), hipMemcpyDeviceToHost, st));
         CHIP(c, hipStreamSynchronize(st));
         CHIP(c, hipGetLastError());
+        if (positions && post.speed)
+            for (int i = 0; i < nb; ++i)
+                memcpy(positions + (size_t)(i0 + i) * pos_stride, pos_host.data() + (size_t)i * k_max,
+                       (size_t)stretch_frames(stretch_len(n_samples[i0 + i], rows.speed[i])) * sizeof(int32_t));
     }
     return NTTS_OK;
 }
 
-// ntts_codec_decode_fmt / ntts_codec_decode_dev_fmt with a speed per utterance (per mille; null = all 1000: the very same calls)
-extern "C" int ntts_codec_decode_speed(ntts_codec* c, int32_t n, const int32_t* codes, const int32_t* lens, const int32_t* speed_permille,
-                                       const ntts_wav_format* fmt, void* out, int64_t out_stride, int32_t* out_lens) {
+// The output stage alone on the caller's 24 kHz float32 waveforms (a watermarker, a host library, sits between the codec and the output).
+extern "C" int ntts_codec_convert(ntts_codec* c, int32_t n, const float* wav, int64_t in_stride, const int32_t* n_samples,
+                                  const ntts_wav_format* fmt, void* out, int64_t out_stride, int32_t* out_lens) {
     if (!c) return NTTS_EINVAL;
-    if (!codes || !out_lens) return cfail(c, NTTS_EINVAL, "null/empty argument");
-    WavFmt w;
-    const int rc = wav_fmt_check(c, fmt, &w);
+    if (n < 1 || !wav || !n_samples || !out || !out_lens || in_stride < 0) return cfail(c, NTTS_EINVAL, "null/empty argument");
+    WavPost post;
+    const int rc = wav_post_format(c, fmt, &post);
     if (rc != NTTS_OK) return rc;
-    return codec_decode_impl(c, n, codes, nullptr, 0, lens, out, out_stride, 0, nullptr, &w, out_lens, speed_permille);
+    return wav_rounds(c, n, wav, in_stride, n_samples, post, out, out_stride, out_lens, nullptr, 0, nullptr);
 }
 
-extern "C" int ntts_codec_decode_dev_speed(ntts_codec* c, int32_t n, const int32_t* codes_dev, int32_t codes_stride, const int32_t* lens,
-                                           const int32_t* speed_permille, void* out, int64_t out_stride, int32_t out_on_device,
-                                           void* producer_stream, const ntts_wav_format* fmt, int32_t* out_lens) {
-    if (!c) return NTTS_EINVAL;
-    if (!codes_dev || !out_lens) return cfail(c, NTTS_EINVAL, "null/empty argument");
-    WavFmt w;
-    const int rc = wav_fmt_check(c, fmt, &w);
-    if (rc != NTTS_OK) return rc;
-    return codec_decode_impl(c, n, nullptr, codes_dev, codes_stride, lens, out, out_stride, out_on_device ? 2 : 1, (hipStream_t)producer_stream, &w,
-                             out_lens, speed_permille);
-}
-
-// The time stretch (and the output stage behind it) alone on the caller's 24 kHz float32 waveforms: ntts_codec_convert's twin, the same rounds.  Blocking.
+// The time stretch (and the output stage behind it) alone on the caller's 24 kHz float32 waveforms: ntts_codec_convert's twin.  Blocking.
 extern "C" int ntts_codec_stretch(ntts_codec* c, int32_t n, const float* wav, int64_t in_stride, const int32_t* n_samples,
                                   const int32_t* speed_permille, const ntts_wav_format* fmt, void* out, int64_t out_stride, int32_t* out_lens,
                                   int32_t* positions, int64_t pos_stride) {
     if (!c) return NTTS_EINVAL;
     if (n < 1 || !wav || !n_samples || !speed_permille || !out || !out_lens || in_stride < 0) return cfail(c, NTTS_EINVAL, "null/empty argument");
-    WavFmt w;
-    int rc = wav_fmt_check(c, fmt, &w);
+    WavPost post;
+    int rc = wav_post_format(c, fmt, &post);
+    if (rc == NTTS_OK) rc = wav_post_stages(c, speed_permille, nullptr, n, &post);
     if (rc != NTTS_OK) return rc;
-    bool any;
-    rc = stretch_check(c, speed_permille, n, &any);
-    if (rc != NTTS_OK) return rc;
-    const int64_t cap = (int64_t)c->cfg.max_frames * c->cfg.hop_length;
-    int64_t Lmax = 0, s_max = 0;
-    for (int i = 0; i < n; ++i) {
-        if (n_samples[i] < 0 || n_samples[i] > in_stride)
-            return cfail(c, NTTS_EINVAL, "utterance %d: n_samples %d outside [0, in_stride %ld]", i, n_samples[i], (long)in_stride);
-        if (n_samples[i] > cap) return cfail(c, NTTS_EINVAL, "utterance %d: %d samples exceed the engine's %ld (max_frames x hop)", i, n_samples[i], (long)cap);
-        Lmax = std::max<int64_t>(Lmax, n_samples[i]);
-        s_max = std::max(s_max, stretch_len(n_samples[i], speed_permille[i]));
-    }
-    const int64_t row_len = w.out_len(s_max), k_max = stretch_frames(s_max);
-    if (out_stride < row_len) return cfail(c, NTTS_EINVAL, "out_stride %ld < %ld samples", (long)out_stride, (long)row_len);
-    if (positions && pos_stride < k_max) return cfail(c, NTTS_EINVAL, "pos_stride %ld < %ld frames", (long)pos_stride, (long)k_max);
-    if (!any) {                            // every row a copy: the output stage alone, nothing of this one is launched
-        rc = ntts_codec_convert(c, n, wav, in_stride, n_samples, fmt, out, out_stride, out_lens);
-        if (rc == NTTS_OK && positions)
-            for (int i = 0; i < n; ++i)
-                for (int64_t k = 0; k < stretch_frames(n_samples[i]); ++k) positions[(size_t)i * pos_stride + k] = (int32_t)(k * kStretchHop);
-        return rc;
-    }
-    for (int i = 0; i < n; ++i) out_lens[i] = (int32_t)w.out_len(stretch_len(n_samples[i], speed_permille[i]));
-    if (Lmax == 0) return NTTS_OK;
-    CHIP(c, hipSetDevice(c->device));
-    hipStream_t st = c->stream;
-    const size_t esz = w.plain() ? sizeof(float) : w.esz, row_bytes = (size_t)row_len * esz;
-    const int per_round = (int)std::min<int64_t>(std::min<int64_t>((int64_t)c->wav_cap / Lmax, c->max_rows), (int64_t)c->meta_cap / 3);
-    std::vector<int32_t> pos_host;
-    for (int i0 = 0; i0 < n; i0 += per_round) {
-        const int nb = std::min(per_round, n - i0);
-        const int k = c->meta_next;            // [samples nb][speed nb][stretched samples nb] through the page-locked meta ring
-        c->meta_next = (k + 1) % ntts_codec::kMetaStages;
-        if (c->meta_used[k]) CHIP(c, hipEventSynchronize(c->meta_ev[k]));
-        int* m = c->meta_host[k];
-        memcpy(m, n_samples + i0, (size_t)nb * sizeof(int));
-        memcpy(m + nb, speed_permille + i0, (size_t)nb * sizeof(int));
-        for (int i = 0; i < nb; ++i) m[2 * nb + i] = (int)stretch_len(n_samples[i0 + i], speed_permille[i0 + i]);
-        CHIP(c, hipMemcpyAsync(c->meta, m, 3 * (size_t)nb * sizeof(int), hipMemcpyHostToDevice, st));
-        c->meta_used[k] = true;
-        CHIP(c, hipEventRecord(c->meta_ev[k], st));
-        CHIP(c, hipMemcpy2DAsync(c->wav, (size_t)Lmax * sizeof(float), wav + (size_t)i0 * in_stride, (size_t)in_stride * sizeof(float),
-                                 (size_t)Lmax * sizeof(float), nb, hipMemcpyHostToDevice, st));
-        CHIP(c, hipEventRecord(c->ev[0], st));
-        rc = wav_stretch_launch(c, c->wav, (long)Lmax, c->meta, 1, c->meta + nb, c->meta + 2 * nb, nb, s_max, st);
-        if (rc != NTTS_OK) return rc;
-        const void* src = c->sbuf;
-        if (!w.plain()) {
-            rc = wav_format_launch(c, w, c->sbuf, (long)s_max, c->meta + 2 * nb, 1, nb, row_len, st);
-            if (rc != NTTS_OK) return rc;
-            src = c->fbuf;
-        }
-        CHIP(c, hipEventRecord(c->ev[1], st));
-        c->have_time = true;
-        CHIP(c, hipMemcpy2DAsync((char*)out + (size_t)i0 * out_stride * esz, (size_t)out_stride * esz, src, row_bytes, row_bytes, nb,
-                                 hipMemcpyDeviceToHost, st));
-        if (positions) {
-            pos_host.resize((size_t)nb * k_max);
-            CHIP(c, hipMemcpyAsync(pos_host.data(), c->spos, pos_host.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        }
-        CHIP(c, hipStreamSynchronize(st));
-        CHIP(c, hipGetLastError());
-        if (positions)                         // row i receives its own K_i positions, nothing behind them
-            for (int i = 0; i < nb; ++i)
-                memcpy(positions + (size_t)(i0 + i) * pos_stride, pos_host.data() + (size_t)i * k_max,
-                       (size_t)stretch_frames(m[2 * nb + i]) * sizeof(int32_t));
-    }
-    return NTTS_OK;
+    return wav_rounds(c, n, wav, in_stride, n_samples, post, out, out_stride, out_lens, positions, pos_stride, nullptr);
 }
 
 // GPU milliseconds of the two kernels of the most recent time stretch (search, render)
@@ -1110,122 +1089,29 @@ extern "C" int ntts_codec_last_stretch_timing(ntts_codec* c, float* search_ms, f
     return NTTS_OK;
 }
 
-// ntts_codec_decode_speed / ntts_codec_decode_dev_speed with a loudness per utterance (null, or every enable 0: the very same calls)
-extern "C" int ntts_codec_decode_loud(ntts_codec* c, int32_t n, const int32_t* codes, const int32_t* lens, const int32_t* speed_permille,
-                                      const ntts_wav_loudness* loudness, const ntts_wav_format* fmt, void* out, int64_t out_stride,
-                                      int32_t* out_lens) {
-    if (!c) return NTTS_EINVAL;
-    if (!codes || !out_lens) return cfail(c, NTTS_EINVAL, "null/empty argument");
-    WavFmt w;
-    const int rc = wav_fmt_check(c, fmt, &w);
-    if (rc != NTTS_OK) return rc;
-    return codec_decode_impl(c, n, codes, nullptr, 0, lens, out, out_stride, 0, nullptr, &w, out_lens, speed_permille, loudness);
-}
-
-extern "C" int ntts_codec_decode_dev_loud(ntts_codec* c, int32_t n, const int32_t* codes_dev, int32_t codes_stride, const int32_t* lens,
-                                          const int32_t* speed_permille, const ntts_wav_loudness* loudness, void* out, int64_t out_stride,
-                                          int32_t out_on_device, void* producer_stream, const ntts_wav_format* fmt, int32_t* out_lens) {
-    if (!c) return NTTS_EINVAL;
-    if (!codes_dev || !out_lens) return cfail(c, NTTS_EINVAL, "null/empty argument");
-    WavFmt w;
-    const int rc = wav_fmt_check(c, fmt, &w);
-    if (rc != NTTS_OK) return rc;
-    return codec_decode_impl(c, n, nullptr, codes_dev, codes_stride, lens, out, out_stride, out_on_device ? 2 : 1, (hipStream_t)producer_stream, &w,
-                             out_lens, speed_permille, loudness);
-}
-
-// The loudness stage (and the output stage behind it) alone on the caller's 24 kHz float32 waveforms, in ntts_codec_stretch's rounds.
-// loud == null: measure only (out / w unused).  measured (may be null): (L, peak, g) per row.
-static int loud_rounds(ntts_codec* c, int32_t n, const float* wav, int64_t in_stride, const int32_t* n_samples, const ntts_wav_loudness* loud,
-                       const WavFmt* w, void* out, int64_t out_stride, int64_t Lmax, double* measured) {
-    if (Lmax == 0) {                       // nothing but empty rows: unmeasurable, nothing to launch
-        if (measured)
-            for (int i = 0; i < n; ++i) { measured[3 * i] = NAN; measured[3 * i + 1] = 0.0; measured[3 * i + 2] = 1.0; }
-        return NTTS_OK;
-    }
-    CHIP(c, hipSetDevice(c->device));
-    hipStream_t st = c->stream;
-    const bool plain = !w || w->plain();
-    const size_t esz = plain ? sizeof(float) : w->esz;
-    const int64_t row_len = w ? w->out_len(Lmax) : Lmax;
-    const size_t row_bytes = (size_t)row_len * esz;
-    const int per_round = (int)std::min<int64_t>(std::min<int64_t>((int64_t)c->wav_cap / Lmax, c->max_rows), (int64_t)c->meta_cap / 5);
-    for (int i0 = 0; i0 < n; i0 += per_round) {
-        const int nb = std::min(per_round, n - i0);
-        const int k = c->meta_next;            // [samples nb][enable, target, peak, max gain x nb] through the page-locked meta ring
-        c->meta_next = (k + 1) % ntts_codec::kMetaStages;
-        if (c->meta_used[k]) CHIP(c, hipEventSynchronize(c->meta_ev[k]));
-        int* m = c->meta_host[k];
-        memcpy(m, n_samples + i0, (size_t)nb * sizeof(int));
-        if (loud) loud_pack(m + nb, loud + i0, nb);
-        CHIP(c, hipMemcpyAsync(c->meta, m, (loud ? 5 : 1) * (size_t)nb * sizeof(int), hipMemcpyHostToDevice, st));
-        c->meta_used[k] = true;
-        CHIP(c, hipEventRecord(c->meta_ev[k], st));
-        CHIP(c, hipMemcpy2DAsync(c->wav, (size_t)Lmax * sizeof(float), wav + (size_t)i0 * in_stride, (size_t)in_stride * sizeof(float),
-                                 (size_t)Lmax * sizeof(float), nb, hipMemcpyHostToDevice, st));
-        CHIP(c, hipEventRecord(c->ev[0], st));
-        int rc = wav_loud_launch(c, c->wav, (long)Lmax, c->meta, 1, loud ? c->meta + nb : nullptr, nb, Lmax, st);
-        if (rc != NTTS_OK) return rc;
-        const void* src = c->wav;
-        if (out && !plain) {
-            rc = wav_format_launch(c, *w, c->wav, (long)Lmax, c->meta, 1, nb, row_len, st);
-            if (rc != NTTS_OK) return rc;
-            src = c->fbuf;
-        }
-        CHIP(c, hipEventRecord(c->ev[1], st));
-        c->have_time = true;
-        if (out)
-            CHIP(c, hipMemcpy2DAsync((char*)out + (size_t)i0 * out_stride * esz, (size_t)out_stride * esz, src, row_bytes, row_bytes, nb,
-                                     hipMemcpyDeviceToHost, st));
-        if (measured) CHIP(c, hipMemcpyAsync(measured + 3 * (size_t)i0, c->lres, 3 * (size_t)nb * sizeof(double), hipMemcpyDeviceToHost, st));
-        CHIP(c, hipStreamSynchronize(st));
-        CHIP(c, hipGetLastError());
-    }
-    return NTTS_OK;
-}
-// what ntts_codec_stretch checks of its rows: every n_samples inside [0, in_stride] and the engine's longest utterance; *Lmax = the longest
-static int loud_rows_check(ntts_codec* c, int32_t n, int64_t in_stride, const int32_t* n_samples, int64_t* Lmax) {
-    const int64_t cap = (int64_t)c->cfg.max_frames * c->cfg.hop_length;
-    *Lmax = 0;
-    for (int i = 0; i < n; ++i) {
-        if (n_samples[i] < 0 || n_samples[i] > in_stride)
-            return cfail(c, NTTS_EINVAL, "utterance %d: n_samples %d outside [0, in_stride %ld]", i, n_samples[i], (long)in_stride);
-        if (n_samples[i] > cap) return cfail(c, NTTS_EINVAL, "utterance %d: %d samples exceed the engine's %ld (max_frames x hop)", i, n_samples[i], (long)cap);
-        *Lmax = std::max<int64_t>(*Lmax, n_samples[i]);
-    }
-    return NTTS_OK;
-}
-
+// The loudness stage (and the output stage behind it) alone on the caller's 24 kHz float32 waveforms: their twin.  measured (may be null): (L, peak, g)
+// per row.  Blocking.
 extern "C" int ntts_codec_normalize(ntts_codec* c, int32_t n, const float* wav, int64_t in_stride, const int32_t* n_samples,
                                     const ntts_wav_loudness* loudness, const ntts_wav_format* fmt, void* out, int64_t out_stride, int32_t* out_lens,
                                     double* measured) {
     if (!c) return NTTS_EINVAL;
     if (n < 1 || !wav || !n_samples || !loudness || !out || !out_lens || in_stride < 0) return cfail(c, NTTS_EINVAL, "null/empty argument");
-    WavFmt w;
-    int rc = wav_fmt_check(c, fmt, &w);
+    WavPost post;
+    int rc = wav_post_format(c, fmt, &post);
+    if (rc == NTTS_OK) rc = wav_post_stages(c, nullptr, loudness, n, &post);
     if (rc != NTTS_OK) return rc;
-    bool any;
-    rc = loud_check(c, loudness, n, &any);
-    if (rc != NTTS_OK) return rc;
-    int64_t Lmax;
-    rc = loud_rows_check(c, n, in_stride, n_samples, &Lmax);
-    if (rc != NTTS_OK) return rc;
-    const int64_t row_len = w.out_len(Lmax);
-    if (out_stride < row_len) return cfail(c, NTTS_EINVAL, "out_stride %ld < %ld samples", (long)out_stride, (long)row_len);
-    if (!any && !measured)                 // no row has the option on and nobody asks for the figures: the output stage alone
-        return ntts_codec_convert(c, n, wav, in_stride, n_samples, fmt, out, out_stride, out_lens);
-    for (int i = 0; i < n; ++i) out_lens[i] = (int32_t)w.out_len(n_samples[i]);
-    return loud_rounds(c, n, wav, in_stride, n_samples, loudness, &w, out, out_stride, Lmax, measured);
+    if (measured) post.loud = loudness;    // somebody asks for the figures: the stage runs even with no row on (every row at gain 1)
+    return wav_rounds(c, n, wav, in_stride, n_samples, post, out, out_stride, out_lens, nullptr, 0, measured);
 }
 
+// The measurement alone: no parameter block, no apply kernel, no output
 extern "C" int ntts_codec_measure_loudness(ntts_codec* c, int32_t n, const float* wav, int64_t in_stride, const int32_t* n_samples,
                                            double* measured) {
     if (!c) return NTTS_EINVAL;
     if (n < 1 || !wav || !n_samples || !measured || in_stride < 0) return cfail(c, NTTS_EINVAL, "null/empty argument");
-    int64_t Lmax;
-    const int rc = loud_rows_check(c, n, in_stride, n_samples, &Lmax);
-    if (rc != NTTS_OK) return rc;
-    return loud_rounds(c, n, wav, in_stride, n_samples, nullptr, nullptr, nullptr, 0, Lmax, measured);
+    WavPost post;
+    post.measure = true;
+    return wav_rounds(c, n, wav, in_stride, n_samples, post, nullptr, 0, nullptr, nullptr, 0, measured);
 }
 
 // GPU milliseconds of the measure and the apply kernel of the most recent loudness stage
@@ -1402,15 +1288,21 @@ struct ntts_wav_stream {
     std::string err;
 };
 static std::string g_wav_stream_err;
-static int wfail(ntts_wav_stream* ws, int code, const char* fmt, ...) {
+// a refusal of the stream objects below: the message into its slot (the object's own error string, or its kind's global one when there is no object)
+static int sfail(std::string& slot, int code, const char* fmt, ...) {
     char buf[512];
     va_list ap;
     va_start(ap, fmt);
     vsnprintf(buf, sizeof buf, fmt, ap);
     va_end(ap);
-    if (ws) ws->err = buf; else g_wav_stream_err = buf;
+    slot = buf;
     return code;
 }
+#define WHIP(slot, call)                                                                                     \
+    do {                                                                                                     \
+        hipError_t _s = (call);                                                                              \
+        if (_s != hipSuccess) return sfail(slot, NTTS_EHIP, "%s failed: %s", #call, hipGetErrorString(_s));   \
+    } while (0)
 extern "C" const char* ntts_wav_stream_last_error(const ntts_wav_stream* ws) { return ws ? ws->err.c_str() : g_wav_stream_err.c_str(); }
 
 extern "C" void ntts_wav_stream_destroy(ntts_wav_stream* ws) {
@@ -1421,15 +1313,15 @@ extern "C" void ntts_wav_stream_destroy(ntts_wav_stream* ws) {
 }
 
 extern "C" int ntts_wav_stream_create(ntts_codec* c, const ntts_wav_format* fmt, int32_t n_streams, int32_t max_chunk_samples, ntts_wav_stream** out) {
-    if (!c || !out) return wfail(nullptr, NTTS_EINVAL, "null argument");
+    if (!c || !out) return sfail(g_wav_stream_err, NTTS_EINVAL, "null argument");
     ntts_wav_stream* ws = new ntts_wav_stream();
     ws->c = c; ws->n = n_streams; ws->max_chunk = max_chunk_samples;
     int rc = wav_core_create(c, fmt, n_streams, max_chunk_samples, n_streams, &ws->k);
-    if (rc != NTTS_OK) { rc = wfail(nullptr, rc, "%s", c->err.c_str()); ntts_wav_stream_destroy(ws); return rc; }
+    if (rc != NTTS_OK) { rc = sfail(g_wav_stream_err, rc, "%s", c->err.c_str()); ntts_wav_stream_destroy(ws); return rc; }
     if (!wav_core_plain(ws->k) && hipMalloc((void**)&ws->in_dev, (size_t)n_streams * max_chunk_samples * sizeof(float)) != hipSuccess) {
         (void)hipGetLastError();
         ntts_wav_stream_destroy(ws);
-        return wfail(nullptr, NTTS_ENOMEM, "wav stream: no device memory for %d x %d samples", n_streams, max_chunk_samples);
+        return sfail(g_wav_stream_err, NTTS_ENOMEM, "wav stream: no device memory for %d x %d samples", n_streams, max_chunk_samples);
     }
     ws->seen.assign(n_streams, 0);
     *out = ws;
@@ -1438,29 +1330,30 @@ extern "C" int ntts_wav_stream_create(ntts_codec* c, const ntts_wav_format* fmt,
 
 extern "C" int ntts_wav_stream_count(const ntts_wav_format* fmt, int64_t n_in_total, int32_t last, int64_t* n_out_total) {
     const int rc = wav_stream_count_of(nullptr, fmt, n_in_total, last != 0, n_out_total);
-    if (rc != NTTS_OK) wfail(nullptr, rc, "%s", g_codec_create_err.c_str());
+    if (rc != NTTS_OK) sfail(g_wav_stream_err, rc, "%s", g_codec_create_err.c_str());
     return rc;
 }
 
 extern "C" int ntts_wav_stream_push(ntts_wav_stream* ws, int32_t n, const int32_t* stream, const float* wav, int64_t in_stride, const int32_t* n_samples,
                                     const int32_t* last, void* out, int64_t out_stride, int32_t* out_lens) {
     if (!ws) return NTTS_EINVAL;
-    if (n < 1 || !stream || !wav || !n_samples || !last || !out || !out_lens || in_stride < 0) return wfail(ws, NTTS_EINVAL, "null/empty argument");
+    std::string& err = ws->err;
+    if (n < 1 || !stream || !wav || !n_samples || !last || !out || !out_lens || in_stride < 0) return sfail(err, NTTS_EINVAL, "null/empty argument");
     // ---- every refusal first: nothing is run and no stream's state moves
     ++ws->call;
     int64_t Lmax = 0, Omax = 0;
     for (int i = 0; i < n; ++i) {
         const int u = stream[i];
-        if (u < 0 || u >= ws->n) return wfail(ws, NTTS_EINVAL, "entry %d: stream %d outside [0, %d)", i, u, ws->n);
-        if (ws->seen[u] == ws->call) return wfail(ws, NTTS_EINVAL, "entry %d: stream %d is named twice in one call", i, u);
+        if (u < 0 || u >= ws->n) return sfail(err, NTTS_EINVAL, "entry %d: stream %d outside [0, %d)", i, u, ws->n);
+        if (ws->seen[u] == ws->call) return sfail(err, NTTS_EINVAL, "entry %d: stream %d is named twice in one call", i, u);
         ws->seen[u] = ws->call;
         if (n_samples[i] < 0 || n_samples[i] > in_stride)
-            return wfail(ws, NTTS_EINVAL, "entry %d: n_samples %d outside [0, in_stride %ld]", i, n_samples[i], (long)in_stride);
-        if (n_samples[i] > ws->max_chunk) return wfail(ws, NTTS_EINVAL, "entry %d: n_samples %d above max_chunk_samples %d", i, n_samples[i], ws->max_chunk);
+            return sfail(err, NTTS_EINVAL, "entry %d: n_samples %d outside [0, in_stride %ld]", i, n_samples[i], (long)in_stride);
+        if (n_samples[i] > ws->max_chunk) return sfail(err, NTTS_EINVAL, "entry %d: n_samples %d above max_chunk_samples %d", i, n_samples[i], ws->max_chunk);
         Lmax = std::max<int64_t>(Lmax, n_samples[i]);
         Omax = std::max<int64_t>(Omax, wav_core_peek(ws->k, u, n_samples[i], last[i] != 0));
     }
-    if (out_stride < Omax) return wfail(ws, NTTS_EINVAL, "out_stride %ld < %ld samples", (long)out_stride, (long)Omax);
+    if (out_stride < Omax) return sfail(err, NTTS_EINVAL, "out_stride %ld < %ld samples", (long)out_stride, (long)Omax);
     for (int i = 0; i < n; ++i) out_lens[i] = (int32_t)wav_core_plan(ws->k, i, stream[i], n_samples[i], last[i] != 0, 0);
     if (wav_core_plain(ws->k)) {           // the native format: nothing to compute, nothing is launched
         for (int i = 0; i < n; ++i) memcpy((float*)out + (size_t)i * out_stride, wav + (size_t)i * in_stride, (size_t)n_samples[i] * sizeof(float));
@@ -1468,24 +1361,18 @@ extern "C" int ntts_wav_stream_push(ntts_wav_stream* ws, int32_t n, const int32_
     }
     ntts_codec* c = ws->c;
     const size_t esz = wav_core_esz(ws->k);
-#define WHIP(call)                                                                                           \
-    do {                                                                                                     \
-        hipError_t _s = (call);                                                                              \
-        if (_s != hipSuccess) return wfail(ws, NTTS_EHIP, "%s failed: %s", #call, hipGetErrorString(_s));     \
-    } while (0)
-    WHIP(hipSetDevice(c->device));
+    WHIP(err, hipSetDevice(c->device));
     hipStream_t st = c->stream;
     if (Lmax > 0)
-        WHIP(hipMemcpy2DAsync(ws->in_dev, (size_t)ws->max_chunk * sizeof(float), wav, (size_t)in_stride * sizeof(float), (size_t)Lmax * sizeof(float), n,
+        WHIP(err, hipMemcpy2DAsync(ws->in_dev, (size_t)ws->max_chunk * sizeof(float), wav, (size_t)in_stride * sizeof(float), (size_t)Lmax * sizeof(float), n,
                               hipMemcpyHostToDevice, st));
     const int rc = wav_core_run(ws->k, n, ws->in_dev, ws->max_chunk, st);      // (also with no output at all: the histories move on)
-    if (rc != NTTS_OK) return wfail(ws, rc, "%s", c->err.c_str());
+    if (rc != NTTS_OK) return sfail(err, rc, "%s", c->err.c_str());
     if (Omax > 0)
-        WHIP(hipMemcpy2DAsync(out, (size_t)out_stride * esz, wav_core_out(ws->k), (size_t)wav_core_out_stride(ws->k) * esz, (size_t)Omax * esz, n,
+        WHIP(err, hipMemcpy2DAsync(out, (size_t)out_stride * esz, wav_core_out(ws->k), (size_t)wav_core_out_stride(ws->k) * esz, (size_t)Omax * esz, n,
                               hipMemcpyDeviceToHost, st));
-    WHIP(hipStreamSynchronize(st));
-    WHIP(hipGetLastError());
-#undef WHIP
+    WHIP(err, hipStreamSynchronize(st));
+    WHIP(err, hipGetLastError());
     return NTTS_OK;
 }
 
@@ -1642,15 +1529,6 @@ struct ntts_speed_stream {
     std::string err;
 };
 static std::string g_speed_stream_err;
-static int ssfail(ntts_speed_stream* ss, int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    if (ss) ss->err = buf; else g_speed_stream_err = buf;
-    return code;
-}
 extern "C" const char* ntts_speed_stream_last_error(const ntts_speed_stream* ss) { return ss ? ss->err.c_str() : g_speed_stream_err.c_str(); }
 
 extern "C" void ntts_speed_stream_destroy(ntts_speed_stream* ss) {
@@ -1662,18 +1540,18 @@ extern "C" void ntts_speed_stream_destroy(ntts_speed_stream* ss) {
 }
 
 extern "C" int ntts_speed_stream_create(ntts_codec* c, const ntts_wav_format* fmt, int32_t n_streams, int32_t max_chunk_samples, ntts_speed_stream** out) {
-    if (!c || !out) return ssfail(nullptr, NTTS_EINVAL, "null argument");
+    if (!c || !out) return sfail(g_speed_stream_err, NTTS_EINVAL, "null argument");
     ntts_speed_stream* ss = new ntts_speed_stream();
     ss->c = c; ss->n = n_streams; ss->max_chunk = max_chunk_samples;
     // a stream names its speed with its first chunk: the rows are sized for the slowest one
     int rc = speed_core_create(c, n_streams, max_chunk_samples, 500, n_streams, &ss->k);
     if (rc == NTTS_OK) rc = wav_core_create(c, fmt, n_streams, (int)speed_core_out_stride(ss->k), n_streams, &ss->w);
-    if (rc != NTTS_OK) { rc = ssfail(nullptr, rc, "%s", c->err.c_str()); ntts_speed_stream_destroy(ss); return rc; }
+    if (rc != NTTS_OK) { rc = sfail(g_speed_stream_err, rc, "%s", c->err.c_str()); ntts_speed_stream_destroy(ss); return rc; }
     if (wav_core_plain(ss->w)) { wav_core_destroy(ss->w); ss->w = nullptr; }
     if (hipMalloc((void**)&ss->in_dev, (size_t)n_streams * max_chunk_samples * sizeof(float)) != hipSuccess) {
         (void)hipGetLastError();
         ntts_speed_stream_destroy(ss);
-        return ssfail(nullptr, NTTS_ENOMEM, "speed stream: no device memory for %d x %d samples", n_streams, max_chunk_samples);
+        return sfail(g_speed_stream_err, NTTS_ENOMEM, "speed stream: no device memory for %d x %d samples", n_streams, max_chunk_samples);
     }
     ss->seen.assign(n_streams, 0);
     ss->k0.assign(n_streams, 0); ss->k1.assign(n_streams, 0);
@@ -1682,9 +1560,9 @@ extern "C" int ntts_speed_stream_create(ntts_codec* c, const ntts_wav_format* fm
 }
 
 extern "C" int ntts_speed_stream_count(int32_t speed_permille, int64_t n_in_total, int32_t last, int64_t* n_out_total) {
-    if (!n_out_total || n_in_total < 0) return ssfail(nullptr, NTTS_EINVAL, "ntts_speed_stream_count: null / negative argument");
+    if (!n_out_total || n_in_total < 0) return sfail(g_speed_stream_err, NTTS_EINVAL, "ntts_speed_stream_count: null / negative argument");
     if (speed_permille < 500 || speed_permille > 2000)
-        return ssfail(nullptr, NTTS_EINVAL, "ntts_speed_stream_count: speed %d per mille outside [500, 2000]", speed_permille);
+        return sfail(g_speed_stream_err, NTTS_EINVAL, "ntts_speed_stream_count: speed %d per mille outside [500, 2000]", speed_permille);
     *n_out_total = speed_stream_count_of(speed_permille, n_in_total, last != 0);
     return NTTS_OK;
 }
@@ -1693,26 +1571,27 @@ extern "C" int ntts_speed_stream_push(ntts_speed_stream* ss, int32_t n, const in
                                       int64_t in_stride, const int32_t* n_samples, const int32_t* last, void* out, int64_t out_stride, int32_t* out_lens,
                                       int32_t* pos, int64_t pos_stride, int32_t* n_pos) {
     if (!ss) return NTTS_EINVAL;
+    std::string& err = ss->err;
     if (n < 1 || !stream || !speed_permille || !wav || !n_samples || !last || !out || !out_lens || in_stride < 0 || (pos && (!n_pos || pos_stride < 0)))
-        return ssfail(ss, NTTS_EINVAL, "null/empty argument");
+        return sfail(err, NTTS_EINVAL, "null/empty argument");
     // ---- every refusal first: nothing is run and no stream's state moves
     ++ss->call;
     int64_t Lmax = 0, Omax = 0, Kmax = 0;
     bool any = false;
     for (int i = 0; i < n; ++i) {
         const int u = stream[i], pm = speed_permille[i];
-        if (u < 0 || u >= ss->n) return ssfail(ss, NTTS_EINVAL, "entry %d: stream %d outside [0, %d)", i, u, ss->n);
-        if (ss->seen[u] == ss->call) return ssfail(ss, NTTS_EINVAL, "entry %d: stream %d is named twice in one call", i, u);
+        if (u < 0 || u >= ss->n) return sfail(err, NTTS_EINVAL, "entry %d: stream %d outside [0, %d)", i, u, ss->n);
+        if (ss->seen[u] == ss->call) return sfail(err, NTTS_EINVAL, "entry %d: stream %d is named twice in one call", i, u);
         ss->seen[u] = ss->call;
         if (n_samples[i] < 0 || n_samples[i] > in_stride)
-            return ssfail(ss, NTTS_EINVAL, "entry %d: n_samples %d outside [0, in_stride %ld]", i, n_samples[i], (long)in_stride);
-        if (n_samples[i] > ss->max_chunk) return ssfail(ss, NTTS_EINVAL, "entry %d: n_samples %d above max_chunk_samples %d", i, n_samples[i], ss->max_chunk);
-        if (pm < 500 || pm > 2000) return ssfail(ss, NTTS_EINVAL, "entry %d: speed %d per mille outside [500, 2000]", i, pm);
+            return sfail(err, NTTS_EINVAL, "entry %d: n_samples %d outside [0, in_stride %ld]", i, n_samples[i], (long)in_stride);
+        if (n_samples[i] > ss->max_chunk) return sfail(err, NTTS_EINVAL, "entry %d: n_samples %d above max_chunk_samples %d", i, n_samples[i], ss->max_chunk);
+        if (pm < 500 || pm > 2000) return sfail(err, NTTS_EINVAL, "entry %d: speed %d per mille outside [500, 2000]", i, pm);
         if (speed_core_pm(ss->k, u) && speed_core_pm(ss->k, u) != pm)
-            return ssfail(ss, NTTS_EINVAL, "entry %d: speed %d per mille, but stream %d's signal began at %d: a stream keeps its speed until its last chunk", i,
+            return sfail(err, NTTS_EINVAL, "entry %d: speed %d per mille, but stream %d's signal began at %d: a stream keeps its speed until its last chunk", i,
                           pm, u, speed_core_pm(ss->k, u));
         if (speed_core_total(ss->k, u) + n_samples[i] >= (int64_t)1 << 30)
-            return ssfail(ss, NTTS_EINVAL, "entry %d: stream %d's signal exceeds 2^30 samples", i, u);
+            return sfail(err, NTTS_EINVAL, "entry %d: stream %d's signal exceeds 2^30 samples", i, u);
         const int64_t s = speed_core_peek(ss->k, u, pm, n_samples[i], last[i] != 0);
         any = any || pm != 1000;
         Lmax = std::max<int64_t>(Lmax, n_samples[i]);
@@ -1720,8 +1599,8 @@ extern "C" int ntts_speed_stream_push(ntts_speed_stream* ss, int32_t n, const in
         const int64_t f0 = pm == 1000 ? stretch_frames(speed_core_total(ss->k, u)) : speed_stream_count_of(pm, speed_core_total(ss->k, u), false) / kStretchHop;
         Kmax = std::max(Kmax, stretch_frames(speed_stream_count_of(pm, speed_core_total(ss->k, u) + n_samples[i], last[i] != 0)) - f0);
     }
-    if (out_stride < Omax) return ssfail(ss, NTTS_EINVAL, "out_stride %ld < %ld samples", (long)out_stride, (long)Omax);
-    if (pos && pos_stride < Kmax) return ssfail(ss, NTTS_EINVAL, "pos_stride %ld < %ld frames", (long)pos_stride, (long)Kmax);
+    if (out_stride < Omax) return sfail(err, NTTS_EINVAL, "out_stride %ld < %ld samples", (long)out_stride, (long)Omax);
+    if (pos && pos_stride < Kmax) return sfail(err, NTTS_EINVAL, "pos_stride %ld < %ld frames", (long)pos_stride, (long)Kmax);
     for (int i = 0; i < n; ++i) {
         const int64_t s = speed_core_plan(ss->k, i, stream[i], speed_permille[i], n_samples[i], last[i] != 0, 0, &ss->k0[i], &ss->k1[i]);
         out_lens[i] = (int32_t)(ss->w ? wav_core_plan(ss->w, i, stream[i], (int)s, last[i] != 0, 0) : s);
@@ -1735,21 +1614,16 @@ extern "C" int ntts_speed_stream_push(ntts_speed_stream* ss, int32_t n, const in
         return NTTS_OK;
     }
     ntts_codec* c = ss->c;
-#define WHIP(call)                                                                                           \
-    do {                                                                                                     \
-        hipError_t _s = (call);                                                                              \
-        if (_s != hipSuccess) return ssfail(ss, NTTS_EHIP, "%s failed: %s", #call, hipGetErrorString(_s));    \
-    } while (0)
-    WHIP(hipSetDevice(c->device));
+    WHIP(err, hipSetDevice(c->device));
     hipStream_t st = c->stream;
     if (Lmax > 0)
-        WHIP(hipMemcpy2DAsync(ss->in_dev, (size_t)ss->max_chunk * sizeof(float), wav, (size_t)in_stride * sizeof(float), (size_t)Lmax * sizeof(float), n,
+        WHIP(err, hipMemcpy2DAsync(ss->in_dev, (size_t)ss->max_chunk * sizeof(float), wav, (size_t)in_stride * sizeof(float), (size_t)Lmax * sizeof(float), n,
                               hipMemcpyHostToDevice, st));
     const float* src = ss->in_dev;          // all at 1000: the stretch is not launched, the chunks go to the output stage as they are
     long src_stride = ss->max_chunk;
     if (any) {
         const int rc = speed_core_run(ss->k, n, ss->in_dev, ss->max_chunk, st);     // (also with no output at all: histories and states move on)
-        if (rc != NTTS_OK) return ssfail(ss, rc, "%s", c->err.c_str());
+        if (rc != NTTS_OK) return sfail(err, rc, "%s", c->err.c_str());
         src = speed_core_out(ss->k); src_stride = speed_core_out_stride(ss->k);
     }
     size_t esz = sizeof(float);
@@ -1757,19 +1631,18 @@ extern "C" int ntts_speed_stream_push(ntts_speed_stream* ss, int32_t n, const in
     long res_stride = src_stride;
     if (ss->w) {
         const int rc = wav_core_run(ss->w, n, src, src_stride, st);
-        if (rc != NTTS_OK) return ssfail(ss, rc, "%s", c->err.c_str());
+        if (rc != NTTS_OK) return sfail(err, rc, "%s", c->err.c_str());
         esz = wav_core_esz(ss->w); res = wav_core_out(ss->w); res_stride = wav_core_out_stride(ss->w);
     }
     if (Omax > 0)
-        WHIP(hipMemcpy2DAsync(out, (size_t)out_stride * esz, res, (size_t)res_stride * esz, (size_t)Omax * esz, n, hipMemcpyDeviceToHost, st));
+        WHIP(err, hipMemcpy2DAsync(out, (size_t)out_stride * esz, res, (size_t)res_stride * esz, (size_t)Omax * esz, n, hipMemcpyDeviceToHost, st));
     const long ps = speed_core_pos_stride(ss->k);
     if (pos && any) {
         ss->pos_host.resize((size_t)n * ps);
-        WHIP(hipMemcpyAsync(ss->pos_host.data(), speed_core_pos(ss->k), (size_t)n * ps * sizeof(int), hipMemcpyDeviceToHost, st));
+        WHIP(err, hipMemcpyAsync(ss->pos_host.data(), speed_core_pos(ss->k), (size_t)n * ps * sizeof(int), hipMemcpyDeviceToHost, st));
     }
-    WHIP(hipStreamSynchronize(st));
-    WHIP(hipGetLastError());
-#undef WHIP
+    WHIP(err, hipStreamSynchronize(st));
+    WHIP(err, hipGetLastError());
     if (pos && any)
         for (int i = 0; i < n; ++i)
             if (speed_permille[i] != 1000)

@@ -1466,34 +1466,46 @@ class CodecEngine:
             self._pin_ptr, self._pin_cap = ptr, nbytes
         return np.frombuffer((C.c_char * nbytes).from_address(self._pin_ptr.value), dtype=dtype, count=n)
 
-    def _decode_call(self, n: int, flat: np.ndarray, lens: np.ndarray, tmax: int, fmt, reuse_output: bool, pm: Optional[np.ndarray] = None,
-                     loud=None):
-        """One ntts_codec_decode / ntts_codec_decode_fmt / ntts_codec_decode_speed / ntts_codec_decode_loud call -> ([n, stride] array of the
-        format's dtype, samples per utterance).  pm: speeds per mille (int32 [n]) or None; loud: an ntts_wav_loudness array [n] or None."""
-        fc, dtype, native = fmt
-        i32p = C.POINTER(C.c_int32)
+    def _row_len(self, lens: np.ndarray, fc, pm: Optional[np.ndarray]) -> int:
+        """Samples of the longest utterance of a decode call in the format `fc`, behind the stretch at the speeds pm (None: all 1000)."""
         if pm is None:
-            stride = wav_out_len(self.hop_length * tmax, fc.sample_rate)
-        else:
-            pm = np.ascontiguousarray(pm, dtype=np.int32)
-            stride = wav_out_len(max(wav_stretch_len(self.hop_length * int(t), int(s)) for t, s in zip(lens, pm)), fc.sample_rate)
-        wav = (self._pinned(n * stride, dtype) if reuse_output else np.empty(n * stride, dtype=dtype)).reshape(n, stride)
-        if native and pm is None and loud is None:        # the plain entry point: the calls and the bits of an engine without the output stage
-            self._chk(self.lib.ntts_codec_decode(self.h, n, flat.ctypes.data_as(i32p), lens.ctypes.data_as(i32p),
-                                                 wav.ctypes.data_as(C.POINTER(C.c_float)), stride))
-            return wav, self.hop_length * lens.astype(np.int64)
+            return wav_out_len(self.hop_length * int(lens.max()), fc.sample_rate)
+        return wav_out_len(max(wav_stretch_len(self.hop_length * int(t), int(s)) for t, s in zip(lens, pm)), fc.sample_rate)
+
+    def _decode_entry(self, n: int, codes, lens: np.ndarray, fmt, pm: Optional[np.ndarray], loud, dst: int, stride: int, dev=None):
+        """The one C call of `decode` (codes: the packed int32 array) and of `decode_device` (codes: a device pointer; dev = (codes_stride,
+        destination on the device, producer stream)) -> samples per utterance.  The native format at speed 1 without a loudness is
+        ntts_codec_decode / ntts_codec_decode_dev: the calls and the bits of an engine without the stages.  Everything else is
+        ntts_codec_decode_loud / ntts_codec_decode_dev_loud with null for the stages that are off (the C side makes the very same calls for them).
+        A new stage of the output path gets its argument here."""
+        fc, _, native = fmt
+        i32p = C.POINTER(C.c_int32)
+        src = C.c_void_p(codes) if dev else codes.ctypes.data_as(i32p)
+        if native and pm is None and loud is None:
+            if dev:
+                self._chk(self.lib.ntts_codec_decode_dev(self.h, n, src, dev[0], lens.ctypes.data_as(i32p), C.c_void_p(dst), stride, dev[1],
+                                                         C.c_void_p(dev[2] or None)))
+            else:
+                self._chk(self.lib.ntts_codec_decode(self.h, n, src, lens.ctypes.data_as(i32p), C.cast(C.c_void_p(dst), C.POINTER(C.c_float)), stride))
+            return self.hop_length * lens.astype(np.int64)
         out_lens = np.zeros(n, dtype=np.int32)
-        if loud is not None:
-            self._chk(self.lib.ntts_codec_decode_loud(self.h, n, flat.ctypes.data_as(i32p), lens.ctypes.data_as(i32p),
-                                                      None if pm is None else pm.ctypes.data_as(i32p), loud, C.byref(fc),
-                                                      C.c_void_p(wav.ctypes.data), stride, out_lens.ctypes.data_as(i32p)))
-        elif pm is None:
-            self._chk(self.lib.ntts_codec_decode_fmt(self.h, n, flat.ctypes.data_as(i32p), lens.ctypes.data_as(i32p), C.byref(fc),
-                                                     C.c_void_p(wav.ctypes.data), stride, out_lens.ctypes.data_as(i32p)))
+        sp = None if pm is None else pm.ctypes.data_as(i32p)
+        if dev:
+            self._chk(self.lib.ntts_codec_decode_dev_loud(self.h, n, src, dev[0], lens.ctypes.data_as(i32p), sp, loud, C.c_void_p(dst), stride, dev[1],
+                                                          C.c_void_p(dev[2] or None), C.byref(fc), out_lens.ctypes.data_as(i32p)))
         else:
-            self._chk(self.lib.ntts_codec_decode_speed(self.h, n, flat.ctypes.data_as(i32p), lens.ctypes.data_as(i32p), pm.ctypes.data_as(i32p),
-                                                       C.byref(fc), C.c_void_p(wav.ctypes.data), stride, out_lens.ctypes.data_as(i32p)))
-        return wav, out_lens
+            self._chk(self.lib.ntts_codec_decode_loud(self.h, n, src, lens.ctypes.data_as(i32p), sp, loud, C.byref(fc), C.c_void_p(dst), stride,
+                                                      out_lens.ctypes.data_as(i32p)))
+        return out_lens
+
+    def _decode_call(self, n: int, flat: np.ndarray, lens: np.ndarray, fmt, reuse_output: bool, pm: Optional[np.ndarray] = None, loud=None):
+        """One decode call on packed host codes -> ([n, stride] array of the format's dtype, samples per utterance).  pm: speeds per mille
+        (int32 [n]) or None; loud: an ntts_wav_loudness array [n] or None."""
+        if pm is not None:
+            pm = np.ascontiguousarray(pm, dtype=np.int32)
+        stride = self._row_len(lens, fmt[0], pm)
+        wav = (self._pinned(n * stride, fmt[1]) if reuse_output else np.empty(n * stride, dtype=fmt[1])).reshape(n, stride)
+        return wav, self._decode_entry(n, flat, lens, fmt, pm, loud, wav.ctypes.data, stride)
 
     def decode(self, codes: Sequence[Sequence[int]], reuse_output: bool = False, sample_rate=None, encoding="f32",
                filter_width=None, speed=None, loudness=None, loudness_peak=LOUDNESS_PEAK_DEFAULT,
@@ -1502,10 +1514,10 @@ class CodecEngine:
         sample_rate (one of WAV_RATES) / encoding ("f32", "pcm16" -> int16, "mulaw" -> uint8) / filter_width (the resampler's
         lowpass_filter_width, 1..64, default 6) put the device output stage behind the pass: ceil(hop_length * len * rate / 24000) samples.
         speed (0.5 .. 2.0, one value or one per utterance; None = 1.0) puts the time stretch between the pass and the output stage: the pitch stays,
-        the utterance takes ceil(hop_length * len / speed) samples at 24 kHz (ntts_codec_decode_speed).
+        the utterance takes ceil(hop_length * len / speed) samples at 24 kHz.
         loudness (a target in LUFS, -70 .. 0, one value or one per utterance; None or a None entry = off) puts the BS.1770 loudness normalisation
         between the stretch and the output stage: one gain per utterance, held by loudness_max_gain (dB) and by the sample-peak ceiling
-        loudness_peak (dBFS) (ntts_codec_decode_loud).
+        loudness_peak (dBFS) (ntts_codec_decode_loud, the entry point of every call with a stage on).
         reuse_output=True returns views into an engine-owned pinned buffer (fast D2H, no copy): they are only valid
         until the next decode() call on this engine."""
         fmt = wav_format(sample_rate, encoding, filter_width)
@@ -1521,7 +1533,7 @@ class CodecEngine:
             lens = np.array([len(codes[j]) for j in grp], dtype=np.int32)
             flat = np.ascontiguousarray(np.concatenate([np.asarray(codes[j], dtype=np.int32) for j in grp]))
             # (pinned fast path when a single call covers the batch)
-            wav, out_lens = self._decode_call(len(grp), flat, lens, tmax, fmt, reuse_output and i == 0 and nb == len(order),
+            wav, out_lens = self._decode_call(len(grp), flat, lens, fmt, reuse_output and i == 0 and nb == len(order),
                                               None if pm is None else pm[grp], None if loud is None else _loudness_rows(loud, grp))
             for r, j in enumerate(grp):
                 out[j] = wav[r, : int(out_lens[r])]     # view into this call's buffer: no second copy
@@ -1545,31 +1557,24 @@ class CodecEngine:
         else:
             lens = np.ascontiguousarray(lens, dtype=np.int32)
             flat = np.ascontiguousarray(np.concatenate([codes[i, : lens[i]] for i in range(n)]), dtype=np.int32)
-        return self._decode_call(n, flat, lens, int(lens.max()), fmt, reuse_output, pm)[0]
+        return self._decode_call(n, flat, lens, fmt, reuse_output, pm)[0]
 
     def stretch_array(self, wav: np.ndarray, n_samples, speed, sample_rate=None, encoding="f32", filter_width=None, out_stride: Optional[int] = None,
                       pos_stride: Optional[int] = None):
         """The time stretch alone, and the output stage behind it (ntts_codec_stretch): wav [n, in_stride] float32 at 24 kHz, row i valid up to
         n_samples[i], speed one value or one per row -> ([n, out_stride] array of the encoding's dtype, samples per row, positions [n, pos_stride]
         int32, frames per row): row i's positions p_0 .. p_{K_i - 1} are the input offsets its output frames of 360 samples were taken from."""
-        fc, dtype, _ = wav_format(sample_rate, encoding, filter_width)
-        wav = np.ascontiguousarray(wav, dtype=np.float32)
+        fc, dtype, wav, n_samples = self._array_args(wav, n_samples, sample_rate, encoding, filter_width)
         n, in_stride = wav.shape
-        n_samples = np.ascontiguousarray(n_samples, dtype=np.int32)
-        if len(n_samples) != n:
-            raise ValueError(f"n_samples: {len(n_samples)} values for {n} waveforms")
         pm = speed_permille(speed, n)
         if pm is None:
             pm = np.full(n, 1000, dtype=np.int32)
         s_len = [wav_stretch_len(max(0, int(v)), int(s)) for v, s in zip(n_samples, pm)]
-        if out_stride is None:
-            out_stride = wav_out_len(max(s_len) if n else 0, fc.sample_rate)
+        buf, out_stride, out_lens = self._out_rows(n, out_stride, max(s_len) if n else 0, fc, dtype)
         if pos_stride is None:
             pos_stride = -(-(max(s_len) if n else 0) // STRETCH_HOP)
-        out_stride, pos_stride = int(out_stride), int(pos_stride)
-        buf = np.zeros(max(1, n * max(0, out_stride)), dtype=dtype)       # (never a null pointer, even for n rows of no samples)
+        pos_stride = int(pos_stride)
         pos = np.full(max(1, n * max(0, pos_stride)), -1, dtype=np.int32)
-        out_lens = np.zeros(n, dtype=np.int32)
         i32p = C.POINTER(C.c_int32)
         self._chk(self.lib.ntts_codec_stretch(self.h, n, wav.ctypes.data_as(C.POINTER(C.c_float)), in_stride, n_samples.ctypes.data_as(i32p),
                                               pm.ctypes.data_as(i32p), C.byref(fc), C.c_void_p(buf.ctypes.data), out_stride,
@@ -1580,15 +1585,11 @@ class CodecEngine:
     def stretch(self, wavs: Sequence[np.ndarray], speed, sample_rate=None, encoding="f32", filter_width=None) -> List[np.ndarray]:
         """24 kHz float waveforms (one 1-D array each; e.g. what a watermarker handed back) -> the same `speed` times faster, pitch kept, in the
         output format: what `decode` with these arguments would have produced from them."""
-        wavs = [np.asarray(w, dtype=np.float32).reshape(-1) for w in wavs]
-        if not wavs:
+        buf, n_samples = self._rows_of(wavs)
+        if not len(buf):
             return []
-        n_samples = np.array([len(w) for w in wavs], dtype=np.int32)
-        buf = np.zeros((len(wavs), max(1, int(n_samples.max()))), dtype=np.float32)
-        for r, w in enumerate(wavs):
-            buf[r, : len(w)] = w
         out, out_lens, _, _ = self.stretch_array(buf, n_samples, speed, sample_rate, encoding, filter_width)
-        return [out[r, : int(out_lens[r])] for r in range(len(wavs))]
+        return [out[r, : int(out_lens[r])] for r in range(len(buf))]
 
     def last_stretch_timing(self):
         """GPU milliseconds (search kernel, render kernel) of the most recent time stretch on this engine."""
@@ -1598,46 +1599,65 @@ class CodecEngine:
 
     @staticmethod
     def _rows_of(wavs):
-        """1-D waveforms -> ([n, longest] float32 with zeros behind each row, samples per row)."""
+        """Waveforms (one 1-D array each) -> ([n, longest] float32 with zeros behind each row, samples per row): what `stretch`, `convert`,
+        `normalize` and `measure_loudness` hand to the engine."""
+        wavs = [np.asarray(w, dtype=np.float32).reshape(-1) for w in wavs]
         n_samples = np.array([len(w) for w in wavs], dtype=np.int32)
-        buf = np.zeros((len(wavs), max(1, int(n_samples.max()))), dtype=np.float32)
+        buf = np.zeros((len(wavs), max(1, int(n_samples.max(initial=0)))), dtype=np.float32)
         for r, w in enumerate(wavs):
             buf[r, : len(w)] = w
         return buf, n_samples
+
+    @staticmethod
+    def _array_args(wav, n_samples, sample_rate, encoding, filter_width):
+        """The checked arguments of `stretch_array` and `convert_array` -> (WavFormatC, dtype, wav [n, in_stride] float32, n_samples int32 [n])."""
+        fc, dtype, _ = wav_format(sample_rate, encoding, filter_width)
+        wav = np.ascontiguousarray(wav, dtype=np.float32)
+        n, _ = wav.shape
+        n_samples = np.ascontiguousarray(n_samples, dtype=np.int32)
+        if len(n_samples) != n:
+            raise ValueError(f"n_samples: {len(n_samples)} values for {n} waveforms")
+        return fc, dtype, wav, n_samples
+
+    @staticmethod
+    def _out_rows(n: int, out_stride: Optional[int], longest: int, fc, dtype):
+        """Their destination -> (zeroed flat buffer of n rows, out_stride, out_lens); out_stride None: the `longest` row's samples in the format."""
+        out_stride = int(wav_out_len(longest, fc.sample_rate) if out_stride is None else out_stride)
+        buf = np.zeros(max(1, n * max(0, out_stride)), dtype=dtype)       # (never a null pointer, even for n rows of no samples)
+        return buf, out_stride, np.zeros(n, dtype=np.int32)
 
     def normalize(self, wavs: Sequence[np.ndarray], loudness, loudness_peak=LOUDNESS_PEAK_DEFAULT, loudness_max_gain=LOUDNESS_MAX_GAIN_DEFAULT,
                   sample_rate=None, encoding="f32", filter_width=None, return_measured: bool = False):
         """24 kHz float waveforms (one 1-D array each; e.g. what a watermarker handed back) -> the same at the loudness `decode` with these arguments
         would have given them, in the output format (ntts_codec_normalize).  return_measured=True: (waveforms, float64 [n, 3]) with row i =
         (integrated loudness in LUFS, NaN where the row is unmeasurable; sample peak; the gain applied)."""
-        wavs = [np.asarray(w, dtype=np.float32).reshape(-1) for w in wavs]
+        buf, n_samples = self._rows_of(wavs)
+        n = len(buf)
         fc, dtype, _ = wav_format(sample_rate, encoding, filter_width)
-        loud = loudness_params(loudness, loudness_peak, loudness_max_gain, len(wavs))
-        if not wavs:
+        loud = loudness_params(loudness, loudness_peak, loudness_max_gain, n)
+        if not n:
             return ([], np.zeros((0, 3))) if return_measured else []
         if loud is None:
-            loud = (WavLoudnessC * len(wavs))()
-        buf, n_samples = self._rows_of(wavs)
+            loud = (WavLoudnessC * n)()
         out_stride = wav_out_len(int(n_samples.max()), fc.sample_rate)
-        out = np.zeros((len(wavs), max(1, out_stride)), dtype=dtype)
-        out_lens = np.zeros(len(wavs), dtype=np.int32)
-        measured = np.zeros((len(wavs), 3), dtype=np.float64)
+        out = np.zeros((n, max(1, out_stride)), dtype=dtype)
+        out_lens = np.zeros(n, dtype=np.int32)
+        measured = np.zeros((n, 3), dtype=np.float64)
         i32p = C.POINTER(C.c_int32)
-        self._chk(self.lib.ntts_codec_normalize(self.h, len(wavs), buf.ctypes.data_as(C.POINTER(C.c_float)), buf.shape[1], n_samples.ctypes.data_as(i32p),
+        self._chk(self.lib.ntts_codec_normalize(self.h, n, buf.ctypes.data_as(C.POINTER(C.c_float)), buf.shape[1], n_samples.ctypes.data_as(i32p),
                                                 loud, C.byref(fc), C.c_void_p(out.ctypes.data), out.shape[1], out_lens.ctypes.data_as(i32p),
                                                 measured.ctypes.data_as(C.POINTER(C.c_double)) if return_measured else None))
-        res = [out[r, : int(out_lens[r])] for r in range(len(wavs))]
+        res = [out[r, : int(out_lens[r])] for r in range(n)]
         return (res, measured) if return_measured else res
 
     def measure_loudness(self, wavs: Sequence[np.ndarray]) -> np.ndarray:
         """24 kHz float waveforms -> float64 [n, 3]: row i = (BS.1770-4 integrated loudness in LUFS, NaN where unmeasurable; sample peak max|x|; 1.0).
         Nothing is scaled (ntts_codec_measure_loudness)."""
-        wavs = [np.asarray(w, dtype=np.float32).reshape(-1) for w in wavs]
-        measured = np.zeros((len(wavs), 3), dtype=np.float64)
-        if not wavs:
-            return measured
         buf, n_samples = self._rows_of(wavs)
-        self._chk(self.lib.ntts_codec_measure_loudness(self.h, len(wavs), buf.ctypes.data_as(C.POINTER(C.c_float)), buf.shape[1],
+        measured = np.zeros((len(buf), 3), dtype=np.float64)
+        if not len(buf):
+            return measured
+        self._chk(self.lib.ntts_codec_measure_loudness(self.h, len(buf), buf.ctypes.data_as(C.POINTER(C.c_float)), buf.shape[1],
                                                        n_samples.ctypes.data_as(C.POINTER(C.c_int32)), measured.ctypes.data_as(C.POINTER(C.c_double))))
         return measured
 
@@ -1650,17 +1670,9 @@ class CodecEngine:
     def convert_array(self, wav: np.ndarray, n_samples, sample_rate=None, encoding="f32", filter_width=None, out_stride: Optional[int] = None):
         """The output stage alone (ntts_codec_convert): wav [n, in_stride] float32 at 24 kHz, row i valid up to n_samples[i] (what follows is
         never read as signal) -> ([n, out_stride] array of the encoding's dtype, samples per row)."""
-        fc, dtype, _ = wav_format(sample_rate, encoding, filter_width)
-        wav = np.ascontiguousarray(wav, dtype=np.float32)
+        fc, dtype, wav, n_samples = self._array_args(wav, n_samples, sample_rate, encoding, filter_width)
         n, in_stride = wav.shape
-        n_samples = np.ascontiguousarray(n_samples, dtype=np.int32)
-        if len(n_samples) != n:
-            raise ValueError(f"n_samples: {len(n_samples)} values for {n} waveforms")
-        if out_stride is None:
-            out_stride = wav_out_len(max(0, int(n_samples.max())) if n else 0, fc.sample_rate)
-        out_stride = int(out_stride)
-        buf = np.zeros(max(1, n * max(0, out_stride)), dtype=dtype)       # (never a null pointer, even for n rows of no samples)
-        out_lens = np.zeros(n, dtype=np.int32)
+        buf, out_stride, out_lens = self._out_rows(n, out_stride, max(0, int(n_samples.max(initial=0))), fc, dtype)
         i32p = C.POINTER(C.c_int32)
         self._chk(self.lib.ntts_codec_convert(self.h, n, wav.ctypes.data_as(C.POINTER(C.c_float)), in_stride, n_samples.ctypes.data_as(i32p),
                                               C.byref(fc), C.c_void_p(buf.ctypes.data), out_stride, out_lens.ctypes.data_as(i32p)))
@@ -1670,15 +1682,11 @@ class CodecEngine:
     def convert(self, wavs: Sequence[np.ndarray], sample_rate=None, encoding="f32", filter_width=None) -> List[np.ndarray]:
         """24 kHz float waveforms (one 1-D array each; e.g. what a watermarker handed back) -> the same in another output format, as `decode`
         with these arguments would have produced from them."""
-        wavs = [np.asarray(w, dtype=np.float32).reshape(-1) for w in wavs]
-        if not wavs:
+        buf, n_samples = self._rows_of(wavs)
+        if not len(buf):
             return []
-        n_samples = np.array([len(w) for w in wavs], dtype=np.int32)
-        buf = np.zeros((len(wavs), max(1, int(n_samples.max()))), dtype=np.float32)
-        for r, w in enumerate(wavs):
-            buf[r, : len(w)] = w
         out, out_lens = self.convert_array(buf, n_samples, sample_rate, encoding, filter_width)
-        return [out[r, : int(out_lens[r])] for r in range(len(wavs))]
+        return [out[r, : int(out_lens[r])] for r in range(len(buf))]
 
     def stream_stretcher(self, n: int = 1, speed=1.0, sample_rate=None, encoding="f32", filter_width=None, max_chunk_samples: int = 16384) -> "SpeedStream":
         """The time stretch, and the output stage behind it, for `n` signals that arrive in chunks (ntts_speed_stream_*): the streaming twin of
@@ -1715,43 +1723,21 @@ class CodecEngine:
         destination (a view of the engine's pinned host buffer, or None when `wav_dev_ptr` names a device buffer);
         call sync() before reading it.  float32 at 24 kHz by default; with an output format (as `decode`) elements of the encoding's dtype,
         stride = wav_out_len(hop_length * max(lens), sample_rate) unless given, row i valid up to wav_out_len(hop_length * lens[i], sample_rate).
-        With speed (as `decode`; ntts_codec_decode_dev_speed) the lengths are those of the stretched utterances; loudness / loudness_peak /
-        loudness_max_gain as `decode` (ntts_codec_decode_dev_loud)."""
-        fc, dtype, native = wav_format(sample_rate, encoding, filter_width)
+        With speed (as `decode`) the lengths are those of the stretched utterances; loudness / loudness_peak / loudness_max_gain as `decode`
+        (ntts_codec_decode_dev_loud, the entry point of every call with a stage on)."""
+        fmt = wav_format(sample_rate, encoding, filter_width)
         lens = np.ascontiguousarray(lens, dtype=np.int32)
         n = len(lens)
         pm = speed_permille(speed, n)
         loud = loudness_params(loudness, loudness_peak, loudness_max_gain, n)
-        if pm is None:
-            longest = self.hop_length * int(lens.max())
-        else:
-            longest = max(wav_stretch_len(self.hop_length * int(t), int(s)) for t, s in zip(lens, pm))
-        stride = int(wav_stride or wav_out_len(longest, fc.sample_rate))
+        stride = int(wav_stride or self._row_len(lens, fmt[0], pm))
         wav = None
         if wav_dev_ptr is None:
-            wav = self._pinned(n * stride, dtype).reshape(n, stride)
+            wav = self._pinned(n * stride, fmt[1]).reshape(n, stride)
             dst, on_dev = wav.ctypes.data, 0
         else:
             dst, on_dev = wav_dev_ptr, 1
-        i32p = C.POINTER(C.c_int32)
-        if loud is not None:
-            out_lens = np.zeros(n, dtype=np.int32)
-            self._chk(self.lib.ntts_codec_decode_dev_loud(self.h, n, C.c_void_p(codes_dev_ptr), codes_stride, lens.ctypes.data_as(i32p),
-                                                          None if pm is None else pm.ctypes.data_as(i32p), loud, C.c_void_p(dst), stride, on_dev,
-                                                          C.c_void_p(producer_stream or None), C.byref(fc), out_lens.ctypes.data_as(i32p)))
-        elif native and pm is None:
-            self._chk(self.lib.ntts_codec_decode_dev(self.h, n, C.c_void_p(codes_dev_ptr), codes_stride, lens.ctypes.data_as(i32p),
-                                                     C.c_void_p(dst), stride, on_dev, C.c_void_p(producer_stream or None)))
-        elif pm is None:
-            out_lens = np.zeros(n, dtype=np.int32)
-            self._chk(self.lib.ntts_codec_decode_dev_fmt(self.h, n, C.c_void_p(codes_dev_ptr), codes_stride, lens.ctypes.data_as(i32p),
-                                                         C.c_void_p(dst), stride, on_dev, C.c_void_p(producer_stream or None), C.byref(fc),
-                                                         out_lens.ctypes.data_as(i32p)))
-        else:
-            out_lens = np.zeros(n, dtype=np.int32)
-            self._chk(self.lib.ntts_codec_decode_dev_speed(self.h, n, C.c_void_p(codes_dev_ptr), codes_stride, lens.ctypes.data_as(i32p),
-                                                           pm.ctypes.data_as(i32p), C.c_void_p(dst), stride, on_dev,
-                                                           C.c_void_p(producer_stream or None), C.byref(fc), out_lens.ctypes.data_as(i32p)))
+        self._decode_entry(n, codes_dev_ptr, lens, fmt, pm, loud, dst, stride, dev=(codes_stride, on_dev, producer_stream))
         return wav
 
     def sync(self):
